@@ -32,8 +32,18 @@ One JSON line on stdout (rank 0), at most ~5 KB -- the driver's record keeps the
   legs          LAST in the line: value / roofline.frac / kernel / cpu baseline of every other half of BASELINE's metric --
                 mh (+ mh_8192), c5 (+ c5_32768), smc, c3_65536, c3_8192, hmc_fd_dense (the reference's arithmetic verbatim; the only
                 GPU figure the CPU baseline may be divided into), hmc_8192.
-The verbose document (every leg's notes, spreads, sub-objects) goes to --full-out (default gpurun_out/bench_full.json) and, with
---full, to stdout instead of the compact line; the committed copy is profiles/roundN_bench_full.json.
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up and clock spin-up, the W warmup
+transitions, ONE timed region of exactly K transitions (`--repeats` defaults to 1), `--dump-outputs DIR` if given, and the line with
+the contract keys and the headline kernel's `roofline` (HIP events of the timed launches + committed counter passes: no run of its
+own).  Everything else -- the R-hat / ESS exchange and `check` of the timed draws, the other legs, `extras`, `validity`, the CPU
+baselines, `--repeats` 5 -- runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path handed its caller after its last transition (the draw row that transition wrote, the
+per-chain log-joint and step size) as float64 .npy files; the inputs depend only on the arguments (fixed seeds, Philox keyed by chain).
+
+The verbose document (every leg's notes, spreads, sub-objects) goes to --full-out (with --full, default bench_out/bench_full.json;
+a plain run writes none unless asked) and, with --print-document, to stdout instead of the compact line; the committed copy is
+profiles/roundN_bench_full.json.
 """
 from __future__ import annotations
 
@@ -65,7 +75,8 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K-transition timed region runs (median = value)")
+    ap.add_argument("--repeats", type=int, default=None, help="how many times the K-transition timed region runs (median = value); "
+                    "default 1, or 5 with --full")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --chains per rank; strong: --chains in total, sharded over the ranks")
     ap.add_argument("--chains", type=int, default=CHAINS_PER_GPU, help="chains per GPU (weak) / in total (strong)")
@@ -76,14 +87,24 @@ def parse(argv=None):
     ap.add_argument("--leapfrog", type=int, default=16, help="L (HMCConfig::default is 16; other values are for experiments only)")
     ap.add_argument("--spinup", type=float, default=0.4, help="seconds of untimed throw-away transitions on a scratch engine before the measured "
                     "engine starts (the GPU's clocks settle over the first tens of ms of f64 load); 0 = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline leg only (no MH / SMC / C3 / C5 / dense / validity legs)")
-    ap.add_argument("--full", action="store_true", help="print the verbose document (every leg's notes, spreads and sub-objects) instead of the compact line")
-    ap.add_argument("--full-out", default=os.environ.get("FG_BENCH_FULL_OUT", os.path.join("gpurun_out", "bench_full.json")),
-                    help="where the verbose document is written beside the compact line ('' = nowhere)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: R-hat / ESS of the timed "
+                    "draws, the MH / SMC / C3 / C5 / dense / 8192-chain legs, extras, validity, the CPU baselines; 5 timed regions")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline leg only (no MH / SMC / C3 / C5 / dense / validity legs)")
+    ap.add_argument("--print-document", action="store_true", help="print the verbose document (every leg's notes, spreads and sub-objects) instead of the compact line")
+    ap.add_argument("--full-out", default=None, help="where the verbose document is written beside the compact line ('' = nowhere; "
+                    "default: $FG_BENCH_FULL_OUT, else bench_out/bench_full.json with --full and nowhere without)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the timed path's outputs of its last step to DIR/<name>.npy")
     ap.add_argument("--cpu-chains", type=int, default=4096)
     ap.add_argument("--cpu-transitions", type=int, default=64)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.full_out is None:
+        args.full_out = os.environ.get("FG_BENCH_FULL_OUT", os.path.join("bench_out", "bench_full.json") if args.full else "")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ rank launcher
@@ -328,6 +349,17 @@ def stepped(torch, stream, step_fn, total, per_launch):
     return events
 
 
+def ring_step(eng, n, done, slab, off):
+    """n sampling transitions of the timed region, from its transition `done` on, into the draw slab [rows][d][C]: transition s writes row
+    (s + off) % rows; a launch that would run past the last row is split there."""
+    rows = slab.shape[0]
+    r0 = (done + off) % rows
+    n1 = min(n, rows - r0)
+    eng.hmc_step(n1, slab[r0].data_ptr())
+    if n > n1:
+        eng.hmc_step(n - n1, slab[0].data_ptr())
+
+
 def full_launch_ms(events):
     ms = [(e0.elapsed_time(e1), n) for e0, e1, n in events]
     n0 = events[0][2]
@@ -390,20 +422,29 @@ def run_rank(args):
     eng = E.Engine(cp, C, seed=1, chain_offset=rank * C, device=local_rank)
     stream = X.stream
     eng.set_stream(stream.cuda_stream)                    # kernels + torch events share one stream
-    slab = K * d * C * 8
-    R = max(1, min(R, int(100e9 // max(1, slab))))        # consecutive draw slabs of the R timed regions (<= 100 GB of the 288 GB)
-    draws = torch.empty((R, K, d, C), dtype=torch.float64, device=f"cuda:{local_rank}")
+    # every timed transition writes its draw row [d][C] to HBM.  A slab holds K rows while they fit in 100 GB; beyond that it is a ring of
+    # `rows` rows, offset so that the last `rows` transitions of a region end in order at its end (the same bytes written per transition)
+    row_bytes = d * C * 8
+    rows = min(K, max(1, int(100e9 // row_bytes)))
+    if rows < min(K, args.launch):
+        raise SystemExit(f"bench.py: a draw slab of {rows} rows cannot take a launch of {args.launch} transitions: lower --launch")
+    R = max(1, min(R, int(100e9 // (rows * row_bytes))))   # consecutive draw slabs of the R timed regions (<= 100 GB of the 288 GB)
+    draws = torch.empty((R, rows, d, C), dtype=torch.float64, device=f"cuda:{local_rank}")
+    ring_off = (-K) % rows
 
     eng.hmc_init(cfg, Wn)
     draws.zero_()                                         # the output buffer's pages are touched before anything is timed
     # ---- clock spin-up first: throw-away transitions of the same kernel on a scratch engine (own state, own seed; the measured
     # engine is not touched), so that the W warmup and the timed transitions run at the clocks the GPU settles to under this
     # load rather than on its way there.  The measured engine's W warmup transitions then run directly before the timed regions.
+    # Its first launch writes draw rows into the first timed slab (which the timed transitions overwrite), so that the first timed
+    # launch does not meet rows no kernel has written yet.
     scratch = None
     if args.spinup > 0:
         scratch = E.Engine(cp, C, seed=987654321, chain_offset=rank * C, device=local_rank)
         scratch.set_stream(stream.cuda_stream)
         scratch.hmc_init(cfg, 0)
+        scratch.hmc_step(min(args.launch, rows), draws[0].data_ptr())
         t_sp = time.perf_counter()
         while time.perf_counter() - t_sp < args.spinup:
             scratch.hmc_step(4 * args.launch)
@@ -414,7 +455,7 @@ def run_rank(args):
     events, dts = [], []
     for r in range(R):
         ev = []
-        dts.append(clock.region(lambda: ev.extend(stepped(torch, stream, lambda n, done: eng.hmc_step(n, draws[r, done].data_ptr()), K, args.launch))))
+        dts.append(clock.region(lambda: ev.extend(stepped(torch, stream, lambda n, done: ring_step(eng, n, done, draws[r], ring_off), K, args.launch))))
         events.extend(ev)
     kernel = eng.hmc_last_kernel()
     launch_ms, n_launch = full_launch_ms(events)
@@ -423,7 +464,106 @@ def run_rank(args):
     dt = float(np.median(dts))
     last = draws[R - 1]
 
-    # ---- after the timed regions: the ONLY cross-chain step -- split R-hat / multichain ESS of the last slab.  Each rank reduces
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, draws[R - 1, rows - 1].cpu().numpy(), eng.hmc_log_joint(), eng.hmc_step_sizes(), world, rank)
+    check, failed = check_timed_draws(X, eng, last, rows, d) if args.full else (None, False)    # (of the last `rows` transitions)
+    eng.close()
+    del draws, last
+
+    value = world * C * K * L / dt
+    # ---- roofline of the dominant kernel: algorithmic f64 work / HIP-event time
+    n_stmt = 2 * N_SITES                                                      # S + O statements of the model
+    evals_sparse = (2 * d * (L + 1)) * 2 + n_stmt                             # 2 signs x 2 dependent statements per coordinate per gradient + endpoint score
+    evals_dense = (2 * d * (L + 1)) * n_stmt + n_stmt                         # SURVEY 8d: 2 d (S + O) per gradient
+    evals_dense_executed = (L + 1) * (n_stmt + 2 * 2 * d)                    # the dense kernel evaluates every statement once per gradient + the moved ones at +-h; the rest of the two scoring runs is additions
+    evals = {E.GRAD_FD_SPARSE: evals_sparse, E.GRAD_FD_DENSE: evals_dense_executed, E.GRAD_ANALYTIC: d * (L + 1) * 2 + n_stmt}[mode]
+    achieved_tflops = C * n_launch * evals * FLOPS_PER_NORMAL_LOGPDF / (launch_ms * 1e-3) / 1e12
+    alg_bytes_per_launch = C * n_launch * (L * 32 * d + 8 * d + 16)           # SURVEY 8d: 32 d B / leapfrog step (+ draw row, lj, eps)
+    ent, src = pmc_entry(f"hmc|normal32|{C}|{args.grad}|L{L}")
+    out = {
+        "metric": "hmc_leapfrog_steps_per_sec", "value": value, "unit": "leapfrog-steps/s", "n_gpus": world,
+        "steps": K, "warmup": Wn, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "timed_regions": {"repeats": R, "steps_each": K, "seconds": spread(dts), "value": spread([world * C * K * L / t for t in dts]),
+                          "note": "value / ms_per_step are those of the MEDIAN region; every region is K transitions between barrier + synchronize, MAX over ranks"},
+        "config": {"workload": "C2-normal32: hmc_chain, 32-site conjugate Normal (x#i~N(0,1), y#i~N(x#i,0.5)=0.2i-1), "
+                               f"{C} chains/GPU, L=16, HMCConfig::default", "chains_per_gpu": C, "chains_total": world * C, "n_sites": N_SITES,
+                   "n_leapfrog": L, "grad": args.grad, "grad_note": "fd_sparse = the engine's default in the C ABI, Python and bench; the reference-verbatim dense "
+                   "mode is the `hmc_fd_dense` leg", "transitions_per_launch": n_launch, "clock_spinup_seconds": args.spinup,
+                   "sharding": (f"{args.scaling}: chains x{world}" if world > 1 else "single GPU")},
+        "roofline": {"bound": "valu_f64", "achieved": achieved_tflops, "peak": F64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": achieved_tflops / F64_VALU_PEAK_TFLOPS, "traffic": traffic_from_pmc(ent, n_launch), "traffic_source": src,
+                     "kernel": kernel, "avg_launch_ms": launch_ms,
+                     "logpdf_evals_per_transition": evals, "flops_per_logpdf": FLOPS_PER_NORMAL_LOGPDF,
+                     "note": "achieved = log-pdf evaluations the launch performs x 8 flops / HIP-event time; peak = f64 vector FMA peak "
+                             "(2 flops/instr at 2.4 GHz) -- the arithmetic is unfused add/mul (reference rounding, 1 flop/instr) and the clock "
+                             "sits near 2.1 GHz under f64 load, so ~36 TFLOP/s is the ceiling of this instruction mix.  traffic = measured "
+                             "FETCH_SIZE + WRITE_SIZE per launch (separate rocprofv3 --pmc passes)",
+                     "executed": executed_from_pmc(ent, n_launch, launch_ms * 1e-3), "executed_source": src,
+                     "dense_semantics": {"logpdf_evals_per_transition": evals_dense,
+                                         "note": "SURVEY 8d's 2 d (S+O) log-pdfs per gradient are the two whole scoring runs of grad_log_joint; that arithmetic is the "
+                                                 "`hmc_fd_dense` leg -- the sparse default never forms the terms that cancel in the reference's subtraction"},
+                     "hbm_nominal": {"achieved": alg_bytes_per_launch / (launch_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "note": "SURVEY 8d algorithmic bytes (32 d B per leapfrog step, as if q and p round-tripped HBM) / time: NOT a "
+                                             "claim -- q, p stay in registers for a whole trajectory and the kernel is not HBM bound"}},
+        "incl_warmup": {"leapfrog_steps_per_sec": world * C * (K + Wn) * L / (dt + t_warm) if Wn > 0 else value,
+                        "warmup_seconds": t_warm, "note": "SURVEY 8d counts leapfrog steps over warmup + sampling; `value` follows the bench contract (K timed "
+                                                          "sampling transitions after W untimed warmup transitions)"},
+    }
+    if check is not None:
+        out["check"] = check
+    progress(rank, f"hmc leg done: {value:.4g} leapfrog-steps/s over {world} rank(s) [{kernel}]")
+    if failed:
+        # a thread of this process may still be inside RCCL: no further leg, no further collective
+        out["check"]["note"] += "; the cross-rank exchange FAILED -- remaining legs skipped"
+        if rank == 0:
+            emit(args, out)
+        return EXIT_DIAGNOSTICS_FAILED
+    if args.full and not args.no_extras:
+        out["mh"] = leg_mh(X)
+        progress(rank, "mh leg done")
+        out["smc"] = leg_smc(X)
+        progress(rank, "smc leg done")
+        out["c3"] = leg_c3(X)
+        progress(rank, "c3 leg done")
+        out["c5"] = leg_c5(X)
+        progress(rank, "c5 leg done")
+        if rank == 0:
+            if args.scaling == "weak" and C != 8192:
+                out["hmc_8192"] = leg_hmc_small(X, 8192)
+                progress(rank, "hmc at 8192 chains done")
+            out["hmc_fd_dense"] = leg_dense(X)
+            progress(rank, "dense leg done")
+            out["extras"] = extras(X)
+            progress(rank, "extras done")
+            out["validity"] = validity(E, W, D, local_rank)
+            progress(rank, "validity leg done")
+    if rank == 0:
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            gpu_dense = out.get("hmc_fd_dense", {}).get("value")
+            out["cpu_baseline"] = cpu_baseline_hmc(args, gpu_dense)
+            if "hmc_fd_dense" in out:
+                out["hmc_fd_dense"]["cpu_baseline"] = {k: out["cpu_baseline"][k] for k in ("value", "unit", "cores", "kind", "sample")}
+                out["hmc_fd_dense"]["vs_cpu_baseline"] = gpu_dense / out["cpu_baseline"]["value"]
+            if "mh" in out:
+                out["mh"]["cpu_baseline"] = cpu_baseline_mh()
+            if "smc" in out:
+                out["smc"]["cpu_baseline"] = cpu_baseline_smc()
+            if "c3" in out:
+                out["c3"]["cpu_baseline"] = cpu_baseline_c3(host_cores())
+        emit(args, out)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def check_timed_draws(X, eng, last, K, d):
+    """--full: statistics of the last timed region's draws [K][d][C] and the run's only cross-chain step -- split R-hat / multichain
+    ESS.  Returns (the line's `check`, failed: the cross-rank exchange did not return)."""
+    E, W, D, torch, dist = X.E, X.W, X.D, X.torch, X.dist
+    world, rank, one_device, coll_dev = X.world, X.rank, X.one_device, X.coll_dev
+    # the ONLY cross-chain step -- split R-hat / multichain ESS of the last slab.  Each rank reduces
     # its own draws to chain sums on its GPU; the library all-reduces 6 d + 2 d doubles (+ 32 d per chunk of lags) over RCCL / xGMI
     # (fg_diag_rhat_ess; communicator created from an id that rank 0 obtains and torch.distributed's store hands out).
     t_diag = time.perf_counter()
@@ -486,99 +626,34 @@ def run_rank(args):
     v = last.var(dim=(0, 2)).cpu().numpy()
     _, tm, tv = W.normal_sites_truth(N_SITES)
     mean_err, var_err = float(np.abs(m - tm).max()), float(np.abs(v - tv).max())
-    eng.close()
-    del draws, last
+    return {"posterior_mean_max_abs_err": mean_err, "posterior_var_max_abs_err": var_err,
+            "accept_rate": st.accept_rate, "mean_step_size": st.mean_step_size, "n_divergent": int(st.n_divergent),
+            "split_rhat_max": float(np.max(rhat)), "ess_min": float(np.min(ess)), "chains_in_rhat": int(n_chains_diag),
+            "diagnostics_seconds": t_diag, "diagnostics_path": diag_path, "diagnostics_exchange_bytes_per_rank": int(exch),
+            "note": "statistics of the K draws of the last timed region: with few steps / a short warmup they are NOT the 1e-3 evidence (a chain of "
+                    "20 draws after 5 warmup transitions has not mixed) -- see `validity`"}, failed
 
-    value = world * C * K * L / dt
-    # ---- roofline of the dominant kernel: algorithmic f64 work / HIP-event time
-    n_stmt = 2 * N_SITES                                                      # S + O statements of the model
-    evals_sparse = (2 * d * (L + 1)) * 2 + n_stmt                             # 2 signs x 2 dependent statements per coordinate per gradient + endpoint score
-    evals_dense = (2 * d * (L + 1)) * n_stmt + n_stmt                         # SURVEY 8d: 2 d (S + O) per gradient
-    evals_dense_executed = (L + 1) * (n_stmt + 2 * 2 * d)                    # the dense kernel evaluates every statement once per gradient + the moved ones at +-h; the rest of the two scoring runs is additions
-    evals = {E.GRAD_FD_SPARSE: evals_sparse, E.GRAD_FD_DENSE: evals_dense_executed, E.GRAD_ANALYTIC: d * (L + 1) * 2 + n_stmt}[mode]
-    achieved_tflops = C * n_launch * evals * FLOPS_PER_NORMAL_LOGPDF / (launch_ms * 1e-3) / 1e12
-    alg_bytes_per_launch = C * n_launch * (L * 32 * d + 8 * d + 16)           # SURVEY 8d: 32 d B / leapfrog step (+ draw row, lj, eps)
-    ent, src = pmc_entry(f"hmc|normal32|{C}|{args.grad}|L{L}")
-    out = {
-        "metric": "hmc_leapfrog_steps_per_sec", "value": value, "unit": "leapfrog-steps/s", "n_gpus": world,
-        "steps": K, "warmup": Wn, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": args.scaling,
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "timed_regions": {"repeats": R, "steps_each": K, "seconds": spread(dts), "value": spread([world * C * K * L / t for t in dts]),
-                          "note": "value / ms_per_step are those of the MEDIAN region; every region is K transitions between barrier + synchronize, MAX over ranks"},
-        "config": {"workload": "C2-normal32: hmc_chain, 32-site conjugate Normal (x#i~N(0,1), y#i~N(x#i,0.5)=0.2i-1), "
-                               f"{C} chains/GPU, L=16, HMCConfig::default", "chains_per_gpu": C, "chains_total": world * C, "n_sites": N_SITES,
-                   "n_leapfrog": L, "grad": args.grad, "grad_note": "fd_sparse = the engine's default in the C ABI, Python and bench; the reference-verbatim dense "
-                   "mode is the `hmc_fd_dense` leg", "transitions_per_launch": n_launch, "clock_spinup_seconds": args.spinup,
-                   "sharding": (f"{args.scaling}: chains x{world}" if world > 1 else "single GPU")},
-        "roofline": {"bound": "valu_f64", "achieved": achieved_tflops, "peak": F64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved_tflops / F64_VALU_PEAK_TFLOPS, "traffic": traffic_from_pmc(ent, n_launch), "traffic_source": src,
-                     "kernel": kernel, "avg_launch_ms": launch_ms,
-                     "logpdf_evals_per_transition": evals, "flops_per_logpdf": FLOPS_PER_NORMAL_LOGPDF,
-                     "note": "achieved = log-pdf evaluations the launch performs x 8 flops / HIP-event time; peak = f64 vector FMA peak "
-                             "(2 flops/instr at 2.4 GHz) -- the arithmetic is unfused add/mul (reference rounding, 1 flop/instr) and the clock "
-                             "sits near 2.1 GHz under f64 load, so ~36 TFLOP/s is the ceiling of this instruction mix.  traffic = measured "
-                             "FETCH_SIZE + WRITE_SIZE per launch (separate rocprofv3 --pmc passes)",
-                     "executed": executed_from_pmc(ent, n_launch, launch_ms * 1e-3), "executed_source": src,
-                     "dense_semantics": {"logpdf_evals_per_transition": evals_dense,
-                                         "note": "SURVEY 8d's 2 d (S+O) log-pdfs per gradient are the two whole scoring runs of grad_log_joint; that arithmetic is the "
-                                                 "`hmc_fd_dense` leg -- the sparse default never forms the terms that cancel in the reference's subtraction"},
-                     "hbm_nominal": {"achieved": alg_bytes_per_launch / (launch_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                     "note": "SURVEY 8d algorithmic bytes (32 d B per leapfrog step, as if q and p round-tripped HBM) / time: NOT a "
-                                             "claim -- q, p stay in registers for a whole trajectory and the kernel is not HBM bound"}},
-        "incl_warmup": {"leapfrog_steps_per_sec": world * C * (K + Wn) * L / (dt + t_warm) if Wn > 0 else value,
-                        "warmup_seconds": t_warm, "note": "SURVEY 8d counts leapfrog steps over warmup + sampling; `value` follows the bench contract (K timed "
-                                                          "sampling transitions after W untimed warmup transitions)"},
-        "check": {"posterior_mean_max_abs_err": mean_err, "posterior_var_max_abs_err": var_err,
-                  "accept_rate": st.accept_rate, "mean_step_size": st.mean_step_size, "n_divergent": int(st.n_divergent),
-                  "split_rhat_max": float(np.max(rhat)), "ess_min": float(np.min(ess)), "chains_in_rhat": int(n_chains_diag),
-                  "diagnostics_seconds": t_diag, "diagnostics_path": diag_path, "diagnostics_exchange_bytes_per_rank": int(exch),
-                  "note": "statistics of the K draws of the last timed region: with few steps / a short warmup they are NOT the 1e-3 evidence (a chain of "
-                          "20 draws after 5 warmup transitions has not mixed) -- see `validity`"},
-    }
-    progress(rank, f"hmc leg done: {value:.4g} leapfrog-steps/s over {world} rank(s) [{kernel}]")
-    if failed:
-        # a thread of this process may still be inside RCCL: no further leg, no further collective
-        out["check"]["note"] += "; the cross-rank exchange FAILED -- remaining legs skipped"
-        if rank == 0:
-            emit(args, out)
-        return EXIT_DIAGNOSTICS_FAILED
-    if not args.no_extras:
-        out["mh"] = leg_mh(X)
-        progress(rank, "mh leg done")
-        out["smc"] = leg_smc(X)
-        progress(rank, "smc leg done")
-        out["c3"] = leg_c3(X)
-        progress(rank, "c3 leg done")
-        out["c5"] = leg_c5(X)
-        progress(rank, "c5 leg done")
-        if rank == 0:
-            if args.scaling == "weak" and C != 8192:
-                out["hmc_8192"] = leg_hmc_small(X, 8192)
-                progress(rank, "hmc at 8192 chains done")
-            out["hmc_fd_dense"] = leg_dense(X)
-            progress(rank, "dense leg done")
-            out["extras"] = extras(X)
-            progress(rank, "extras done")
-            out["validity"] = validity(E, W, D, local_rank)
-            progress(rank, "validity leg done")
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            gpu_dense = out.get("hmc_fd_dense", {}).get("value")
-            out["cpu_baseline"] = cpu_baseline_hmc(args, gpu_dense)
-            if "hmc_fd_dense" in out:
-                out["hmc_fd_dense"]["cpu_baseline"] = {k: out["cpu_baseline"][k] for k in ("value", "unit", "cores", "kind", "sample")}
-                out["hmc_fd_dense"]["vs_cpu_baseline"] = gpu_dense / out["cpu_baseline"]["value"]
-            if "mh" in out:
-                out["mh"]["cpu_baseline"] = cpu_baseline_mh()
-            if "smc" in out:
-                out["smc"]["cpu_baseline"] = cpu_baseline_smc()
-            if "c3" in out:
-                out["c3"]["cpu_baseline"] = cpu_baseline_c3(host_cores())
-        emit(args, out)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    return 0
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, draws_last, log_joint, step_size, world=1, rank=0):
+    """--dump-outputs: what the timed path hands its caller after its last transition -- the draw row [d][C] that transition wrote,
+    and the per-chain log-joint [C] and step size [C] it leaves in the engine -- as float64 DIR/<name>.npy (`_rank<r>` with several
+    ranks).  When all ranks together would exceed 64 MB, a fixed seeded sample of chains (the same on every rank) is written, with
+    its global chain ids in chain_id.npy."""
+    d, C = draws_last.shape
+    arrays = {"draws_last_step": draws_last, "log_joint": log_joint, "step_size": step_size}
+    per_chain = (d + 3) * 8 * world
+    if per_chain * C > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(C, (DUMP_LIMIT_BYTES - (64 << 10)) // per_chain, replace=False))    # (64 KB: .npy headers)
+        arrays = {"draws_last_step": draws_last[:, idx], "log_joint": log_joint[idx], "step_size": step_size[idx],
+                  "chain_id": idx + rank * C}
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 # ------------------------------------------------------------------------------------------ the line
@@ -617,7 +692,7 @@ def compact(full):
     """The ONE line the driver records: the contract keys, `roofline` and `cpu_baseline` of the headline kernel, then -- LAST, so that a
     tail of the line still holds them -- `legs`: value / roofline fraction / kernel / CPU baseline of every other half of BASELINE's
     metric (mh, c5, smc, c3 at both chain counts, the reference-verbatim dense HMC).  Notes, spreads and sub-objects live in the verbose
-    document (`--full`, written to --full-out; the committed copy is profiles/roundN_bench_full.json)."""
+    document (written to --full-out, printed with --print-document; the committed copy is profiles/roundN_bench_full.json)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     line = {k: full[k] for k in keep if k in full}
     cfg = full["config"]
@@ -638,11 +713,12 @@ def compact(full):
         if "like_for_like" in cb:
             line["cpu_baseline"]["like_for_like_ratio_gpu_fd_dense"] = _sig(cb["like_for_like"]["ratio"], 3)
     line["timed_regions_value"] = [_sig(v) for v in full["timed_regions"]["value"]["all"]]
-    ck = full["check"]
-    line["check"] = {k: _sig(ck[k], 3) if isinstance(ck[k], float) else ck[k] for k in ("posterior_mean_max_abs_err", "accept_rate", "n_divergent", "split_rhat_max", "chains_in_rhat",
-                                                                                       "diagnostics_path", "diagnostics_exchange_bytes_per_rank") if k in ck}
-    line["check"]["diagnostics_path"] = str(line["check"].get("diagnostics_path", ""))[:200]
-    line["check"] = dict({"of": f"the {full.get('steps')} timed draws behind {full.get('warmup')} warmup transitions from the prior draw (no convergence claim at this length: see validity)"}, **line["check"])
+    if "check" in full:
+        ck = full["check"]
+        line["check"] = {k: _sig(ck[k], 3) if isinstance(ck[k], float) else ck[k] for k in ("posterior_mean_max_abs_err", "accept_rate", "n_divergent", "split_rhat_max", "chains_in_rhat",
+                                                                                           "diagnostics_path", "diagnostics_exchange_bytes_per_rank") if k in ck}
+        line["check"]["diagnostics_path"] = str(line["check"].get("diagnostics_path", ""))[:200]
+        line["check"] = dict({"of": f"the {full.get('steps')} timed draws behind {full.get('warmup')} warmup transitions from the prior draw (no convergence claim at this length: see validity)"}, **line["check"])
     if "validity" in full:
         v = full["validity"]
         line["validity"] = {"posterior_mean_max_abs_err": _sig(v["posterior_mean_max_abs_err"], 3), "target_1e-3": v["target_1e-3"], "split_rhat_max": _sig(v["split_rhat_max"], 5),
@@ -685,7 +761,7 @@ def compact(full):
 
 
 def emit(args, full):
-    """Rank 0: the verbose document to --full-out (best effort), the compact line (or, with --full, the document) to stdout."""
+    """Rank 0: the verbose document to --full-out (best effort), the compact line (or, with --print-document, the document) to stdout."""
     if args.full_out:
         try:
             os.makedirs(os.path.dirname(os.path.abspath(args.full_out)), exist_ok=True)
@@ -694,7 +770,7 @@ def emit(args, full):
             full["full_document"] = args.full_out
         except OSError as ex:
             full["full_document"] = f"not written ({ex})"
-    print(json.dumps(full if args.full else compact(full), separators=(",", ":")), flush=True)
+    print(json.dumps(full if args.print_document else compact(full), separators=(",", ":")), flush=True)
 
 
 def timed_hmc(X, cp, C, cfg, n_warm, n_timed, per_launch, repeats, seed=1, with_draws=False, local=False):

@@ -8,7 +8,7 @@ IFS=';' read -ra VS <<< "$VARIANTS"
 for v in "${VS[@]}"; do
   for ch in $CHAINS; do
     echo "== $v chains=$ch"
-    env $v python3 bench.py --steps 200 --warmup 50 --chains $ch --no-extras --no-cpu-baseline 2>&1 | python3 -c "
+    env $v python3 bench.py --full --steps 200 --warmup 50 --chains $ch --no-extras --no-cpu-baseline 2>&1 | python3 -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()

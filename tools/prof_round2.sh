@@ -8,7 +8,7 @@ O=$R/gpurun_out/r2prof
 rm -rf $O && mkdir -p $O
 set -e
 # 1. the default bench command, as the driver runs it
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python3 $R/bench.py > $O/bench.json 2> $O/bench.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python3 $R/bench.py --full > $O/bench.json 2> $O/bench.log
 echo "[prof] bench stats done"
 # 2. HBM traffic: HMC headline kernel
 HMC="python3 $R/bench.py --steps 100 --warmup 50 --launch 25 --no-cpu-baseline --no-extras"
