@@ -456,7 +456,8 @@ __device__ __forceinline__ void fg_ess_window(FgEssBracket &B, double target) {
 // [beta, 1]: mid <= za goes right, mid >= zb goes left; a midpoint strictly inside (za, zb), if one comes up, and the last levels are
 // decided by evaluation again, by the plain passes below, whose first candidate is b = hi itself (its sum is the reweight's
 // log-normaliser).  Same beta' as the loop of smc.rs:612-619 wherever the evaluated ESS is monotone; inside the few-ulp band where
-// rounding makes it wiggle either is a root to working precision (the tests hold the ladder to 1e-9).  FG_SMC_ZOOM=0: plain passes only.
+// rounding makes it wiggle either is a root to working precision (the criterion: tests/smc_judge.py).  zk = 0 (FG_SMC_ZOOM=0):
+// plain passes only.
 __device__ __forceinline__ FgEssBracket fg_ess_step(FgEssBracket B, const double *ess_c, const double *s1_c, double beta, double target, double n_particles) {
     double cand[ESS_MAXC];
     const int nc = fg_ess_candidates(B, cand);
@@ -553,6 +554,12 @@ __device__ long long fg_smc_prof[64][2][8];
 #else
 #define FG_SMC_T(i)
 #endif
+// k_smc_ess2_pass's term at its recorded candidate, from the product-form term t at the grid point dk below it: t exp(dk x) = t (1 + u)
+// while u^2 / 2 is below rounding, else exp(dc x) itself (dc = candidate - beta)
+__device__ __forceinline__ double fg_ess_move(double t, double dk, double dc, double x) {
+    const double u = dk * x;
+    return fabs(u) < 0x1p-27 ? fma(t, u, t) : exp(dc * x);
+}
 __global__ __launch_bounds__(ESS2_THREADS) void k_smc_ess2_pass(const double *ll, long long n, int pass, const double *beta_ptr, double target, const double *part_max, int n_pmax,
                                                                 FgEssBracket *brk, double *part, double *lmax, int *host_flag, int flag_base, int zoom) {
     __shared__ double shl[ESS2_THREADS / 64][ESS_MAXC][2];
@@ -598,6 +605,24 @@ __global__ __launch_bounds__(ESS2_THREADS) void k_smc_ess2_pass(const double *ll
     const int nc = x0 + (1 << lv) - 1;
     const double lo = B.zmode ? B.wl : B.lo;
     const double d0 = lo - beta, d1 = (first ? 1.0 : B.xb) - beta, dl = B.zmode ? B.wd : (B.hi - B.lo) / (double)(1 << lv);
+    // The product form evaluates grid point k at lo + k dl exactly; the candidate the decisions and the bracket record is a double -- the
+    // reference's midpoint chain 0.5 (lo + hi), or wl + k wd -- up to half an ulp of b away.  Relative to b - beta that is no rounding error
+    // (b = 0.3 + 1.7e-8: 3e-9 of the exponent), so sum k is moved onto its candidate: t *= exp(dk x), dk = candidate - (lo + k dl) (exact
+    // by the fma; 0 while the bracket is wide).  Then the ESS behind a decision, the pair the replay trusts and the log-normaliser taken
+    // from s1_hi / s1_one are all evaluated at the double they are recorded at.
+    double dk[8], dc[8];
+    {
+        double cand[ESS_MAXC];
+        (void)fg_ess_candidates(B, cand);
+        const int pos3[7] = {4, 2, 6, 1, 3, 5, 7}, pos2[3] = {2, 1, 3};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { dk[k] = 0.0; dc[k] = 0.0; }
+        for (int q = 0; q < (1 << lv) - 1; ++q) {
+            const int k = lv == 3 ? pos3[q] : (lv == 2 ? pos2[q] : 1);
+            dk[k] = fma(-(double)k, dl, cand[x0 + q] - lo);
+            dc[k] = cand[x0 + q] - beta;
+        }
+    }
     double s1[ESS_MAXC], s2[ESS_MAXC];
 #pragma unroll
     for (int q = 0; q < ESS_MAXC; ++q) { s1[q] = 0.0; s2[q] = 0.0; }
@@ -619,15 +644,19 @@ __global__ __launch_bounds__(ESS2_THREADS) void k_smc_ess2_pass(const double *ll
                 if (lv == 0) continue;
             }
             const double E = exp(d0 * x), R = exp(dl * x);
-            const double p1 = E * R, p2 = p1 * R, p3 = p2 * R;
+#define ESS_AT(k, p) (dk[k] == 0.0 ? (p) : fg_ess_move(p, dk[k], dc[k], x))
+            const double q1 = E * R, q2 = q1 * R, q3 = q2 * R;
+            const double p1 = ESS_AT(1, q1), p2 = ESS_AT(2, q2), p3 = ESS_AT(3, q3);
             if (lv == 3) {                                           // the depth-3 tree (or the window's seven inner points), heap order
-                const double p4 = p3 * R, p5 = p4 * R, p6 = p5 * R, p7 = p6 * R;
+                const double q4 = q3 * R, q5 = q4 * R, q6 = q5 * R, q7 = q6 * R;
+                const double p4 = ESS_AT(4, q4), p5 = ESS_AT(5, q5), p6 = ESS_AT(6, q6), p7 = ESS_AT(7, q7);
                 if (x0) { ESS_ADD(1, p4) ESS_ADD(2, p2) ESS_ADD(3, p6) ESS_ADD(4, p1) ESS_ADD(5, p3) ESS_ADD(6, p5) ESS_ADD(7, p7) }
                 else { ESS_ADD(0, p4) ESS_ADD(1, p2) ESS_ADD(2, p6) ESS_ADD(3, p1) ESS_ADD(4, p3) ESS_ADD(5, p5) ESS_ADD(6, p7) }
             } else if (lv == 2) { if (x0) { ESS_ADD(1, p2) ESS_ADD(2, p1) ESS_ADD(3, p3) } else { ESS_ADD(0, p2) ESS_ADD(1, p1) ESS_ADD(2, p3) } }
             else { if (x0) ESS_ADD(1, p1) else ESS_ADD(0, p1) }
         }
     }
+#undef ESS_AT
 #undef ESS_ADD
     FG_SMC_T(4)
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1238,11 +1267,10 @@ struct Reducer {     // scratch for the two-pass reductions
     // the passes alone: part_max[0 .. n_pmax) holds block maxima of ll (their producer's: k_smc_split_acc_max or the step's last
     // rejuvenation sweep); what follows them is k_smc_ess2_apply.  The host looks at pass 1's bracket through pinned memory.
     int ess2_passes(hipStream_t s, const double *ll, long long n, const double *beta_ptr, double target, int n_pmax, FgSmcHostScalars *hs_host,
-                    FgSmcHostScalars *hs_dev, int epoch, int *last_out, int *nb_out, bool *ends_at_one) {
+                    FgSmcHostScalars *hs_dev, int epoch, int zoom, int *last_out, int *nb_out, bool *ends_at_one) {
         double *part = ess2, *lmax = ess2 + (size_t)2 * ESS2_BLOCKS * ESS_MAXC * 2;
         FgEssBracket *brk = (FgEssBracket *)(lmax + 2);
         const int nb = (int)std::min<long long>(ESS2_BLOCKS, (n + ESS2_THREADS - 1) / ESS2_THREADS);
-        static const int zoom = []() { const char *z = std::getenv("FG_SMC_ZOOM"); return (z && std::atoi(z) == 0) ? 0 : 1; }();
         // Pass p + 1 is queued when pass p's flag arrives (block 0 writes it before its sums: the queue is never empty), and none once a
         // flag says the bracket is final: how many passes a step takes -- two when ESS(1) >= target, 8 - 10 with the zoom passes, 19 - 22
         // without -- is only known on the device.
@@ -1387,6 +1415,52 @@ int smc_workspace(fg_engine *e, SmcWs &W) {
     return FG_OK;
 }
 
+// FG_SMC_ZOOM=0: next_beta by the plain passes only (zoom = 0 of Reducer::ess2_passes); read once per process
+static int smc_zoom_default() {
+    static const int zoom = []() { const char *z = std::getenv("FG_SMC_ZOOM"); return (z && std::atoi(z) == 0) ? 0 : 1; }();
+    return zoom;
+}
+static int smc_force_sum_env() { const char *f = std::getenv("FG_SMC_FORCE_SUM"); return (f && std::atoi(f) != 0) ? 1 : 0; }
+// One tempering step of adaptive_smc (smc.rs:501-529) from uniform log-weights lw0: next_beta by the ess2 passes (part_max[0 .. n_pmax)
+// holds block maxima of ll), then the last decision, reweight and evidence in one launch (k_smc_ess2_apply) -- or, when beta' = beta + 1e-9
+// (need_sum) or force_sum, k_smc_ess2_final and the separate kernels.  beta comes in through st->beta2[parity & 1] (and st->beta), beta'
+// goes out through st->beta2[(parity + 1) & 1].  may_end: ESS(1) >= target may end the ladder without a look at the pinned scalars.
+// fg_smc_run and fg_device_smc_temper take their steps here.
+struct SmcStep { double beta, log_evidence; bool fused, ends; };
+static int smc_temper_step(hipStream_t s, Reducer &R, const double *ll, long long N, int n_pmax, FgSmcScalars *st, int parity, double lw0,
+                           double *d_lw, double *d_w, double *chunk, double *chunk2, FgSmcHostScalars *hs, FgSmcHostScalars *hs_dev, int epoch,
+                           int zoom, int force_sum, bool may_end, FgSmcScalars &h, SmcStep &o) {
+    const int TB = 256, NB = (int)((N + TB - 1) / TB), n_chunks = (int)((N + SCAN_CHUNK - 1) / SCAN_CHUNK);
+    double *lmax = R.ess2 + (size_t)2 * ESS2_BLOCKS * ESS_MAXC * 2;
+    FgEssBracket *brk = (FgEssBracket *)(lmax + 2);
+    int last = 0, nb = 0;
+    const double *beta_in = &st->beta2[parity & 1]; double *beta_out = &st->beta2[(parity + 1) & 1];
+    bool ends_at_one = false;
+    if (int rc = R.ess2_passes(s, ll, N, beta_in, h.target_ess, n_pmax, hs, hs_dev, epoch, zoom, &last, &nb, &ends_at_one)) return rc;
+    // the last decision, reweight + evidence (smc.rs:512-529), weights and the chunk totals of the resampling prefix sum: one launch
+    hipLaunchKernelGGL(k_smc_ess2_apply, dim3((unsigned)n_chunks), dim3(SCAN_THREADS), 0, s, ll, N, last, nb, h.target_ess,
+                       (const FgEssBracket *)brk, (const double *)R.ess2, (const double *)lmax, st, beta_in, beta_out, lw0, d_lw, d_w, chunk, chunk2, hs_dev, force_sum);
+    HIPCHK(hipGetLastError());
+    // ESS(1) >= target (pass 1 said so): beta' = 1 ends the ladder -- nothing to look at before the final normalisation is queued
+    o.ends = ends_at_one && may_end && !force_sum;
+    if (!o.ends) HIPCHK(smc_wait(s));
+    o.fused = o.ends || hs->need_sum == 0;
+    if (o.ends) { o.beta = 1.0; o.log_evidence = 0.0; }
+    else if (o.fused) { o.beta = hs->beta; o.log_evidence = hs->log_evidence; }
+    else {                                                   // beta' = beta + 1e-9: the separate kernels (maximum, sum, finish, apply)
+        hipLaunchKernelGGL(k_smc_ess2_final, dim3(1), dim3(ESS2_THREADS), 0, s, N, last, nb, (const double *)&st->beta, h.target_ess, brk, (const double *)R.ess2,
+                           (const double *)lmax, st, lw0, R.part_max, RED_BLOCKS);
+        hipLaunchKernelGGL(k_fill, dim3(NB), dim3(TB), 0, s, d_lw, N, lw0);
+        if (int rc = R.run_sum_only(s, d_lw, ll, N, st, (const double *)&st->bnew, 3)) return rc;
+        hipLaunchKernelGGL(k_smc_apply, dim3(NB), dim3(TB), 0, s, d_lw, ll, d_w, N, (const FgSmcScalars *)st);
+        HIPCHK(hipMemcpyAsync(beta_out, &st->beta, sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        o.beta = h.beta; o.log_evidence = h.log_evidence;
+    }
+    return FG_OK;
+}
+
 int set_device_or_fail(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { fg_set_error("no HIP device available: no CPU fallback (FG_E_NO_DEVICE)"); return FG_E_NO_DEVICE; }
@@ -1445,6 +1519,53 @@ int fg_device_next_beta(int device, double beta, const double *h_log_w, const do
     rc = R.next_beta(nullptr, d_lw, d_ll, n, st);
     if (!rc) { hipError_t e_ = hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost); if (e_ != hipSuccess) rc = FG_E_HIP; else *out_beta = h.bnew; }
     (void)hipFree(d_lw); (void)hipFree(d_ll); (void)hipFree(st); R.free_all();
+    return rc;
+}
+
+// one tempering step of fg_smc_run (smc_temper_step) on the caller's log-likelihoods, from uniform log-weights -ln n.  flags: 1 = plain passes
+// only (no zoom passes), 2 = the separate-kernels reweight (as FG_SMC_FORCE_SUM=1).  Out: beta', the reweight's log-normaliser, the new
+// log-weights and weights (before any final normalisation), and whether the separate kernels took the step.
+int fg_device_smc_temper(int device, double beta, const double *h_ll, int64_t n, double target_ess, int flags, double *out_beta,
+                         double *out_log_norm, double *h_log_w, double *h_weights, int *out_need_sum) {
+    int rc = set_device_or_fail(device);
+    if (rc) return rc;
+    if (!h_ll || !out_beta || !out_log_norm || n <= 0 || (flags & ~3)) return FG_E_BAD_ARG;
+    const long long N = n, n_chunks = (N + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    double *d_ll = nullptr, *d_lw = nullptr, *d_w = nullptr, *d_chunk = nullptr, *d_chunk2 = nullptr; FgSmcScalars *st = nullptr; Reducer R;
+    FgSmcHostScalars *hs = nullptr, *hs_dev = nullptr; hipStream_t s = nullptr;
+    auto release = [&]() {
+        if (s) (void)hipStreamSynchronize(s);
+        (void)hipFree(d_ll); (void)hipFree(d_lw); (void)hipFree(d_w); (void)hipFree(d_chunk); (void)hipFree(d_chunk2); (void)hipFree(st); R.free_all();
+        if (hs) (void)hipHostFree(hs);
+        if (s) (void)hipStreamDestroy(s);
+    };
+    rc = FG_E_HIP;
+    bool stepped = false;
+    if (!dev_alloc(&d_ll, (size_t)N) && !dev_alloc(&d_lw, (size_t)N) && !dev_alloc(&d_w, (size_t)N) && !dev_alloc(&d_chunk, (size_t)n_chunks) &&
+        !dev_alloc(&d_chunk2, (size_t)n_chunks) && !dev_alloc(&st, 1) && !R.init() &&
+        hipHostMalloc((void **)&hs, sizeof(FgSmcHostScalars), hipHostMallocMapped) == hipSuccess &&
+        hipHostGetDevicePointer((void **)&hs_dev, hs, 0) == hipSuccess && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess) {
+        std::memset(hs, 0, sizeof(*hs));
+        FgSmcScalars h; std::memset(&h, 0, sizeof(h));
+        h.beta = beta; h.one = 1.0; h.target_ess = target_ess; h.beta2[0] = beta; h.beta2[1] = beta;
+        // (blocking uploads from the caller's pageable memory: complete before anything on the stream reads them)
+        if (hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_ll, h_ll, (size_t)N * 8, hipMemcpyHostToDevice) == hipSuccess) {
+            // the block maxima of ll for the first pass: fg_smc_run's source when no rejuvenation sweep left them
+            hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, (const double *)d_ll, (const double *)nullptr, N, (const double *)&st->one, (const double *)&st->one, R.part_max);
+            SmcStep o;
+            stepped = true;
+            rc = smc_temper_step(s, R, d_ll, N, RED_BLOCKS, st, 1, -std::log((double)N), d_lw, d_w, d_chunk, d_chunk2, hs, hs_dev, 1,
+                                 (flags & 1) ? 0 : 1, (flags & 2) ? 1 : 0, false, h, o);
+            if (!rc) {
+                if (hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    (h_log_w && hipMemcpyAsync(h_log_w, d_lw, (size_t)N * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+                    (h_weights && hipMemcpyAsync(h_weights, d_w, (size_t)N * 8, hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess) rc = FG_E_HIP;
+                else { *out_beta = h.beta; *out_log_norm = h.log_norm; if (out_need_sum) *out_need_sum = o.fused ? 0 : 1; }
+            }
+        }
+    }
+    if (rc == FG_E_HIP && !stepped) fg_set_error("fg_device_smc_temper: allocation or upload failed");
+    release();
     return rc;
 }
 
@@ -1512,42 +1633,23 @@ int fg_smc_run(fg_engine *e, const fg_smc_config *cfg, double *h_log_w, double *
         hipLaunchKernelGGL(k_smc_split_acc_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, (const double *)e->d_acc, M.lprior, M.ll, N, R.part_max);
         int n_pmax = RED_BLOCKS;
         const int n_chunks = (int)((N + SCAN_CHUNK - 1) / SCAN_CHUNK);
-        double *lmax = R.ess2 + (size_t)2 * ESS2_BLOCKS * ESS_MAXC * 2;
-        FgEssBracket *brk = (FgEssBracket *)(lmax + 2);
+        const int zoom = smc_zoom_default();
         double beta = 0.0;
         int steps = 0;
         while (beta < 1.0) {                                 // smc.rs:501-560
             steps += 1;
             // next_beta: ESS at b = 1, then 64 bisections on the device (smc.rs:588-622)
             if (steps >= 10000) { int one = 1; SMC_HIP(hipMemcpyAsync(&st->force_one, &one, sizeof(int), hipMemcpyHostToDevice, s)); }
-            int last = 0, nb = 0;
-            const double *beta_in = &st->beta2[steps & 1]; double *beta_out = &st->beta2[(steps + 1) & 1];   // (both start at 0: k_smc_init)
-            bool ends_at_one = false;
             e->smc_epoch = (e->smc_epoch + 1) & 0x0fffffff;
             if (e->smc_epoch == 0) e->smc_epoch = 1;                // (0 is what an unwritten flag reads as)
-            SMC_TRY(R.ess2_passes(s, M.ll, N, beta_in, h.target_ess, n_pmax, hs, hs_dev, e->smc_epoch, &last, &nb, &ends_at_one));
-            // the last decision, reweight + evidence (smc.rs:512-529), weights and the chunk totals of the resampling prefix sum: one launch
-            hipLaunchKernelGGL(k_smc_ess2_apply, dim3((unsigned)n_chunks), dim3(SCAN_THREADS), 0, s, (const double *)M.ll, N, last, nb, h.target_ess,
-                               (const FgEssBracket *)brk, (const double *)R.ess2, (const double *)lmax, st, beta_in, beta_out, lw0, d_lw, d_w, SC.chunk, WS.d_chunk2, hs_dev,
-                               (std::getenv("FG_SMC_FORCE_SUM") && std::atoi(std::getenv("FG_SMC_FORCE_SUM")) != 0) ? 1 : 0);
-            SMC_HIP(hipGetLastError());
-            // ESS(1) >= target (pass 1 said so): beta' = 1 ends the ladder -- nothing to look at before the final normalisation is queued
-            const bool ends = ends_at_one && steps < 10000 && !(std::getenv("FG_SMC_FORCE_SUM") && std::atoi(std::getenv("FG_SMC_FORCE_SUM")) != 0);
-            if (!ends) SMC_HIP(smc_wait(s));
-            const bool fused = ends || hs->need_sum == 0;
-            if (ends) { beta = 1.0; have_evidence = true; evidence_late = true; fin_ready = true; }
-            else if (fused) { beta = hs->beta; log_evidence = hs->log_evidence; have_evidence = true; fin_ready = beta >= 1.0; }
-            else {                                           // beta' = beta + 1e-9: the separate kernels (maximum, sum, finish, apply)
-                hipLaunchKernelGGL(k_smc_ess2_final, dim3(1), dim3(ESS2_THREADS), 0, s, N, last, nb, (const double *)&st->beta, h.target_ess, brk, (const double *)R.ess2,
-                                   (const double *)lmax, st, lw0, R.part_max, RED_BLOCKS);
-                hipLaunchKernelGGL(k_fill, dim3(NB), dim3(TB), 0, s, d_lw, N, lw0);
-                SMC_TRY(R.run_sum_only(s, d_lw, M.ll, N, st, (const double *)&st->bnew, 3));
-                hipLaunchKernelGGL(k_smc_apply, dim3(NB), dim3(TB), 0, s, d_lw, (const double *)M.ll, d_w, N, (const FgSmcScalars *)st);
-                SMC_HIP(hipMemcpyAsync(beta_out, &st->beta, sizeof(double), hipMemcpyDeviceToDevice, s));
-                SMC_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-                SMC_HIP(hipStreamSynchronize(s));
-                beta = h.beta; have_evidence = false; fin_ready = false;
-            }
+            SmcStep o;
+            SMC_TRY(smc_temper_step(s, R, M.ll, N, n_pmax, st, steps, lw0, d_lw, d_w, SC.chunk, WS.d_chunk2, hs, hs_dev, e->smc_epoch,
+                                    zoom, smc_force_sum_env(), steps < 10000, h, o));
+            const bool fused = o.fused;
+            beta = o.beta;
+            if (o.ends) { have_evidence = true; evidence_late = true; fin_ready = true; }
+            else if (fused) { log_evidence = o.log_evidence; have_evidence = true; fin_ready = beta >= 1.0; }
+            else { have_evidence = false; fin_ready = false; }
             betas.push_back(beta); n_steps++;
             if (beta < 1.0) {                                // resample + rejuvenate (smc.rs:534-559)
                 double U = 0.0;

@@ -72,7 +72,7 @@ ABI_SYMBOLS = [
     "fg_state_size", "fg_state_export", "fg_state_import", "fg_hmc_grad", "fg_hmc_transition_injected",
     "fg_hmc_find_eps_injected", "fg_mh_init", "fg_mh_step", "fg_mh_set_recording", "fg_mh_run", "fg_mh_get_stats", "fg_mh_get_scales",
     "fg_mh_get_log_weight", "fg_smc_config_default", "fg_smc_run", "fg_smc_prior_particles", "fg_smc_normalize", "fg_smc_ess", "fg_smc_resample", "fg_smc_rejuvenate",
-    "fg_smc_get_weights", "fg_smc_set_log_weights", "fg_device_log_sum_exp", "fg_device_next_beta",
+    "fg_smc_get_weights", "fg_smc_set_log_weights", "fg_device_log_sum_exp", "fg_device_next_beta", "fg_device_smc_temper",
     "fg_device_resample_indices", "fg_diag_chain_moments", "fg_diag_autocov_sums", "fg_diag_rhat_ess", "fg_diag_combine", "fg_diag_geweke",
     "fg_diag_combine_reduced", "fg_diag_set_exchange", "fg_diag_exchange_bytes", "fg_hmc_last_kernel", "fg_mh_last_kernel", "fg_diag_quantiles",
     "fg_comm_unique_id", "fg_comm_init", "fg_comm_destroy", "fg_device_alloc", "fg_device_free", "fg_device_download", "fg_device_upload",
@@ -180,6 +180,7 @@ def lib():
     L.fg_smc_set_log_weights.argtypes = [vp, dp]
     L.fg_device_log_sum_exp.argtypes = [C.c_int, dp, C.c_int64, dp]
     L.fg_device_next_beta.argtypes = [C.c_int, C.c_double, dp, dp, C.c_int64, C.c_double, dp]
+    L.fg_device_smc_temper.argtypes = [C.c_int, C.c_double, dp, C.c_int64, C.c_double, C.c_int, dp, dp, dp, dp, ip]
     L.fg_device_resample_indices.argtypes = [C.c_int, C.c_int, dp, C.c_int64, dp, C.POINTER(C.c_int64)]
     L.fg_diag_chain_moments.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     L.fg_diag_autocov_sums.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, dp]
@@ -693,6 +694,18 @@ def device_next_beta(beta, log_w, ll, target_ess, device: int = 0) -> float:
     out = C.c_double()
     _check(lib().fg_device_next_beta(device, float(beta), _dp(lw), _dp(l2), lw.size, float(target_ess), C.byref(out)))
     return out.value
+
+
+def device_smc_temper(beta, ll, target_ess, zoom: bool = True, force_sum: bool = False, device: int = 0) -> dict:
+    """One tempering step of smc_run's ladder on `ll` from uniform log-weights -ln n: beta' (next_beta), the reweight's log-normaliser,
+    the reweighted log_w / w, and need_sum (the separate-kernels path took the step)."""
+    l2 = np.ascontiguousarray(ll, dtype=np.float64)
+    n = l2.size
+    lw, w = np.empty(n), np.empty(n)
+    b, ln, ns = C.c_double(), C.c_double(), C.c_int32()
+    flags = (0 if zoom else 1) | (2 if force_sum else 0)
+    _check(lib().fg_device_smc_temper(device, float(beta), _dp(l2), n, float(target_ess), flags, C.byref(b), C.byref(ln), _dp(lw), _dp(w), C.byref(ns)))
+    return {"beta": b.value, "log_norm": ln.value, "log_w": lw, "w": w, "need_sum": bool(ns.value)}
 
 
 def device_resample_indices(method: int, weights, u, device: int = 0) -> np.ndarray:

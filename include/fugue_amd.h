@@ -321,6 +321,14 @@ int fg_device_next_beta(int device_ordinal, double beta, const double *h_log_w, 
                         int64_t n, double target_ess, double *out_beta);
 int fg_device_resample_indices(int device_ordinal, int method, const double *h_weights, int64_t n,
                                const double *h_u, int64_t *h_idx);
+/* one tempering step of fg_smc_run (next_beta by the device's passes, reweight, log-normaliser) on the
+ * log-likelihoods h_loglik[n] from uniform log-weights -ln n.  flags: 1 = plain passes only (no zoom
+ * passes), 2 = force the separate-kernels reweight.  h_log_w / h_weights receive the reweighted
+ * log-weights and weights (either may be NULL); *out_need_sum (or NULL) = 1 when the separate kernels
+ * took the step (beta' = beta + 1e-9, or flag 2). */
+int fg_device_smc_temper(int device_ordinal, double beta, const double *h_loglik, int64_t n, double target_ess,
+                         int flags, double *out_beta, double *out_log_norm, double *h_log_w, double *h_weights,
+                         int *out_need_sum);
 
 /* ------------------------------------------------------------------ cross-chain diagnostics
  * Per-chain statistics behind r_hat_f64 / effective_sample_size_multichain

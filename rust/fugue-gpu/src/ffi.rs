@@ -167,6 +167,8 @@ extern "C" {
     pub fn fg_device_log_sum_exp(device_ordinal: c_int, h_x: *const f64, n: i64, out: *mut f64) -> c_int;
     pub fn fg_device_next_beta(device_ordinal: c_int, beta: f64, h_log_w: *const f64, h_loglik: *const f64, n: i64, target_ess: f64, out_beta: *mut f64) -> c_int;
     pub fn fg_device_resample_indices(device_ordinal: c_int, method: c_int, h_weights: *const f64, n: i64, h_u: *const f64, h_idx: *mut i64) -> c_int;
+    pub fn fg_device_smc_temper(device_ordinal: c_int, beta: f64, h_loglik: *const f64, n: i64, target_ess: f64, flags: c_int, out_beta: *mut f64,
+                                out_log_norm: *mut f64, h_log_w: *mut f64, h_weights: *mut f64, out_need_sum: *mut c_int) -> c_int;
     pub fn fg_diag_chain_moments(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, d_moments: *mut f64) -> c_int;
     pub fn fg_diag_autocov_sums(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, d_moments: *const f64, lag0: c_int, n_lags: c_int, h_sums: *mut f64) -> c_int;
 }

@@ -249,3 +249,106 @@ def test_adaptive_smc_edge_population_sizes(method):
         assert np.isfinite(r["log_evidence"]), N
         assert abs(r["weights"].sum() - 1.0) < 1e-9 and (r["weights"] >= 0).all(), N
         assert r["betas"][-1] == 1.0 and (np.diff(r["betas"]) > 0).all(), (N, r["betas"])
+
+
+# ---- whole ladders against the oracle where the tempering step is hardest ---------------------------------------------------------
+def _tie_model():
+    """Log-likelihoods with only a few distinct values: two discrete latents, each with an observation whose mean is a constant picked by
+    the latent (the pattern of workloads.mixture with the component means given).  No f64 site: rejuvenation moves nothing, the ties
+    survive every step, and each step's log-likelihoods are the resampled ones of the step before."""
+    from fugue_amd.model import Categorical, Normal, Program, addr, select
+    P = Program()
+    for i, xi in enumerate((1.3, -0.4)):
+        z = P.sample(addr("z", i), Categorical([0.1, 0.2, 0.3, 0.4]))
+        P.observe(addr("x", i), Normal(select(z, [-6.0, -2.0, 2.0, 6.0]), 1.0), xi)
+    return P
+
+
+def _resample_host(oracle, w, method, seed, step):
+    n = w.size
+    if method == E.RESAMPLE_SYSTEMATIC:
+        u = np.array([oracle.lib().orc_stream_u01(oracle.stream(seed, 0, step, 5))])
+        return oracle.systematic_indices(w, u[0]), (u[0] / n + np.arange(n) / n)
+    u = np.array([oracle.lib().orc_stream_u01(oracle.stream(seed, j, step, 5)) for j in range(n)])   # ORC_RNG_SMC_RESAMPLE
+    if method == E.RESAMPLE_STRATIFIED:
+        return oracle.stratified_indices(w, u), (np.arange(n) + u) / n
+    return oracle.multinomial_indices(w, u), u
+
+
+def _judged_tie_ladder(oracle, N, method, seed):
+    """fg_smc_run on the tie model against the oracle's smc_run: every step's beta through the judge on that step's log-likelihoods (the
+    ladder replayed on the host with the oracle's primitives, from the device's prior draw), the evidence within the sum of the steps'
+    log-normaliser tolerances, the particles exactly unless a resampling threshold lay within 1e-12 of a cumulative weight."""
+    from tests import smc_judge as J
+    prog = _tie_model()
+    cp, om = E.compile_model(prog), oracle.OracleModel(prog)
+    eng = E.Engine(cp, N, seed=seed)
+    eng.smc_prior_particles(0)                          # fg_smc_run's prior draw (iteration 0, the SMC prior stream)
+    ll = eng.smc_weights()[0].copy()                     # log_weight = log_likelihood before any reweight
+    got = eng.smc_run(rejuvenation_steps=1, ess_threshold=0.5, resampling_method=method)
+    eng.close()
+    exp = om.smc_run(N, seed, method=method, ess_threshold=0.5, rejuvenation_steps=1, batched=1)
+    assert len(np.unique(ll)) <= 16
+    lw0, target = -math.log(N), min(max(0.5 * N, 1.0), float(N))
+    # the replay follows the DEVICE's ladder, so that every step is judged on the device's own population (the oracle's sums of tied
+    # terms round alike: its betas may sit ~1e-12 off the exact crossing, and a resampling threshold may fall the other way)
+    beta, steps, tol, logz, knife_edges, max_db = 0.0, 0, 0.0, 0.0, [], 0.0
+    while beta < 1.0:
+        steps += 1
+        want = oracle.next_beta(beta, np.full(N, lw0), ll, target) if steps < 10000 else 1.0
+        assert steps <= len(got["betas"]), (N, method, steps)
+        b = got["betas"][steps - 1]
+        assert J.accept(J.Curve(ll, beta), target, b, want, case=f"tie ladder N={N} method={method} step={steps}"), (N, method, steps, b, want)
+        max_db = max(max_db, abs(b - want) * float(np.ptp(ll)))
+        comb = lw0 + (b - beta) * ll
+        ln = oracle.log_sum_exp(comb)
+        logz += ln
+        tol += J.log_norm_tol(ll, beta, b) + J.EPS * (N - 1)      # (+ the oracle's sequential sum)
+        lw = comb - ln if math.isfinite(ln) else np.full(N, lw0)
+        beta = b
+        if beta < 1.0:
+            w = np.exp(lw)
+            idx, thr = _resample_host(oracle, w, method, seed, steps)
+            cum = np.cumsum(w)
+            near = np.minimum(np.abs(cum[idx] - thr), np.abs(np.where(idx > 0, cum[np.maximum(idx - 1, 0)], -1.0) - thr))
+            if (near < 1e-12 + max_db).any():
+                knife_edges.append((steps, int(np.argmin(near)), float(near.min())))
+            ll = ll[idx]
+    assert len(got["betas"]) == steps == len(exp["betas"]) and got["betas"][-1] == 1.0
+    np.testing.assert_allclose(got["betas"], exp["betas"], rtol=1e-9, atol=0)
+    assert abs(got["log_evidence"] - logz) <= tol, (got["log_evidence"], logz, tol)
+    assert got["log_evidence"] == pytest.approx(exp["log_evidence"], rel=1e-9)
+    assert got["n_model_runs"] == exp["n_model_evals"]
+    bad = (got["values"] != exp["values"]).any(axis=0)
+    if bad.any():
+        assert knife_edges and bad.mean() < 0.01, (int(bad.sum()), knife_edges)
+        knife.used("tie ladder: resampling indices", N=N, method=method, particles=int(bad.sum()), threshold_minus_cum=knife_edges)
+    np.testing.assert_allclose(got["weights"][~bad], exp["weights"][~bad], rtol=1e-9, atol=0)
+    return got
+
+
+@pytest.mark.parametrize("method", [E.RESAMPLE_SYSTEMATIC, E.RESAMPLE_STRATIFIED, E.RESAMPLE_MULTINOMIAL])
+@pytest.mark.parametrize("N", [2048, 131073])
+def test_tie_heavy_ladder_matches_the_oracle(oracle, N, method):
+    """The in-process parity of the tempering step where it is hardest: log-likelihoods with a handful of distinct values, every step."""
+    got = _judged_tie_ladder(oracle, N, method, seed=21)
+    assert len(got["betas"]) >= 3
+
+
+@pytest.mark.parametrize("method", [0, 1, 2])
+def test_adaptive_smc_edge_population_sizes_match_the_oracle(oracle, method):
+    """The edge population sizes of test_adaptive_smc_edge_population_sizes against the oracle's batched smc_run: with rejuvenation
+    (normal_sites(8)) the ladder to 1e-9, the evidence to rel 1e-9 and the model-run count exactly; on the tie model every step's beta
+    through the judge (the per-step log-likelihoods are known there)."""
+    prog = W.normal_sites(8)
+    cp, om = E.compile_model(prog), oracle.OracleModel(prog)
+    for N in (1, 2, 63, 64, 65, 2047, 2048, 2049, 4097):
+        eng = E.Engine(cp, N, seed=11)
+        r = eng.smc_run(rejuvenation_steps=2, ess_threshold=0.5, resampling_method=method)
+        eng.close()
+        exp = om.smc_run(N, 11, method=method, ess_threshold=0.5, rejuvenation_steps=2, batched=1)
+        assert len(r["betas"]) == len(exp["betas"]), (N, r["betas"], exp["betas"])
+        np.testing.assert_allclose(r["betas"], exp["betas"], rtol=1e-9, atol=0, err_msg=str(N))
+        assert r["log_evidence"] == pytest.approx(exp["log_evidence"], rel=1e-9), N
+        assert r["n_model_runs"] == exp["n_model_evals"], N
+        _judged_tie_ladder(oracle, N, method, seed=11)
