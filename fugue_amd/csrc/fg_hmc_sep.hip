@@ -29,6 +29,7 @@ __device__ unsigned long long fg_hmc_prof[FG_SEP_WMAX][8];
 #define FG_PROF_T(i)
 #endif
 struct FgSegSep { int c[FG_SEP_WMAX + 1]; int sum4;       // sum4: the four in-order sums of a transition's end on four waves (tiles that are alone on their CU)
+                  int predraw;                           // resident form: waves 1.. draw their next transition's momenta while wave 0 decides
                   int own[FG_SEP_WMAX][4], n_own[FG_SEP_WMAX]; };   // MODE 3 (dense, coordinates in registers): each wave's <= 4 coordinates (whole Box-Muller pairs), ascending
 #ifndef FG_SEP_STAGGER
 #define FG_SEP_STAGGER 2          /* x 4 096 cycles: the late start of a CU's second tile (k_hmc_sep_steps) */
@@ -303,7 +304,15 @@ __device__ __forceinline__ bool fg_dense_trajectory(const FgProgramDev &P, const
 // waves all wait while wave 0 adds and decides (tools/prof_hmc_phases.py at 8 192 chains: 8 200 of a transition's 22 400 ticks); two
 // quarter tiles per CU take turns.  Per
 // (chain, coordinate) the arithmetic is unchanged; wave 0's in-order sums run in both halves on the same rows.
-template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */>
+//
+// NC > 0 (MODE 0, 64-chain tiles, every coordinate the record shape NOBS_R / U0_R with power-of-two sigmas, no statement that reads
+// no coordinate, <= NC coordinates per wave): the RESIDENT form.  A wave loads its coordinates' values, mass and record offsets once
+// per launch and keeps them in registers: each trajectory starts from q_cur, the proposal stays in registers, the commit is a select
+// (no proposal rows, no global load between the two barriers) and the value rows are stored once, at the launch's end.  While
+// wave 0 adds and decides, the other waves draw the Box-Muller pairs of their next transition.  The arithmetic per coordinate is
+// fg_sep_trajectory's for the shape NC = 0 dispatches to: every result is bit-identical to NC = 0.  (The records themselves are still
+// loaded per trajectory: held for four coordinates they spill SGPRs into the leapfrog loop.)
+template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false>
 __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgProgramDev P, FgChainCtx X, FgHmcDev H, FgSegSep seg, int iter0, int n_steps,
                                                                              int n_warmup, int welford_on, double *draws, int first_sample_t,
                                                                              double *pos_all /*[n][d][C] or null*/, double *info /*[n][4][C] or null*/) {
@@ -311,6 +320,9 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     constexpr int tw = FG_WAVE >> HALF;
     constexpr bool DFAST = MODE == 3, DENSE = MODE == 1 || DFAST, AN = MODE == 2;   // (3: DENSE with the coordinates in registers, fg_dense_trajectory)
     static_assert(!HALF || MODE == 0, "half tiles: sparse finite difference only");
+    constexpr bool RES = NC > 0;
+    constexpr int NCX = RES ? NC : 1;
+    static_assert(!RES || (MODE == 0 && HALF == 0 && NC <= 4 && NOBS_R >= 0 && NOBS_R <= 3), "resident form: sparse 64-chain tiles");
     const int lane = threadIdx.x & (tw - 1);                       // chain of the tile
     const int half = HALF == 1 ? (int)((threadIdx.x >> 5) & 1u) : (HALF == 2 ? (int)((threadIdx.x >> 4) & 3u) : 0);   // which of the wave's 2 / 4 coordinates this lane runs
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -344,6 +356,21 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     const double *ms = MASS ? H.mass_sqrt + c : nullptr;
     const double h = fg_uniform(H.h), two_h = fg_uniform(2.0 * H.h), rcp_2h = fg_uniform(1.0 / (2.0 * H.h));
     const uint32_t sk0 = (uint32_t)X.seed, sk1 = (uint32_t)(X.seed >> 32), gchain = X.chain0 + (uint32_t)c;
+    // RES: the wave's k1 - k0 <= NC coordinates for the whole launch -- committed values, proposals, mass, record offsets
+    const int nown = k1 - k0;
+    double qc[NCX], qpr[NCX], mir[NCX], msr[NCX];
+    uint32_t roff[NCX];
+    if (RES) {
+#pragma unroll
+        for (int j = 0; j < NCX; ++j) {
+            const int i = j < nown ? k0 + j : 0;                     // (slots past the wave's coordinates: loaded, never used)
+            roff[j] = P.sep_coord[i].off;
+            qc[j] = fg_as_double(X.values[(long long)P.f64_site[i] * X.C + c]);
+            qpr[j] = qc[j];
+            mir[j] = MASS ? H.m_inv[(long long)i * X.C + c] : 1.0;
+            msr[j] = MASS ? H.mass_sqrt[(long long)i * X.C + c] : 1.0;
+        }
+    }
     // wave 0 owns the per-chain sampler state
     double lj = 0.0, eps = 0.0, frozen = 0.0, da_mu = 0.0, da_leb = 0.0, da_hbar = 0.0, asum = 0.0, e_cur = 0.0;
     unsigned long long da_m = 0, ndiv = 0;
@@ -382,6 +409,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     // draw the Box-Muller pair their NEXT transition starts with (Philox is counter based: the same numbers).  A tile that is alone on
     // its CU otherwise leaves that phase's SIMD cycles empty (8 192 chains: a quarter of a trajectory's instructions are this pair).
     FgD2 zpre = {0.0, 0.0};
+    FgD2 zn[RES ? (NC + 1) / 2 : 1];                                 // RES: every pair of the wave's next transition
     bool have_pre = false;
     const uint32_t first_block = DENSE ? 0u : (HALF == 2 ? (uint32_t)(((k0 + half < d) ? k0 + half : k0) >> 1)
                                                          : (uint32_t)(k0 >> 1) + ((HALF == 1 && half && k0 + 2 < k1) ? 1u : 0u));
@@ -395,7 +423,41 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         double zb = 0.0;
         FgD2 zzh = {0.0, 0.0}; bool zh_next = false;                 // half tiles: the pair a lane half generated, and whether the upper half's is the next pair
         const double *termsE = terms;                                // rows of the endpoint's score terms
-        if (DFAST) {
+        // RES: the lane's chain and LDS column, opaque to the compiler once per transition -- otherwise it hoists every row address
+        // and global index of the unrolled coordinates out of the transition loop and spills them
+        int lnl = lane;
+        long long cl = c;
+        if (RES) { asm volatile("" : "+v"(lnl)); asm volatile("" : "+v"(cl)); }
+        double *termsR = RES ? lds + (long long)(srows + 2 * d) * tw + lnl : terms;
+        double *kin0R = RES ? lds + (long long)srows * tw + lnl : kin0;
+        double *kin1R = RES ? kin0R + (long long)d * tw : kin1;
+        if (RES) {
+#pragma unroll
+            for (int j = 0; j < NCX; ++j) {
+                if (j >= nown) break;
+                const int i = k0 + j;
+                if (prio_turns) { if ((j ^ (wv >> 2)) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+                double z;
+                if (!(j & 1)) { const FgD2 zz = have_pre ? zn[j >> 1] : fg_cold_normal_pair(sk0, sk1, gchain, (uint32_t)(i >> 1), (uint32_t)iter, FG_RNG_HMC); z = zz.a; zb = zz.b; }
+                else z = zb;
+                double p = MASS ? z * msr[j] : z;
+                const double mii = mir[j];
+                kin0R[i * tw] = MASS ? p * p * mii : p * p;
+                double q = qc[j];
+                const double emi = MASS ? e * mii : e;
+                const double q0 = q, p0 = p;
+                const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + roff[j]);
+                fg_sep_trajectory<NOBS_R, true, false, false, U0_R>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R);
+                if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // some force component may have been non-finite: the exact per-step test
+                    // (inline, not fg_sep_trajectory_checked: no call.  Its generic record mix computes the same bits for this shape:
+                    // every record is POW2 -- (x - mu) * (1 / sigma) -- and a U0 record is exactly N(0, 1), see FG_SEP_LP_U)
+                    q = q0; p = p0;
+                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R) || bad;
+                }
+                qpr[j] = q;                                              // the proposal
+                kin1R[i * tw] = MASS ? p * p * mii : p * p;
+            }
+        } else if (DFAST) {
             const int own[4] = { seg.own[wv][0], seg.own[wv][1], seg.own[wv][2], seg.own[wv][3] };
 #define FG_DENSE_CALL(NC_, OBS_) fg_dense_trajectory<NC_, OBS_, MASS>(P, X, H, own, terms, qrow, kin0, kin1, tw, n_pri, n_s, L, e, h, two_h, rcp_2h, sk0, sk1, gchain, (uint32_t)iter, c, live)
             const int nown = seg.n_own[wv];
@@ -563,7 +625,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         // hides wave 0's serial phase) adds them on four waves, a fifth draws the accept uniform; wave 0 keeps the first sum and picks the
         // others up behind a barrier -- the same additions in the same order either way.
         const int W = (int)(blockDim.x >> 6);
-        const bool sum4 = HALF != 0 && seg.sum4 != 0 && W >= 4;        // (compile-time off for 64-chain tiles: their instantiation keeps its registers)
+        const bool sum4 = (HALF != 0 || RES) && seg.sum4 != 0 && W >= 4;        // (compile-time off for plain 64-chain tiles: their instantiation keeps its registers; FG_HMC_SUM4=1 reaches the resident form)
         double s0 = 0.0;
         if (sum4) {
             if (wv == 0) s0 = fg_inorder_sum1(kin0, d, tw);
@@ -574,6 +636,12 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             __syncthreads();
         }
         have_pre = false;
+        if (RES && seg.predraw && wv != 0 && t + 1 < n_steps) {          // the next transition's momenta, behind wave 0
+#pragma unroll
+            for (int jp = 0; jp < (NCX + 1) / 2; ++jp)
+                if (2 * jp < nown) zn[jp] = fg_cold_normal_pair(sk0, sk1, gchain, (uint32_t)(k0 >> 1) + (uint32_t)jp, (uint32_t)(iter + 1), FG_RNG_HMC);
+            have_pre = true;
+        }
         if (HALF != 0 && seg.sum4 != 0 && wv != 0 && t + 1 < n_steps && k0 < k1 && !(k0 & 1)) {
             zpre = fg_cold_normal_pair(sk0, sk1, gchain, first_block, (uint32_t)(iter + 1), FG_RNG_HMC);
             have_pre = true;
@@ -626,17 +694,12 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         const bool acc = xch[tw] != 0.0;
         unsigned long long wn = 0;
         if (warming && welford_on) wn = H.w_n[c] + 1ull;          // every wave reads the old count before wave 0 bumps it below
-        for (int jo = 0; jo < (DFAST ? seg.n_own[wv] : k1 - k0); jo += 1 << HALF) {   // commit or roll back the own f64 sites
-            const int i0 = DFAST ? seg.own[wv][jo] : k0 + jo;
-            const bool on = !HALF || i0 + half < d;
-            const int i = HALF ? (on ? i0 + half : i0) : i0;
-            const long long g = (long long)P.f64_site[i] * X.C + c;
-            const double x = acc ? H.p0_scratch[(long long)i * X.C + c] : fg_as_double(X.values[g]);
-            if (acc && live && on) X.values[g] = fg_as_i64(x);
-            if (live && on && pos_all) pos_all[((long long)t * d + i) * X.C + c] = x;
+        // the committed value x of coordinate i: draws, positions, Welford (cc: the lane's chain)
+        auto commit = [&](int i, double x, bool on, long long cc) {
+            if (live && on && pos_all) pos_all[((long long)t * d + i) * X.C + cc] = x;
             if (warming) {
                 if (welford_on) {                                 // Welford::push: hmc.rs:202-211
-                    const long long gi = (long long)i * X.C + c;
+                    const long long gi = (long long)i * X.C + cc;
                     const double n = (double)wn;
                     double mean = H.w_mean[gi];
                     const double delta = x - mean;
@@ -644,7 +707,25 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                     const double delta2 = x - mean;
                     if (live && on) { H.w_mean[gi] = mean; H.w_m2[gi] += delta * delta2; }
                 }
-            } else if (draws && live && on) draws[((long long)(t - first_sample_t) * d + i) * X.C + c] = x;   // hmc.rs:577-582
+            } else if (draws && live && on) draws[((long long)(t - first_sample_t) * d + i) * X.C + cc] = x;   // hmc.rs:577-582
+        };
+        if (RES) {                                                  // commit or roll back: a select (the value rows: at the launch's end)
+#pragma unroll
+            for (int j = 0; j < NCX; ++j) {
+                if (j >= nown) break;
+                const double x = acc ? qpr[j] : qc[j];
+                qc[j] = x;
+                commit(k0 + j, x, true, cl);
+            }
+        } else
+        for (int jo = 0; jo < (DFAST ? seg.n_own[wv] : k1 - k0); jo += 1 << HALF) {   // commit or roll back the own f64 sites
+            const int i0 = DFAST ? seg.own[wv][jo] : k0 + jo;
+            const bool on = !HALF || i0 + half < d;
+            const int i = HALF ? (on ? i0 + half : i0) : i0;
+            const long long g = (long long)P.f64_site[i] * X.C + c;
+            const double x = acc ? H.p0_scratch[(long long)i * X.C + c] : fg_as_double(X.values[g]);
+            if (acc && live && on) X.values[g] = fg_as_i64(x);
+            commit(i, x, on, c);
         }
         if (warming && welford_on) {
             __syncthreads();                                      // all waves hold the old count
@@ -655,11 +736,42 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
 #ifdef FG_HMC_PROF
     if (blockIdx.x == 0 && lane == 0) for (int q = 0; q < 8; ++q) fg_hmc_prof[wv][q] = prof_[q];
 #endif
+    if (RES && live) {
+#pragma unroll
+        for (int j = 0; j < NCX; ++j)
+            if (j < nown) X.values[(long long)P.f64_site[k0 + j] * X.C + c] = fg_as_i64(qc[j]);
+    }
     if (wv == 0 && live0) {
         H.lj[c] = lj; H.eps[c] = eps; H.frozen[c] = frozen;
         H.da_mu[c] = da_mu; H.da_leb[c] = da_leb; H.da_hbar[c] = da_hbar; H.da_m[c] = da_m;
         H.alpha_sum[c] += asum; H.n_div[c] += ndiv;
     }
+}
+
+// the resident form (NC > 0) of one record shape: 0 .. 3 observations, 4: U0 prior + one observation
+template <bool MASS, int NC, int NOBS, bool U0>
+static int fg_sep_res_go(fg_engine *e, unsigned tiles, int W, size_t lds, const FgSegSep &seg, int iter0, int n, int welford_on, double *draws,
+                         int first_sample_t, double *pos_all, double *info) {
+    static bool attr_set_dev[64];
+    bool &attr_set = attr_set_dev[e->device & 63];
+    if (!attr_set) {
+        const hipError_t he = hipFuncSetAttribute((const void *)k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0>), dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->H, seg, iter0, n,
+                       e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
+    return FG_OK;
+}
+template <bool MASS, int NC>
+static int fg_sep_res_shape(int shape, fg_engine *e, unsigned tiles, int W, size_t lds, const FgSegSep &seg, int iter0, int n, int welford_on,
+                            double *draws, int first_sample_t, double *pos_all, double *info) {
+#define FG_SEP_RES(NO, UU) fg_sep_res_go<MASS, NC, NO, UU>(e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
+    switch (shape) {
+        case 0: return FG_SEP_RES(0, false); case 1: return FG_SEP_RES(1, false); case 2: return FG_SEP_RES(2, false);
+        case 3: return FG_SEP_RES(3, false); default: return FG_SEP_RES(1, true);
+    }
+#undef FG_SEP_RES
 }
 
 // Launch for `n` transitions from iteration `iter0`; returns FG_E_UNSUPPORTED when the program / configuration is not an
@@ -673,10 +785,10 @@ int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *dr
     // half tiles (32 chains per workgroup, the two coordinates of a Box-Muller pair in the two lane halves): when 64-chain tiles
     // would leave half of the CUs without one, for programs whose coordinates all have one record shape with power-of-two sigmas
     int half = 0;                                            // 1: half tiles, 2: quarter tiles (16 chains, four coordinates per wave)
+    const std::vector<FgSepCoord> &cdu = e->prog->sep_coord;
+    bool uniform = true;
+    for (const FgSepCoord &q : cdu) uniform = uniform && q.n == cdu[0].n && (q.n & 256);
     if (!dense && !analytic && e->d >= 2) {
-        const std::vector<FgSepCoord> &cd = e->prog->sep_coord;
-        bool uniform = true;
-        for (const FgSepCoord &q : cd) uniform = uniform && q.n == cd[0].n && (q.n & 256);
         // half tiles up to two of them per CU (16 384 chains: 1.57e10 with 64-chain tiles, 1.67e10, 1.75e10 with the late start below);
         // quarter tiles where even half tiles leave CUs without one (4 096 chains: 6.7e9 -> 9.2e9; at 8 192 the two are level)
         if (uniform && tiles64 <= n_cu) half = (4 * tiles64 < 2 * n_cu && e->d >= 8) ? 2 : 1;
@@ -745,6 +857,26 @@ int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *dr
     if (W == 8 && !half && !(std::getenv("FG_HMC_PRIO") && std::atoi(std::getenv("FG_HMC_PRIO")) == 0)) seg.c[FG_SEP_WMAX] = -1;   // priority turns: two waves of a tile per SIMD
     if (half == 1 && (long long)tiles > n_cu && (long long)tiles <= 2 * n_cu) seg.c[FG_SEP_WMAX] = -3;                                  // two half tiles on a CU: the odd ones start late (+5 %; 64-chain tiles lose 5 % to it)
     if (const char *sg = std::getenv("FG_HMC_STAGGER")) { const int v = std::atoi(sg); seg.c[FG_SEP_WMAX] = (v == 1 || v == 2) ? -1 - v : (seg.c[FG_SEP_WMAX] <= -2 ? e->d : seg.c[FG_SEP_WMAX]); }   // experiments
+    // the resident form: 64-chain sparse tiles of one record shape with power-of-two sigmas, <= 4 coordinates per wave
+    int res_nc = 0;
+    if (!dense && !analytic && !half && uniform && e->P.n_sep_free == 0 && !e->sep_res_disabled && (cdu[0].n & 7) >= 1 && (cdu[0].n & 7) <= 4) {
+        int most = 0;
+        for (int w = 0; w < W; ++w) most = std::max(most, (w + 1 < W ? seg.c[w + 1] : e->d) - seg.c[w]);
+        res_nc = most <= 2 ? 2 : (most <= 4 ? 4 : 0);
+    }
+    seg.predraw = 1;
+    if (const char *pv = std::getenv("FG_HMC_PREDRAW")) seg.predraw = std::atoi(pv) != 0 ? 1 : 0;   // experiments
+    if (res_nc) {
+        const int nobs = (cdu[0].n & 7) - 1, shape = ((cdu[0].n & 512) && nobs == 1) ? 4 : nobs;
+        const int rc = res_nc == 2 ? (e->H.use_mass ? fg_sep_res_shape<true, 2>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
+                                                    : fg_sep_res_shape<false, 2>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info))
+                                   : (e->H.use_mass ? fg_sep_res_shape<true, 4>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
+                                                    : fg_sep_res_shape<false, 4>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info));
+        if (rc != FG_OK) return rc;
+        HIPCHK(hipGetLastError());
+        e->last_hmc_kernel = std::string("k_hmc_sep_steps (resident) W=") + std::to_string(W);
+        return FG_OK;
+    }
     static bool attr_set_dev[64][12];
     const int mass = e->H.use_mass ? 1 : 0, mode = dense ? 1 : (analytic ? 2 : 0), variant = dfast ? 10 + mass : (half ? 4 + 2 * half + mass : 2 * mode + mass);
     const void *fns[12] = { (const void *)k_hmc_sep_steps<false, 0>, (const void *)k_hmc_sep_steps<true, 0>, (const void *)k_hmc_sep_steps<false, 1>,
