@@ -743,6 +743,7 @@ fg_engine *fg_engine_new(const fg_program *p, int64_t n_chains, uint64_t seed, u
     if (const char *mw = std::getenv("FG_HMC_WAVES")) { const int w = std::atoi(mw); if (w == 1 || w == 2 || w == 4 || w == 8 || w == 16) e->mw_override = w; }
     if (const char *sp = std::getenv("FG_HMC_SEP")) e->sep_disabled = std::atoi(sp) == 0;
     if (const char *sp = std::getenv("FG_HMC_SEP_RESIDENT")) e->sep_res_disabled = std::atoi(sp) == 0;
+    if (const char *sp = std::getenv("FG_HMC_SEP_FOLD")) e->sep_fold_disabled = std::atoi(sp) == 0;
     if (const char *sp = std::getenv("FG_HMC_LIN")) e->lin_disabled = std::atoi(sp) == 0;
     if (const char *sp = std::getenv("FG_HMC_INTERP_MW")) e->interp_mw_disabled = std::atoi(sp) == 0;
     if (const char *sp = std::getenv("FG_MH_MW")) e->mh_mw_disabled = std::atoi(sp) == 0;

@@ -45,6 +45,7 @@ struct fg_engine {
     bool mh_has_prior_resample = false;   // an override asks for PriorResample on some site (needs the model-driven proposal path)
     bool sep_disabled = false;   // FG_HMC_SEP=0: keep independent-sites programs on the gradient-stream kernel (A/B tests)
     bool sep_res_disabled = false;   // FG_HMC_SEP_RESIDENT=0: 64-chain sparse tiles without the resident form of k_hmc_sep_steps (A/B tests)
+    bool sep_fold_disabled = false;  // FG_HMC_SEP_FOLD=0: k_hmc_sep_steps's trajectories without the folded loop (A/B tests)
     bool gt = false;             // the program's tile exceeds a CU's LDS: tiles in global memory, one-wave-per-tile kernels only
     double *d_gtile = nullptr;
     bool lin_disabled = false;   // FG_HMC_LIN=0: keep dense regressions on the gradient-stream kernel (A/B tests)

@@ -79,6 +79,19 @@ __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const char *p) { return *(const f
     double outp, outm;                                                                                 \
     { const double c = fg_dbl(a##k[2], a##k[3]); const double zp = FG_SEP_Z(k, qp - c), zm = FG_SEP_Z(k, qm - c); \
       outp = FG_SEP_LPF(k, zp); outm = FG_SEP_LPF(k, zm); }
+// FG_SEP_DUALF in one instruction less per sign (FOLD, P2 records): s = 1 / sigma = 2^k is folded into the fma's coefficient,
+// nhs2 = -0.5 s^2 (exact, from the record), and d = q -+ h - c is squared unscaled: fma(nhs2, RN(d d), -ln sigma).  d s is exact and
+// RN(d^2 s^2) = s^2 RN(d^2) in the normal range, so both fmas see the same exact product.  Elsewhere: d^2 or (d s)^2 below
+// 2^-1022 leaves both products under a quarter ulp of ln sigma (|ln sigma| >= ln 2 when s != 1; the host keeps s <= 2^480), which
+// swallows them; (d s)^2 >= 2^1024 with d^2 finite gives the reference's own finite value where FG_SEP_LPF gave -inf; d^2 = inf gives
+// -inf, a non-finite endpoint momentum and the checked re-run.
+// nhs2 sits in VGPRs (fg_sep_trajectory, before the loop): with ln sigma it would be a second scalar operand of the fma, which the VALU
+// cannot take -- the compiler then moves one of them into VGPRs in every step.
+#define FG_SEP_DUALS(k, outp, outm)                                                                    \
+    double outp, outm;                                                                                 \
+    { const double c = fg_dbl(a##k[2], a##k[3]); const double dp = qp - c, dm = qm - c;                \
+      outp = __builtin_fma(nhs2_##k, dp * dp, -fg_dbl(a##k[6], a##k[7])) - 0.5 * FG_LN_2PI;            \
+      outm = __builtin_fma(nhs2_##k, dm * dm, -fg_dbl(a##k[6], a##k[7])) - 0.5 * FG_LN_2PI; }
 // record k at q + h and q - h with the guard of a scoring run (the dense mode adds these into whole log-joints)
 #define FG_SEPD_OWN(k, outp, outm) double outp, outm;                                                  \
     { const double c_ = fg_dbl(a##k[2], a##k[3]); const double zp_ = FG_SEP_Z(k, qp - c_), zm_ = FG_SEP_Z(k, qm - c_); \
@@ -97,13 +110,23 @@ __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const char *p) { return *(const f
 // two v_cndmask per f64 and a compare in a loop that is bound by VALU issue).
 // AN = FG_GRAD_ANALYTIC: g_i = sum over the coordinate's records of d lp / d q_i = -(q - c) / sigma^2, one evaluation per record,
 // the additions of fg_grec_math's analytic branch in the same order ((x - mu) is +-(q - c) and its coefficient -+1: the same bits).
-template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, typename RB = const FG_AS4 char *>
+// FOLD (CHECK = false, host switch FG_HMC_SEP_FOLD): P2 records take FG_SEP_DUALS, and the range test of the quotient leaves the step
+// too.  g is always fg_div_const's; a 32-bit running maximum over the high word of n records whether some |n| fell outside
+// [2^-823, 2^953) (0, inf and NaN included), and such a trajectory ends with a NaN momentum: the caller's non-finite test re-runs it
+// with the CHECK instance, whose per-step test and true division give the exact bits.  In range the two quotients are the same.
+template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, bool FOLD = false, typename RB = const FG_AS4 char *>
 __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p_io, double emi, double hk, int L, double h, double two_h,
                                                   double rcp_2h, double *terms, int tw, int nobs_rt) {
 #define FG_SEP_HAS(k) (NOBS >= 0 ? NOBS >= (k) : nobs_rt >= (k))
     FG_SEP_LOAD(0) FG_SEP_LOAD(1) FG_SEP_LOAD(2) FG_SEP_LOAD(3)
     double q = q_io, p = p_io;
     bool bad = false;
+    constexpr bool FOLDED = FOLD && P2 && !CHECK && !AN;
+    double nhs2_0 = 0.0, nhs2_1 = 0.0, nhs2_2 = 0.0, nhs2_3 = 0.0;    // FOLDED: -0.5 / sigma^2 of each record, in VGPRs
+#define FG_SEP_NHS2(k) if (FOLDED && (k > 0 || !U0) && FG_SEP_HAS(k)) { nhs2_##k = fg_dbl(b##k[2], b##k[3]); asm volatile("" : "+v"(nhs2_##k)); }
+    FG_SEP_NHS2(0) FG_SEP_NHS2(1) FG_SEP_NHS2(2) FG_SEP_NHS2(3)
+#undef FG_SEP_NHS2
+    uint32_t nrange = 0u;                                        // FOLD: max over the steps of 2 |hi(n)| - 2 hi(2^-823), mod 2^32
     for (int gs = 0; gs <= L; ++gs) {
         double g;
         if (AN) {
@@ -119,7 +142,17 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         } else {
         const double qp = q + h, qm = q - h;                     // the perturbed coordinate holds orig +- h (hmc.rs:317-319)
         double tp, tm;
-        if (!CHECK) {                                            // fused forms: a non-finite force re-runs the coordinate with CHECK
+        if (FOLDED) {                                            // folded fused form
+            if (U0) { tp = FG_SEP_LPF_U(qp); tm = FG_SEP_LPF_U(qm); }
+            else { FG_SEP_DUALS(0, tp_, tm_) tp = tp_; tm = tm_; }
+            if (FG_SEP_HAS(1)) {
+                FG_SEP_DUALS(1, lp1, lm1)
+                double sp = lp1, sm = lm1;
+                if (FG_SEP_HAS(2)) { FG_SEP_DUALS(2, lp2, lm2) sp += lp2; sm += lm2; }
+                if (FG_SEP_HAS(3)) { FG_SEP_DUALS(3, lp3, lm3) sp += lp3; sm += lm3; }
+                tp = tp + sp; tm = tm + sm;                      // log_prior + log_likelihood
+            }
+        } else if (!CHECK) {                                     // fused forms: a non-finite force re-runs the coordinate with CHECK
             if (U0) { tp = FG_SEP_LPF_U(qp); tm = FG_SEP_LPF_U(qm); }
             else { FG_SEP_DUALF(0, tp_, tm_) tp = tp_; tm = tm_; }
             if (FG_SEP_HAS(1)) {
@@ -142,8 +175,15 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         }
         const double n = tp - tm;
         g = fg_div_const(n, two_h, rcp_2h);                      // (lp - lm) / (2h), hmc.rs:322
+        if (!CHECK && FOLD) {                                    // in range iff 2 |hi(n)| - 0x19000000 < 0xde000000 (mod 2^32)
+            uint32_t hi = (uint32_t)__double2hiint(n);
+            asm("" : "+v"(hi));                                  // (else the shift is folded into the 64-bit word: v_alignbit + v_and)
+            const uint32_t nr = (hi << 1) - 0x19000000u;
+            nrange = nrange > nr ? nrange : nr;
+        } else {
         const double an = __builtin_fabs(n);                     // |n| outside [2^-823, 2^953] (0 and NaN too): a true division is always right
         if (__builtin_expect(__any(!(an >= 0x1p-823 && an <= 0x1p953)), 0)) g = n / two_h;
+        }
         }
         if (CHECK) bad = bad || !fg_finite(g);
         const double kick = hk * g;
@@ -151,6 +191,7 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         if (gs > 0 && gs < L) { asm volatile(""); p = p + kick; }   // trailing kick of this step + leading kick of the next
         if (gs < L) { asm volatile(""); q = q + emi * p; }       // hmc.rs:391-393
     }
+    if (!CHECK && FOLD && nrange >= 0xde000000u) p = __builtin_nan("");   // some quotient out of fg_div_const's range: the checked re-run
     if (U0) { const double lp = FG_SEP_LP_U(q); terms[a0[1] * tw] = (q != q) ? FG_NEG_INF : lp; }
     else FG_SEP_TERM(0)
     if (FG_SEP_HAS(1)) FG_SEP_TERM(1)
@@ -165,7 +206,7 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
 template <bool AN, typename RB>
 __device__ __noinline__ FgD3 fg_sep_trajectory_checked(RB rb, double q, double p, double emi, double hk, int L, double h,
                                                        double two_h, double rcp_2h, double *terms, int tw, int nobs) {
-    const bool bad = fg_sep_trajectory<-1, false, true, AN, false, RB>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, nobs);
+    const bool bad = fg_sep_trajectory<-1, false, true, AN, false, false, RB>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, nobs);
     FgD3 r; r.a = q; r.b = p; r.c = bad ? 1.0 : 0.0;
     return r;
 }
@@ -312,7 +353,7 @@ __device__ __forceinline__ bool fg_dense_trajectory(const FgProgramDev &P, const
 // wave 0 adds and decides, the other waves draw the Box-Muller pairs of their next transition.  The arithmetic per coordinate is
 // fg_sep_trajectory's for the shape NC = 0 dispatches to: every result is bit-identical to NC = 0.  (The records themselves are still
 // loaded per trajectory: held for four coordinates they spill SGPRs into the leapfrog loop.)
-template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false>
+template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false, bool FOLD = false>
 __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgProgramDev P, FgChainCtx X, FgHmcDev H, FgSegSep seg, int iter0, int n_steps,
                                                                              int n_warmup, int welford_on, double *draws, int first_sample_t,
                                                                              double *pos_all /*[n][d][C] or null*/, double *info /*[n][4][C] or null*/) {
@@ -323,6 +364,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     constexpr bool RES = NC > 0;
     constexpr int NCX = RES ? NC : 1;
     static_assert(!RES || (MODE == 0 && HALF == 0 && NC <= 4 && NOBS_R >= 0 && NOBS_R <= 3), "resident form: sparse 64-chain tiles");
+    static_assert(!FOLD || MODE == 0, "the folded trajectory loop: sparse finite difference only");
     const int lane = threadIdx.x & (tw - 1);                       // chain of the tile
     const int half = HALF == 1 ? (int)((threadIdx.x >> 5) & 1u) : (HALF == 2 ? (int)((threadIdx.x >> 4) & 3u) : 0);   // which of the wave's 2 / 4 coordinates this lane runs
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -447,8 +489,8 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                 const double emi = MASS ? e * mii : e;
                 const double q0 = q, p0 = p;
                 const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + roff[j]);
-                fg_sep_trajectory<NOBS_R, true, false, false, U0_R>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R);
-                if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // some force component may have been non-finite: the exact per-step test
+                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R);
+                if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                     // (inline, not fg_sep_trajectory_checked: no call.  Its generic record mix computes the same bits for this shape:
                     // every record is POW2 -- (x - mu) * (1 / sigma) -- and a U0 record is exactly N(0, 1), see FG_SEP_LP_U)
                     q = q0; p = p0;
@@ -592,22 +634,22 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             const double q0 = q, p0 = p;
             if (HALF) {
                 const char *rb = (const char *)(P.sep + P.sep_coord[ci].off);
-#define FG_SEP_CALLH(NO, UU) fg_sep_trajectory<NO, true, false, false, UU, const char *>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO)
+#define FG_SEP_CALLH(NO, UU) fg_sep_trajectory<NO, true, false, false, UU, FOLD, const char *>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO)
                 if ((cd.n & 512) && nobs == 1) FG_SEP_CALLH(1, true);
                 else if (nobs == 1) FG_SEP_CALLH(1, false); else if (nobs == 0) FG_SEP_CALLH(0, false); else if (nobs == 2) FG_SEP_CALLH(2, false); else FG_SEP_CALLH(3, false);
 #undef FG_SEP_CALLH
-                if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // some force component may have been non-finite: the exact per-step test
+                if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                     const FgD3 r = fg_sep_trajectory_checked<AN, const char *>(rb, q0, p0, emi, hk, L, h, two_h, rcp_2h, terms, tw, nobs);
                     q = r.a; p = r.b; bad = bad || (on && r.c != 0.0);
                 }
             } else {
             const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + cd.off);
-#define FG_SEP_CALL(NO, PP) fg_sep_trajectory<NO, PP, false, AN>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO)
-            if (!AN && (cd.n & 512) && nobs == 1) fg_sep_trajectory<1, true, false, false, true>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, 1);
+#define FG_SEP_CALL(NO, PP) fg_sep_trajectory<NO, PP, false, AN, false, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO)
+            if (!AN && (cd.n & 512) && nobs == 1) fg_sep_trajectory<1, true, false, false, true, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, 1);
             else if (cd.n & 256) { if (nobs == 1) FG_SEP_CALL(1, true); else if (nobs == 0) FG_SEP_CALL(0, true); else if (nobs == 2) FG_SEP_CALL(2, true); else FG_SEP_CALL(3, true); }
             else { if (nobs == 1) FG_SEP_CALL(1, false); else if (nobs == 0) FG_SEP_CALL(0, false); else if (nobs == 2) FG_SEP_CALL(2, false); else FG_SEP_CALL(3, false); }
 #undef FG_SEP_CALL
-            if (__builtin_expect(__any(!fg_finite(p)), 0)) {           // some force component may have been non-finite: the exact per-step test
+            if (__builtin_expect(__any(!fg_finite(p)), 0)) {           // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                 const FgD3 r = fg_sep_trajectory_checked<AN, const FG_AS4 char *>(rb, q0, p0, emi, hk, L, h, two_h, rcp_2h, terms, tw, nobs);
                 q = r.a; p = r.b; bad = bad || r.c != 0.0;
             }
@@ -749,24 +791,24 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
 }
 
 // the resident form (NC > 0) of one record shape: 0 .. 3 observations, 4: U0 prior + one observation
-template <bool MASS, int NC, int NOBS, bool U0>
+template <bool MASS, int NC, int NOBS, bool U0, bool FOLD>
 static int fg_sep_res_go(fg_engine *e, unsigned tiles, int W, size_t lds, const FgSegSep &seg, int iter0, int n, int welford_on, double *draws,
                          int first_sample_t, double *pos_all, double *info) {
     static bool attr_set_dev[64];
     bool &attr_set = attr_set_dev[e->device & 63];
     if (!attr_set) {
-        const hipError_t he = hipFuncSetAttribute((const void *)k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const hipError_t he = hipFuncSetAttribute((const void *)k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0>), dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->H, seg, iter0, n,
+    hipLaunchKernelGGL((k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0, FOLD>), dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->H, seg, iter0, n,
                        e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
     return FG_OK;
 }
-template <bool MASS, int NC>
+template <bool MASS, int NC, bool FOLD>
 static int fg_sep_res_shape(int shape, fg_engine *e, unsigned tiles, int W, size_t lds, const FgSegSep &seg, int iter0, int n, int welford_on,
                             double *draws, int first_sample_t, double *pos_all, double *info) {
-#define FG_SEP_RES(NO, UU) fg_sep_res_go<MASS, NC, NO, UU>(e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
+#define FG_SEP_RES(NO, UU) fg_sep_res_go<MASS, NC, NO, UU, FOLD>(e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
     switch (shape) {
         case 0: return FG_SEP_RES(0, false); case 1: return FG_SEP_RES(1, false); case 2: return FG_SEP_RES(2, false);
         case 3: return FG_SEP_RES(3, false); default: return FG_SEP_RES(1, true);
@@ -864,26 +906,32 @@ int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *dr
         for (int w = 0; w < W; ++w) most = std::max(most, (w + 1 < W ? seg.c[w + 1] : e->d) - seg.c[w]);
         res_nc = most <= 2 ? 2 : (most <= 4 ? 4 : 0);
     }
+    // the folded trajectory loop (fg_sep_trajectory's FOLD): sparse finite differences, the host's range of 1 / sigma
+    const bool fold = !dense && !analytic && e->prog->sep_fold && !e->sep_fold_disabled;
     seg.predraw = 1;
     if (const char *pv = std::getenv("FG_HMC_PREDRAW")) seg.predraw = std::atoi(pv) != 0 ? 1 : 0;   // experiments
     if (res_nc) {
         const int nobs = (cdu[0].n & 7) - 1, shape = ((cdu[0].n & 512) && nobs == 1) ? 4 : nobs;
-        const int rc = res_nc == 2 ? (e->H.use_mass ? fg_sep_res_shape<true, 2>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
-                                                    : fg_sep_res_shape<false, 2>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info))
-                                   : (e->H.use_mass ? fg_sep_res_shape<true, 4>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
-                                                    : fg_sep_res_shape<false, 4>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info));
+#define FG_SEP_RES_NC(NC_, FO) (e->H.use_mass ? fg_sep_res_shape<true, NC_, FO>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info) \
+                                              : fg_sep_res_shape<false, NC_, FO>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info))
+        const int rc = res_nc == 2 ? (fold ? FG_SEP_RES_NC(2, true) : FG_SEP_RES_NC(2, false)) : (fold ? FG_SEP_RES_NC(4, true) : FG_SEP_RES_NC(4, false));
+#undef FG_SEP_RES_NC
         if (rc != FG_OK) return rc;
         HIPCHK(hipGetLastError());
-        e->last_hmc_kernel = std::string("k_hmc_sep_steps (resident) W=") + std::to_string(W);
+        e->last_hmc_kernel = std::string(fold ? "k_hmc_sep_steps (resident) (folded) W=" : "k_hmc_sep_steps (resident) W=") + std::to_string(W);
         return FG_OK;
     }
-    static bool attr_set_dev[64][12];
-    const int mass = e->H.use_mass ? 1 : 0, mode = dense ? 1 : (analytic ? 2 : 0), variant = dfast ? 10 + mass : (half ? 4 + 2 * half + mass : 2 * mode + mass);
-    const void *fns[12] = { (const void *)k_hmc_sep_steps<false, 0>, (const void *)k_hmc_sep_steps<true, 0>, (const void *)k_hmc_sep_steps<false, 1>,
+    static bool attr_set_dev[64][18];
+    const int mass = e->H.use_mass ? 1 : 0, mode = dense ? 1 : (analytic ? 2 : 0);
+    const int variant = dfast ? 10 + mass : (mode == 0 && fold ? 12 + 2 * half + mass : (half ? 4 + 2 * half + mass : 2 * mode + mass));
+    const void *fns[18] = { (const void *)k_hmc_sep_steps<false, 0>, (const void *)k_hmc_sep_steps<true, 0>, (const void *)k_hmc_sep_steps<false, 1>,
                            (const void *)k_hmc_sep_steps<true, 1>, (const void *)k_hmc_sep_steps<false, 2>, (const void *)k_hmc_sep_steps<true, 2>,
                            (const void *)k_hmc_sep_steps<false, 0, 1>, (const void *)k_hmc_sep_steps<true, 0, 1>,
                            (const void *)k_hmc_sep_steps<false, 0, 2>, (const void *)k_hmc_sep_steps<true, 0, 2>,
-                           (const void *)k_hmc_sep_steps<false, 3>, (const void *)k_hmc_sep_steps<true, 3> };
+                           (const void *)k_hmc_sep_steps<false, 3>, (const void *)k_hmc_sep_steps<true, 3>,
+                           (const void *)k_hmc_sep_steps<false, 0, 0, 0, 0, false, true>, (const void *)k_hmc_sep_steps<true, 0, 0, 0, 0, false, true>,
+                           (const void *)k_hmc_sep_steps<false, 0, 1, 0, 0, false, true>, (const void *)k_hmc_sep_steps<true, 0, 1, 0, 0, false, true>,
+                           (const void *)k_hmc_sep_steps<false, 0, 2, 0, 0, false, true>, (const void *)k_hmc_sep_steps<true, 0, 2, 0, 0, false, true> };
     bool &attr_set = attr_set_dev[e->device & 63][variant];
     if (!attr_set) {
         const hipError_t he = hipFuncSetAttribute(fns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -897,11 +945,16 @@ int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *dr
         case 3: FG_SEP_LAUNCH(true, 1); break;  case 4: FG_SEP_LAUNCH(false, 2); break; case 5: FG_SEP_LAUNCH(true, 2); break;
         case 6: FG_SEP_LAUNCH(false, 0, 1); break; case 7: FG_SEP_LAUNCH(true, 0, 1); break;
         case 8: FG_SEP_LAUNCH(false, 0, 2); break; case 9: FG_SEP_LAUNCH(true, 0, 2); break;
-        case 10: FG_SEP_LAUNCH(false, 3); break; default: FG_SEP_LAUNCH(true, 3); break;
+        case 10: FG_SEP_LAUNCH(false, 3); break; case 11: FG_SEP_LAUNCH(true, 3); break;
+        case 12: FG_SEP_LAUNCH(false, 0, 0, 0, 0, false, true); break; case 13: FG_SEP_LAUNCH(true, 0, 0, 0, 0, false, true); break;
+        case 14: FG_SEP_LAUNCH(false, 0, 1, 0, 0, false, true); break; case 15: FG_SEP_LAUNCH(true, 0, 1, 0, 0, false, true); break;
+        case 16: FG_SEP_LAUNCH(false, 0, 2, 0, 0, false, true); break; default: FG_SEP_LAUNCH(true, 0, 2, 0, 0, false, true); break;
     }
 #undef FG_SEP_LAUNCH
     HIPCHK(hipGetLastError());
-    e->last_hmc_kernel = std::string(dfast ? "k_hmc_sep_steps (dense, coordinates in registers) W=" : dense ? "k_hmc_sep_steps (dense) W=" : (analytic ? "k_hmc_sep_steps (analytic) W=" : (half == 2 ? "k_hmc_sep_steps (quarter tiles) W=" : (half ? "k_hmc_sep_steps (half tiles) W=" : "k_hmc_sep_steps W=")))) + std::to_string(W);
+    e->last_hmc_kernel = std::string(dfast ? "k_hmc_sep_steps (dense, coordinates in registers) W=" : dense ? "k_hmc_sep_steps (dense) W=" : (analytic ? "k_hmc_sep_steps (analytic) W=" : (half == 2 ? "k_hmc_sep_steps (quarter tiles) W=" : (half ? "k_hmc_sep_steps (half tiles) W=" : "k_hmc_sep_steps W="))));
+    if (variant >= 12) e->last_hmc_kernel.insert(e->last_hmc_kernel.size() - 2, "(folded) ");
+    e->last_hmc_kernel += std::to_string(W);
     return FG_OK;
 }
 

@@ -104,7 +104,8 @@ static_assert(sizeof(FgGradRec) == 64, "FgGradRec must be 64 bytes");
 //   flags: FG_G_POW2 / FG_G_DIV as in the gradient stream;  trow = LDS row of the statement's endpoint-score term
 //   (prior terms first, then likelihood terms, each in program order).
 #define FG_SEP_MAXREC 4
-struct FgSepRec { uint32_t flags, trow; double c, inv, lns, sigma; double pad1[3]; };   // dwords 0..7 = one s_load_dwordx8, sigma = dwords 8..9
+//   nhs2 = -0.5 / sigma^2 (power-of-two sigma: exact), the coefficient of the folded hot-loop density (fg_hmc_sep.hip, FG_SEP_DUALS).
+struct FgSepRec { uint32_t flags, trow; double c, inv, lns, sigma, nhs2; double pad1[2]; };   // dwords 0..7 = one s_load_dwordx8, sigma / nhs2 = dwords 8..11
 static_assert(sizeof(FgSepRec) == 64, "FgSepRec must be 64 bytes");
 struct FgSepCoord { int off, n; };     // records of coordinate k: sep[off .. off + (n & 7)); bit 8 of n: every sigma is a power of two; bit 9: and record 0 is Normal(0, 1)
 struct FgSepFree { uint32_t sidx, trow; };   // score-stream statements that read no coordinate: evaluated once per launch

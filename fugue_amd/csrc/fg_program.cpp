@@ -661,7 +661,7 @@ int fg_program::finalize() {
         if (n_sstream > 0) for (size_t i = 0; i < stmts.size(); i++) if (stmts[i].kind == 0) site_rec[stmts[i].sorted] = (int)i;
     }
     // independent-sites programs: compact per-coordinate records for the register-resident trajectories
-    sep.clear(); sep_coord.clear(); sep_free.clear();
+    sep.clear(); sep_coord.clear(); sep_free.clear(); sep_fold = false;
     if (n_gstream > 0 && n_sstream > 0 && !sstream_has_lin && !sstream_has_gen) {
         bool ok = true;
         // LDS row of every statement's score term: prior terms first, then likelihood terms, each in program order
@@ -689,6 +689,7 @@ int fg_program::finalize() {
             q.trow = trow[si];
             q.c = x_own ? r.mimm : r.ximm;
             q.inv = r.inv; q.lns = r.lns; q.sigma = r.sigma;
+            if (q.flags & FG_G_POW2) q.nhs2 = -0.5 * q.inv * q.inv;        // 1 / sigma = 2^k, |k| <= 500 (fg_pow2_scale): exact
             if (first) cds[ck].off = (int)recs.size();
             cds[ck].n += 1;
             if (cds[ck].n > FG_SEP_MAXREC) ok = false;
@@ -708,6 +709,9 @@ int fg_program::finalize() {
         if (ok) {
             for (int k = 0; k < n_sstream; k++) if (!covered[k]) sep_free.push_back(FgSepFree{(uint32_t)k, trow[k]});
             sep = recs; sep_coord = cds;
+            // the folded hot loop (fg_hmc_sep.hip, FG_SEP_DUALS) computes the fused loop's bits while 1 / sigma <= 2^480
+            sep_fold = true;
+            for (const FgSepRec &r : recs) if ((r.flags & FG_G_POW2) && !(r.inv <= 0x1p480)) sep_fold = false;
             for (int q = 0; q < FG_SEP_MAXREC; q++) { FgSepRec z; std::memset(&z, 0, sizeof(z)); sep.push_back(z); }
         }
     }

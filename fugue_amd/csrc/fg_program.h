@@ -41,6 +41,7 @@ struct fg_program {
     bool sstream_has_gen = false;       // some record is a general distribution record (FG_G_GEN)
     std::vector<FgSepRec> sep;        // empty unless the program is an independent-sites model (fg_ir.h)
     std::vector<FgSepCoord> sep_coord;
+    bool sep_fold = false;            // every power-of-two record's 1 / sigma <= 2^480: the folded hot loop is exact (fg_hmc_sep.hip)
     std::vector<FgSepFree> sep_free; int n_prior_terms = 0;
     std::vector<uint32_t> sobs;       // observe bits of the score stream
     std::vector<int> site_rec;        // [S] score-stream record of each site's sample statement
