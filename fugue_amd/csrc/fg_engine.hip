@@ -790,10 +790,7 @@ fg_engine *fg_engine_new(const fg_program *p, int64_t n_chains, uint64_t seed, u
     e->P.lin_tab = e->d_lin_tab; e->P.lin_meta = e->d_lin_meta; e->P.lin_n = p->lin_n; e->P.lin_p2 = p->lin_p2;
     e->X.C = e->C; e->X.chain0 = e->chain0; e->X.seed = e->seed; e->X.values = e->d_values;
     if (set_lds(k_prior_init<false>, lds_sc) || set_lds(k_log_joint<false>, lds_sc) || set_lds(k_log_joint_stream<false>, lds_sc) ||
-        set_lds(k_hmc_steps<false>, lds_hmc) || set_lds(k_hmc_stream_steps<0, false, true>, lds_hmc) || set_lds(k_hmc_stream_steps<1, false, true>, lds_hmc) || set_lds(k_hmc_stream_steps<2, false, true>, lds_hmc) ||
-        set_lds(k_hmc_stream_steps<0, true, true>, lds_hmc) || set_lds(k_hmc_stream_steps<1, true, true>, lds_hmc) ||
-        set_lds(k_hmc_stream_steps<0, false, false>, lds_hmc) || set_lds(k_hmc_stream_steps<1, false, false>, lds_hmc) || set_lds(k_hmc_stream_steps<2, false, false>, lds_hmc) ||
-        set_lds(k_hmc_stream_steps<0, true, false>, lds_hmc) || set_lds(k_hmc_stream_steps<1, true, false>, lds_hmc) || set_lds(k_hmc_transition_injected<false>, lds_hmc) ||
+        set_lds(k_hmc_steps<false>, lds_hmc) || set_lds(k_hmc_transition_injected<false>, lds_hmc) ||     // (k_hmc_stream_steps: at its launch, fg_launch)
         set_lds(k_hmc_grad<false>, lds_hmc) || set_lds(k_hmc_find_eps<false>, lds_hmc) ||
         set_lds(k_mh_steps<false>, lds_sc))
         return fail("hipFuncSetAttribute");
@@ -1106,18 +1103,18 @@ static int hmc_launch_steps(fg_engine *e, int iter0, int n, int welford_on, doub
             }
         int rk = e->P.sstream_kinds;                             // record kinds present in either stream
         for (int k = 0; k < nrec && rk < 2; ++k) rk = std::max(rk, (gs[k].flags & FG_G_GEN) ? 2 : ((gs[k].flags & FG_G_LIN) ? 1 : 0));
-#define FG_LAUNCH_STREAM(RK, AN, SS) hipLaunchKernelGGL((k_hmc_stream_steps<RK, AN, SS>), dim3(tiles), dim3(FG_WAVE * W), e->lds_bytes, e->stream, e->P, e->X, e->H, seg, \
-                                                        iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info)
+        using FgStreamKernel = void (*)(FgProgramDev, FgChainCtx, FgHmcDev, FgSeg, int, int, int, int, double *, int, double *, double *);
+        struct FgStreamVariant { int rk; bool an, ss; FgStreamKernel fn; unsigned long long raised; };       // record kinds, analytic gradient, the program has a score stream
+#define FG_STREAM_ENTRIES(SS) { 0, false, SS, k_hmc_stream_steps<0, false, SS> }, { 1, false, SS, k_hmc_stream_steps<1, false, SS> }, { 2, false, SS, k_hmc_stream_steps<2, false, SS> }, \
+                              { 0, true, SS, k_hmc_stream_steps<0, true, SS> }, { 1, true, SS, k_hmc_stream_steps<1, true, SS> }
+        static FgStreamVariant variants[] = { FG_STREAM_ENTRIES(true), FG_STREAM_ENTRIES(false) };
+#undef FG_STREAM_ENTRIES
         const bool ss = e->P.sstream != nullptr;
-        if (!analytic) {
-            if (ss) { if (rk == 2) FG_LAUNCH_STREAM(2, false, true); else if (rk == 1) FG_LAUNCH_STREAM(1, false, true); else FG_LAUNCH_STREAM(0, false, true); }
-            else { if (rk == 2) FG_LAUNCH_STREAM(2, false, false); else if (rk == 1) FG_LAUNCH_STREAM(1, false, false); else FG_LAUNCH_STREAM(0, false, false); }
-        } else {
-            if (ss) { if (rk == 1) FG_LAUNCH_STREAM(1, true, true); else FG_LAUNCH_STREAM(0, true, true); }
-            else { if (rk == 1) FG_LAUNCH_STREAM(1, true, false); else FG_LAUNCH_STREAM(0, true, false); }
-        }
-#undef FG_LAUNCH_STREAM
-        HIPCHK(hipGetLastError());
+        if (analytic && rk == 2) rk = 0;                         // (the analytic gradient has no general-record instantiation: such a launch has always taken the plain one)
+        FgStreamVariant *v = std::find_if(std::begin(variants), std::end(variants), [&](const FgStreamVariant &q) { return q.rk == rk && q.an == analytic && q.ss == ss; });
+        if (v == std::end(variants)) return FG_E_UNSUPPORTED;
+        const int rc = fg_launch(e, v->fn, v->raised, dim3(tiles), dim3(FG_WAVE * W), e->lds_bytes, e->P, e->X, e->H, seg, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
+        if (rc != FG_OK) return rc;
         e->last_hmc_kernel = std::string(dense_stream ? "k_hmc_stream_steps (dense stream) W=" : "k_hmc_stream_steps W=") + std::to_string(W);
         return FG_OK;
     }

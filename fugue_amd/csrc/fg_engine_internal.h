@@ -137,6 +137,24 @@ int dev_upload(T **p, const std::vector<T> &v) {
     return FG_OK;
 }
 
+// One launch of a library kernel picked from a table of typed pointers (all instantiations of a kernel template have one
+// function type: the arguments are checked against it here, once).  A tile above 64 KB needs the function's dynamic-LDS limit
+// raised, once per (device, function): `raised` is the table entry's mask of the devices that have it.
+template <typename T> struct fg_same { using type = T; };
+template <typename... P>
+int fg_launch(fg_engine *e, void (*fn)(P...), unsigned long long &raised, dim3 grid, dim3 block, size_t lds, const typename fg_same<P>::type &...args) {
+    const unsigned long long dev_bit = 1ull << (e->device & 63);
+    if (lds > 64 * 1024 && !(raised & dev_bit)) {
+        const hipError_t he = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
+        raised |= dev_bit;
+    }
+    void *argv[] = { (void *)&args... };
+    (void)hipLaunchKernel((const void *)fn, grid, block, argv, lds, e->stream);
+    HIPCHK(hipGetLastError());
+    return FG_OK;
+}
+
 }  // namespace
 
 

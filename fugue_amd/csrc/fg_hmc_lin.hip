@@ -508,30 +508,21 @@ int fg_hmc_lin_launch(fg_engine *e, int iter0, int n, int welford_on, double *dr
     int W = (D >= 32 || (D == 16 && !half)) ? D / 8 : D / 4;
     if (e->mw_override == D / 4 || (D < 64 && e->mw_override == D / 2) || (D >= 16 && e->mw_override == D / 8)) W = e->mw_override;
     const bool p2 = e->P.lin_p2 != 0;
+    using FgLinKernel = void (*)(FgProgramDev, FgChainCtx, FgHmcDev, int, int, int, int, double *, int, double *, double *);
+    struct FgLinVariant { int D, W; bool p2, half; FgLinKernel fn; unsigned long long raised; };
 #define FG_LIN_KERNELS_D(X, DD, HH) X(DD, DD / 8, false, HH) X(DD, DD / 8, true, HH) X(DD, DD / 4, false, HH) X(DD, DD / 4, true, HH) X(DD, DD / 2, false, HH) X(DD, DD / 2, true, HH)
 #define FG_LIN_KERNELS(X) FG_LIN_KERNELS_D(X, 32, false) FG_LIN_KERNELS_D(X, 32, true) FG_LIN_KERNELS_D(X, 16, false) FG_LIN_KERNELS_D(X, 16, true)      \
                           X(8, 2, false, false) X(8, 2, true, false) X(8, 4, false, false) X(8, 4, true, false) X(8, 2, false, true) X(8, 2, true, true)    \
                           X(8, 4, false, true) X(8, 4, true, true) X(64, 8, false, false) X(64, 8, true, false) X(64, 16, false, false) X(64, 16, true, false)
-    const void *fn = nullptr;
-    int variant = -1, idx = 0;
-#define FG_LIN_FN(DD, WW, PP, HH) if (D == DD && W == WW && p2 == PP && half == HH) { fn = (const void *)k_hmc_lin_steps<DD, WW, PP, HH>; variant = idx; } ++idx;
-    FG_LIN_KERNELS(FG_LIN_FN)
-#undef FG_LIN_FN
-    if (!fn) return FG_E_UNSUPPORTED;
-    static bool attr_set_dev[64][64];
-    bool &attr_set = attr_set_dev[e->device & 63][variant];
-    if (!attr_set && lds > 64 * 1024) {
-        const hipError_t he = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
-        attr_set = true;
-    }
-#define FG_LIN_GO(DD, WW, PP, HH) if (D == DD && W == WW && p2 == PP && half == HH) hipLaunchKernelGGL((k_hmc_lin_steps<DD, WW, PP, HH>), dim3(tiles), dim3(FG_WAVE * WW), lds, e->stream, e->P, e->X, e->H, \
-                                                                                                        iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
-    FG_LIN_KERNELS(FG_LIN_GO)
-#undef FG_LIN_GO
+#define FG_LIN_ENTRY(DD, WW, PP, HH) { DD, WW, PP, HH, k_hmc_lin_steps<DD, WW, PP, HH>, 0 },
+    static FgLinVariant variants[] = { FG_LIN_KERNELS(FG_LIN_ENTRY) };
+#undef FG_LIN_ENTRY
 #undef FG_LIN_KERNELS
 #undef FG_LIN_KERNELS_D
-    HIPCHK(hipGetLastError());
+    FgLinVariant *v = std::find_if(std::begin(variants), std::end(variants), [&](const FgLinVariant &q) { return q.D == D && q.W == W && q.p2 == p2 && q.half == half; });
+    if (v == std::end(variants)) return FG_E_UNSUPPORTED;
+    const int rc = fg_launch(e, v->fn, v->raised, dim3(tiles), dim3(FG_WAVE * W), lds, e->P, e->X, e->H, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
+    if (rc != FG_OK) return rc;
     e->last_hmc_kernel = std::string(half ? "k_hmc_lin_steps (half tiles) W=" : "k_hmc_lin_steps W=") + std::to_string(W);
     return FG_OK;
 }

@@ -18,8 +18,9 @@
 #include "fg_engine_internal.h"
 #include "fg_gradstream.h"
 #include "fg_cold.h"
+#include "fg_hmc_sep_plan.h"
 
-#define FG_SEP_WMAX 16
+static_assert(FG_SEP_WAVE == FG_WAVE, "fg_hmc_sep_plan.h sizes tiles for 64-lane waves");
 
 // FG_HMC_PROF (experiment builds, tools/prof_hmc_phases.py): cycles tile 0's waves spend in each part of a transition
 #ifdef FG_HMC_PROF
@@ -28,9 +29,6 @@ __device__ unsigned long long fg_hmc_prof[FG_SEP_WMAX][8];
 #else
 #define FG_PROF_T(i)
 #endif
-struct FgSegSep { int c[FG_SEP_WMAX + 1]; int sum4;       // sum4: the four in-order sums of a transition's end on four waves (tiles that are alone on their CU)
-                  int predraw;                           // resident form: waves 1.. draw their next transition's momenta while wave 0 decides
-                  int own[FG_SEP_WMAX][4], n_own[FG_SEP_WMAX]; };   // MODE 3 (dense, coordinates in registers): each wave's <= 4 coordinates (whole Box-Muller pairs), ascending
 #ifndef FG_SEP_STAGGER
 #define FG_SEP_STAGGER 2          /* x 4 096 cycles: the late start of a CU's second tile (k_hmc_sep_steps) */
 #endif
@@ -790,172 +788,30 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     }
 }
 
-// the resident form (NC > 0) of one record shape: 0 .. 3 observations, 4: U0 prior + one observation
-template <bool MASS, int NC, int NOBS, bool U0, bool FOLD>
-static int fg_sep_res_go(fg_engine *e, unsigned tiles, int W, size_t lds, const FgSegSep &seg, int iter0, int n, int welford_on, double *draws,
-                         int first_sample_t, double *pos_all, double *info) {
-    static bool attr_set_dev[64];
-    bool &attr_set = attr_set_dev[e->device & 63];
-    if (!attr_set) {
-        const hipError_t he = hipFuncSetAttribute((const void *)k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((k_hmc_sep_steps<MASS, 0, 0, NC, NOBS, U0, FOLD>), dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->H, seg, iter0, n,
-                       e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
-    return FG_OK;
-}
-template <bool MASS, int NC, bool FOLD>
-static int fg_sep_res_shape(int shape, fg_engine *e, unsigned tiles, int W, size_t lds, const FgSegSep &seg, int iter0, int n, int welford_on,
-                            double *draws, int first_sample_t, double *pos_all, double *info) {
-#define FG_SEP_RES(NO, UU) fg_sep_res_go<MASS, NC, NO, UU, FOLD>(e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info)
-    switch (shape) {
-        case 0: return FG_SEP_RES(0, false); case 1: return FG_SEP_RES(1, false); case 2: return FG_SEP_RES(2, false);
-        case 3: return FG_SEP_RES(3, false); default: return FG_SEP_RES(1, true);
-    }
-#undef FG_SEP_RES
-}
+using FgSepKernel = void (*)(FgProgramDev, FgChainCtx, FgHmcDev, FgSegSep, int, int, int, int, double *, int, double *, double *);
+struct FgSepVariant { FgSepKey key; FgSepKernel fn; unsigned long long raised; };       // raised: fg_launch
+#define FG_SEP_ENTRY(M, MODE, HALF, NC, NOBS, U0, FOLD) { { M, MODE, HALF, NC, NOBS, U0, FOLD }, k_hmc_sep_steps<M, MODE, HALF, NC, NOBS, U0, FOLD>, 0 },
+static FgSepVariant fg_sep_variants[] = { FG_SEP_VARIANTS(FG_SEP_ENTRY) };
+#undef FG_SEP_ENTRY
+
+static FgSwitch fg_env_switch(const char *name) { const char *v = std::getenv(name); return FgSwitch{ v != nullptr, v ? std::atoi(v) : 0 }; }
 
 // Launch for `n` transitions from iteration `iter0`; returns FG_E_UNSUPPORTED when the program / configuration is not an
-// independent-sites FD-sparse run (the caller then takes the gradient-stream kernel).
+// independent-sites FD-sparse run (the caller then takes the gradient-stream kernel).  Plan (fg_hmc_sep_plan.h), look up, launch, name.
 int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {
-    const bool dense = e->cfg.grad_mode == FG_GRAD_FD_DENSE, analytic = e->cfg.grad_mode == FG_GRAD_ANALYTIC;
-    if (e->gt) return FG_E_UNSUPPORTED;                       // tiles in global memory: the one-wave-per-tile kernels (fg_engine.hip)
-    if (!e->P.sep || (e->cfg.grad_mode != FG_GRAD_FD_SPARSE && !dense && !analytic) || e->d < 1 || e->sep_disabled) return FG_E_UNSUPPORTED;
-    const long long n_cu = std::max(1, e->n_simd / 4);
-    const long long tiles64 = (e->C + FG_WAVE - 1) / FG_WAVE;
-    // half tiles (32 chains per workgroup, the two coordinates of a Box-Muller pair in the two lane halves): when 64-chain tiles
-    // would leave half of the CUs without one, for programs whose coordinates all have one record shape with power-of-two sigmas
-    int half = 0;                                            // 1: half tiles, 2: quarter tiles (16 chains, four coordinates per wave)
-    const std::vector<FgSepCoord> &cdu = e->prog->sep_coord;
-    bool uniform = true;
-    for (const FgSepCoord &q : cdu) uniform = uniform && q.n == cdu[0].n && (q.n & 256);
-    if (!dense && !analytic && e->d >= 2) {
-        // half tiles up to two of them per CU (16 384 chains: 1.57e10 with 64-chain tiles, 1.67e10, 1.75e10 with the late start below);
-        // quarter tiles where even half tiles leave CUs without one (4 096 chains: 6.7e9 -> 9.2e9; at 8 192 the two are level)
-        if (uniform && tiles64 <= n_cu) half = (4 * tiles64 < 2 * n_cu && e->d >= 8) ? 2 : 1;
-        if (const char *hv = std::getenv("FG_HMC_SEP_HALF")) half = uniform ? std::max(0, std::min(2, std::atoi(hv))) : 0;
-        if (half == 2 && e->d < 4) half = 1;
-    }
-    const int tw = FG_WAVE >> half;
-    const unsigned tiles = (unsigned)((e->C + tw - 1) / tw);
-    // dense with the coordinates in registers (fg_dense_trajectory): every coordinate one Normal prior with or without ONE observation,
-    // all sigmas powers of two, no statement that reads no coordinate
-    bool dfast = dense && e->P.n_sep_free == 0 && e->d >= 1;
-    if (dfast) {
-        const std::vector<FgSepCoord> &cd = e->prog->sep_coord;
-        for (const FgSepCoord &q : cd) dfast = dfast && (q.n & 256) && (q.n & 7) == (cd[0].n & 7) && ((q.n & 7) == 1 || (q.n & 7) == 2);
-        if (const char *dv = std::getenv("FG_HMC_DENSE_FAST")) dfast = dfast && std::atoi(dv) != 0;
-    }
-    const size_t rows = (size_t)(e->P.n_sep_free > 0 ? e->n_slots : 0) + 2 * (size_t)e->d + (size_t)e->P.n_sstream + 3 +
-                        (dense ? 8 : 4 + 8);     // (dense: the kinetic terms end the tile -- the in-order sums read whole chunks of eight rows; sparse: 4 exchange rows + the chunk a sum may read past them)
-    // (the register-resident dense form has two sets of n_s term rows, the second of which also takes the 2 d kinetic terms: with n_s = d
-    // or 2 d that is the 2 d + n_s rows of the row-resident form)
-    const size_t lds = rows * tw * sizeof(double);
-    if (lds > 160 * 1024) return FG_E_UNSUPPORTED;
-    // waves per tile: aim at 4 waves per SIMD (16 per CU); the LDS tile caps the tiles resident on a CU, few tiles (small
-    // chain counts) leave CUs with one tile -- the waves then come from sharing the tile.  Every wave owns >= 2 coordinates
-    // (a half tile: >= 1 pair, both coordinates at once).
-    const int unit = half == 2 ? 4 : 2;                      // coordinates a wave takes at a time
-    const int pairs = (e->d + unit - 1) / unit;
-    int W = e->mw_override > 0 ? e->mw_override : 1;
-    if (e->mw_override <= 0) {
-        const long long resident = std::max(1LL, std::min<long long>((160 * 1024) / (long long)lds, ((long long)tiles + n_cu - 1) / n_cu));
-        while (W < FG_SEP_WMAX && resident * W < 16 && (half ? pairs >= 2 * W : e->d >= 4 * W)) W *= 2;     // (a half tile with a pair per wave beats two pairs per wave sharing their random numbers: 1.31e10 against 1.25e10 at 8 192 chains)
-    }
-    while (W > 1 && unit * (W - 1) >= e->d + 1) W /= 2;          // no empty waves
-    FgSegSep seg;
-    std::memset(&seg, 0, sizeof(seg));
-    if (dfast) {
-        // Whole Box-Muller pairs, at most two per wave.  A coordinate whose own row is r adds 2 (rows - r) terms behind it: the pairs go
-        // out by row, to the waves and back (0 .. W-1, W-1 .. 0), so every wave adds about the same number; within a wave by row.
-        const int np = (e->d + 1) / 2, W_plain = W;
-        W = std::min(std::max(W, (np + 1) / 2), np);
-        if (W > FG_SEP_WMAX) dfast = false;
-        else {
-            const std::vector<FgSepCoord> &cd = e->prog->sep_coord;
-            auto row_of = [&](int i, int k) { return (int)e->prog->sep[(size_t)cd[i].off + k].trow; };
-            std::vector<int> pr(np);
-            for (int q = 0; q < np; ++q) pr[q] = q;
-            std::stable_sort(pr.begin(), pr.end(), [&](int a, int b) { return row_of(2 * a, 0) < row_of(2 * b, 0); });
-            for (int q = 0; q < np; ++q) {
-                const int w = q < W ? q : 2 * W - 1 - q;
-                for (int i = 2 * pr[q]; i < std::min(e->d, 2 * pr[q] + 2); ++i) seg.own[w][seg.n_own[w]++] = i;
-            }
-            const bool obs = (cd[0].n & 7) == 2;
-            for (int w = 0; w < W && dfast; ++w) {
-                std::sort(seg.own[w], seg.own[w] + seg.n_own[w], [&](int a, int b) { return row_of(a, 0) < row_of(b, 0); });
-                for (int j = 0; j + 1 < seg.n_own[w]; ++j)
-                    if (row_of(seg.own[w][j], 0) >= row_of(seg.own[w][j + 1], 0) || (obs && row_of(seg.own[w][j], 1) >= row_of(seg.own[w][j + 1], 1))) dfast = false;
-                if (seg.n_own[w] < 1) dfast = false;
-            }
-        }
-        if (!dfast) { std::memset(&seg, 0, sizeof(seg)); W = W_plain; }       // (rows out of order within a wave, or more than 32 pairs: the row-resident form)
-    }
-    seg.sum4 = (!dense && half != 0) ? 1 : 0;                    // a tile alone on its CU: the transition's four end sums on four waves
-    if (const char *sv = std::getenv("FG_HMC_SUM4")) seg.sum4 = std::atoi(sv) != 0 ? 1 : 0;
-    for (int w = 0; w <= FG_SEP_WMAX; ++w) seg.c[w] = e->d;
-    for (int w = 0; w < W; ++w) seg.c[w] = std::min(e->d, unit * (int)((long long)pairs * w / W));
-    if (W == 8 && !half && !(std::getenv("FG_HMC_PRIO") && std::atoi(std::getenv("FG_HMC_PRIO")) == 0)) seg.c[FG_SEP_WMAX] = -1;   // priority turns: two waves of a tile per SIMD
-    if (half == 1 && (long long)tiles > n_cu && (long long)tiles <= 2 * n_cu) seg.c[FG_SEP_WMAX] = -3;                                  // two half tiles on a CU: the odd ones start late (+5 %; 64-chain tiles lose 5 % to it)
-    if (const char *sg = std::getenv("FG_HMC_STAGGER")) { const int v = std::atoi(sg); seg.c[FG_SEP_WMAX] = (v == 1 || v == 2) ? -1 - v : (seg.c[FG_SEP_WMAX] <= -2 ? e->d : seg.c[FG_SEP_WMAX]); }   // experiments
-    // the resident form: 64-chain sparse tiles of one record shape with power-of-two sigmas, <= 4 coordinates per wave
-    int res_nc = 0;
-    if (!dense && !analytic && !half && uniform && e->P.n_sep_free == 0 && !e->sep_res_disabled && (cdu[0].n & 7) >= 1 && (cdu[0].n & 7) <= 4) {
-        int most = 0;
-        for (int w = 0; w < W; ++w) most = std::max(most, (w + 1 < W ? seg.c[w + 1] : e->d) - seg.c[w]);
-        res_nc = most <= 2 ? 2 : (most <= 4 ? 4 : 0);
-    }
-    // the folded trajectory loop (fg_sep_trajectory's FOLD): sparse finite differences, the host's range of 1 / sigma
-    const bool fold = !dense && !analytic && e->prog->sep_fold && !e->sep_fold_disabled;
-    seg.predraw = 1;
-    if (const char *pv = std::getenv("FG_HMC_PREDRAW")) seg.predraw = std::atoi(pv) != 0 ? 1 : 0;   // experiments
-    if (res_nc) {
-        const int nobs = (cdu[0].n & 7) - 1, shape = ((cdu[0].n & 512) && nobs == 1) ? 4 : nobs;
-#define FG_SEP_RES_NC(NC_, FO) (e->H.use_mass ? fg_sep_res_shape<true, NC_, FO>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info) \
-                                              : fg_sep_res_shape<false, NC_, FO>(shape, e, tiles, W, lds, seg, iter0, n, welford_on, draws, first_sample_t, pos_all, info))
-        const int rc = res_nc == 2 ? (fold ? FG_SEP_RES_NC(2, true) : FG_SEP_RES_NC(2, false)) : (fold ? FG_SEP_RES_NC(4, true) : FG_SEP_RES_NC(4, false));
-#undef FG_SEP_RES_NC
-        if (rc != FG_OK) return rc;
-        HIPCHK(hipGetLastError());
-        e->last_hmc_kernel = std::string(fold ? "k_hmc_sep_steps (resident) (folded) W=" : "k_hmc_sep_steps (resident) W=") + std::to_string(W);
-        return FG_OK;
-    }
-    static bool attr_set_dev[64][18];
-    const int mass = e->H.use_mass ? 1 : 0, mode = dense ? 1 : (analytic ? 2 : 0);
-    const int variant = dfast ? 10 + mass : (mode == 0 && fold ? 12 + 2 * half + mass : (half ? 4 + 2 * half + mass : 2 * mode + mass));
-    const void *fns[18] = { (const void *)k_hmc_sep_steps<false, 0>, (const void *)k_hmc_sep_steps<true, 0>, (const void *)k_hmc_sep_steps<false, 1>,
-                           (const void *)k_hmc_sep_steps<true, 1>, (const void *)k_hmc_sep_steps<false, 2>, (const void *)k_hmc_sep_steps<true, 2>,
-                           (const void *)k_hmc_sep_steps<false, 0, 1>, (const void *)k_hmc_sep_steps<true, 0, 1>,
-                           (const void *)k_hmc_sep_steps<false, 0, 2>, (const void *)k_hmc_sep_steps<true, 0, 2>,
-                           (const void *)k_hmc_sep_steps<false, 3>, (const void *)k_hmc_sep_steps<true, 3>,
-                           (const void *)k_hmc_sep_steps<false, 0, 0, 0, 0, false, true>, (const void *)k_hmc_sep_steps<true, 0, 0, 0, 0, false, true>,
-                           (const void *)k_hmc_sep_steps<false, 0, 1, 0, 0, false, true>, (const void *)k_hmc_sep_steps<true, 0, 1, 0, 0, false, true>,
-                           (const void *)k_hmc_sep_steps<false, 0, 2, 0, 0, false, true>, (const void *)k_hmc_sep_steps<true, 0, 2, 0, 0, false, true> };
-    bool &attr_set = attr_set_dev[e->device & 63][variant];
-    if (!attr_set) {
-        const hipError_t he = hipFuncSetAttribute(fns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
-        attr_set = true;
-    }
-#define FG_SEP_LAUNCH(...) hipLaunchKernelGGL((k_hmc_sep_steps<__VA_ARGS__>), dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->H, seg, iter0, n, \
-                                               e->n_warmup, welford_on, draws, first_sample_t, pos_all, info)
-    switch (variant) {
-        case 0: FG_SEP_LAUNCH(false, 0); break; case 1: FG_SEP_LAUNCH(true, 0); break; case 2: FG_SEP_LAUNCH(false, 1); break;
-        case 3: FG_SEP_LAUNCH(true, 1); break;  case 4: FG_SEP_LAUNCH(false, 2); break; case 5: FG_SEP_LAUNCH(true, 2); break;
-        case 6: FG_SEP_LAUNCH(false, 0, 1); break; case 7: FG_SEP_LAUNCH(true, 0, 1); break;
-        case 8: FG_SEP_LAUNCH(false, 0, 2); break; case 9: FG_SEP_LAUNCH(true, 0, 2); break;
-        case 10: FG_SEP_LAUNCH(false, 3); break; case 11: FG_SEP_LAUNCH(true, 3); break;
-        case 12: FG_SEP_LAUNCH(false, 0, 0, 0, 0, false, true); break; case 13: FG_SEP_LAUNCH(true, 0, 0, 0, 0, false, true); break;
-        case 14: FG_SEP_LAUNCH(false, 0, 1, 0, 0, false, true); break; case 15: FG_SEP_LAUNCH(true, 0, 1, 0, 0, false, true); break;
-        case 16: FG_SEP_LAUNCH(false, 0, 2, 0, 0, false, true); break; default: FG_SEP_LAUNCH(true, 0, 2, 0, 0, false, true); break;
-    }
-#undef FG_SEP_LAUNCH
-    HIPCHK(hipGetLastError());
-    e->last_hmc_kernel = std::string(dfast ? "k_hmc_sep_steps (dense, coordinates in registers) W=" : dense ? "k_hmc_sep_steps (dense) W=" : (analytic ? "k_hmc_sep_steps (analytic) W=" : (half == 2 ? "k_hmc_sep_steps (quarter tiles) W=" : (half ? "k_hmc_sep_steps (half tiles) W=" : "k_hmc_sep_steps W="))));
-    if (variant >= 12) e->last_hmc_kernel.insert(e->last_hmc_kernel.size() - 2, "(folded) ");
-    e->last_hmc_kernel += std::to_string(W);
-    return FG_OK;
+    if (e->gt || !e->P.sep || e->sep_disabled) return FG_E_UNSUPPORTED;   // (fg_hmc_sep_plan says so too: every HMC launch asks here first, most read no switch)
+    const FgSepPlanIn in = { e->C, e->d, e->n_simd, e->n_slots, e->P.n_sep_free, e->P.n_sstream, e->cfg.grad_mode, e->H.use_mass != 0, e->mw_override,
+                             e->gt, e->sep_disabled, e->sep_res_disabled, e->sep_fold_disabled, e->prog->sep_fold, &e->prog->sep_coord, &e->prog->sep,
+                             fg_env_switch("FG_HMC_SEP_HALF"), fg_env_switch("FG_HMC_DENSE_FAST"), fg_env_switch("FG_HMC_SUM4"), fg_env_switch("FG_HMC_PRIO"),
+                             fg_env_switch("FG_HMC_STAGGER"), fg_env_switch("FG_HMC_PREDRAW") };
+    FgSepPlan pl;
+    int rc = fg_hmc_sep_plan(in, &pl);
+    if (rc != FG_OK) return rc;
+    FgSepVariant *v = std::find_if(std::begin(fg_sep_variants), std::end(fg_sep_variants), [&](const FgSepVariant &q) { return q.key == pl.key; });
+    if (v == std::end(fg_sep_variants)) return FG_E_UNSUPPORTED;
+    rc = fg_launch(e, v->fn, v->raised, dim3(pl.tiles), dim3(FG_WAVE * pl.W), pl.lds, e->P, e->X, e->H, pl.seg, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
+    if (rc == FG_OK) e->last_hmc_kernel = pl.name;
+    return rc;
 }
 
 #ifdef FG_HMC_PROF

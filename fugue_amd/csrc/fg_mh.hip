@@ -314,28 +314,16 @@ int fg_mh_mw_launch(fg_engine *e, int iter0, int n_steps, long long *draws, int 
         e->last_mh_kernel = std::string(sh.pipe ? "k_mh_mw2_jit_steps W=" : "k_mh_mw_jit_steps W=") + std::to_string(W) + " (statements compiled at run time)";
         return FG_OK;
     }
-    static bool attr_set_dev[64][16];
-    const int variant = 2 * (rk == 0 ? 0 : (rk == 2 ? 1 : 2)) + split_sums + (sh.pipe ? 6 : 0);
-    const void *fns[12] = { (const void *)k_mh_mw_steps<0, false>, (const void *)k_mh_mw_steps<0, true>, (const void *)k_mh_mw_steps<2, false>,
-                            (const void *)k_mh_mw_steps<2, true>, (const void *)k_mh_mw_steps<3, false>, (const void *)k_mh_mw_steps<3, true>,
-                            (const void *)k_mh_mw2_steps<0, false>, (const void *)k_mh_mw2_steps<0, true>, (const void *)k_mh_mw2_steps<2, false>,
-                            (const void *)k_mh_mw2_steps<2, true>, (const void *)k_mh_mw2_steps<3, false>, (const void *)k_mh_mw2_steps<3, true> };
-    bool &attr_set = attr_set_dev[e->device & 63][variant];
-    if (!attr_set) {
-        const hipError_t he = hipFuncSetAttribute(fns[variant], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
-        attr_set = true;
-    }
-#define FG_MH_LAUNCH(K, R, SP) hipLaunchKernelGGL((K<R, SP>), dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->M, e->d_mh_srt, seg, iter0, n_steps, \
-                                                  e->mh_warmup, draws, first_sample_t, exp_mask, pool_n)
-    switch (variant) {
-        case 0: FG_MH_LAUNCH(k_mh_mw_steps, 0, false); break; case 1: FG_MH_LAUNCH(k_mh_mw_steps, 0, true); break; case 2: FG_MH_LAUNCH(k_mh_mw_steps, 2, false); break;
-        case 3: FG_MH_LAUNCH(k_mh_mw_steps, 2, true); break;  case 4: FG_MH_LAUNCH(k_mh_mw_steps, 3, false); break; case 5: FG_MH_LAUNCH(k_mh_mw_steps, 3, true); break;
-        case 6: FG_MH_LAUNCH(k_mh_mw2_steps, 0, false); break; case 7: FG_MH_LAUNCH(k_mh_mw2_steps, 0, true); break; case 8: FG_MH_LAUNCH(k_mh_mw2_steps, 2, false); break;
-        case 9: FG_MH_LAUNCH(k_mh_mw2_steps, 2, true); break;  case 10: FG_MH_LAUNCH(k_mh_mw2_steps, 3, false); break; default: FG_MH_LAUNCH(k_mh_mw2_steps, 3, true); break;
-    }
-#undef FG_MH_LAUNCH
-    HIPCHK(hipGetLastError());
+    using FgMhMwKernel = void (*)(FgProgramDev, FgChainCtx, FgMhDev, const FgGradRec *, FgMhSeg, int, int, int, long long *, int, int, int);
+    struct FgMhMwVariant { bool pipe; int rk; bool split; FgMhMwKernel fn; unsigned long long raised; };
+#define FG_MH_ENTRIES(PIPE, K) { PIPE, 0, false, K<0, false> }, { PIPE, 0, true, K<0, true> }, { PIPE, 2, false, K<2, false> }, { PIPE, 2, true, K<2, true> }, \
+                               { PIPE, 3, false, K<3, false> }, { PIPE, 3, true, K<3, true> }
+    static FgMhMwVariant variants[] = { FG_MH_ENTRIES(false, k_mh_mw_steps), FG_MH_ENTRIES(true, k_mh_mw2_steps) };
+#undef FG_MH_ENTRIES
+    FgMhMwVariant *v = std::find_if(std::begin(variants), std::end(variants), [&](const FgMhMwVariant &q) { return q.pipe == (sh.pipe != 0) && q.rk == rk && q.split == (split_sums != 0); });
+    if (v == std::end(variants)) return FG_E_UNSUPPORTED;
+    const int rc = fg_launch(e, v->fn, v->raised, dim3(tiles), dim3(FG_WAVE * W), lds, e->P, e->X, e->M, e->d_mh_srt, seg, iter0, n_steps, e->mh_warmup, draws, first_sample_t, exp_mask, pool_n);
+    if (rc != FG_OK) return rc;
 #ifdef FG_MH_PROF
     fg_mh_prof_set_module(nullptr);
 #endif
