@@ -13,3 +13,5 @@ from .inference import (ChainBatch, HMCConfig, ResamplingMethod, SMCConfig, SMCR
 from .diagnostics import (ParameterSummary, classic_r_hat_f64, effective_sample_size, effective_sample_size_multichain,  # noqa: F401
                           geweke_diagnostic, r_hat_f64, summarize_f64_parameter)
 from .validation import effective_sample_size_mcmc  # noqa: F401
+from .vi import (GuideError, MeanFieldGuide, ParamCoord, Support, VIConfig, VIResult, VariationalParam, elbo_gradient_fd,  # noqa: F401
+                 elbo_with_guide, estimate_elbo, optimize_meanfield_vi, optimize_meanfield_vi_with_config)

@@ -803,6 +803,7 @@ void fg_engine_free(fg_engine *e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     for (void *q : e->hmc_allocs) hipFree(q);
     for (void *q : e->mh_allocs) hipFree(q);
+    for (void *q : e->vi_allocs) hipFree(q);
     if (e->d_rec) hipFree(e->d_rec);
     if (e->smc_arena) hipFree(e->smc_arena);
     if (e->smc_host) (void)hipHostFree(e->smc_host);

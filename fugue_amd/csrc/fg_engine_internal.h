@@ -94,6 +94,10 @@ struct fg_engine {
     int jit_mhmw_state = 0; hipModule_t jit_mhmw_mod = nullptr; hipFunction_t jit_mhmw_fn = nullptr; double *d_jit_mhmw_tab = nullptr;   // ... the multi-wave stream MH kernel with phase B generated (fg_mh.hip)
     int jit_mh_state = 0, jit_mh_W = 1, jit_mh_direct = 0; size_t jit_mh_lds = 0; hipModule_t jit_mh_mod = nullptr; hipFunction_t jit_mh_fn[2] = {nullptr, nullptr};   // ... and its MH kernel (128- and 256-VGPR builds)
     std::string last_mh_kernel;  // kernel the last fg_mh_step launch ran (fg_mh_last_kernel)
+    // mean-field VI (fg_vi.hip): factor table, stream ids, per-sample terms, per-wave sums, ELBOs, global tiles -- grown on demand
+    std::vector<void *> vi_allocs;
+    void *d_vi_tab = nullptr; uint32_t *d_vi_sid = nullptr; double *d_vi_terms = nullptr, *d_vi_partial = nullptr, *d_vi_elbo = nullptr, *d_vi_gtile = nullptr;
+    size_t vi_cap_tab = 0, vi_cap_eval = 0, vi_cap_terms = 0;
     int mw_override = 0;       // FG_HMC_WAVES env: force waves per tile of the multi-wave HMC kernel (tests)
 };
 

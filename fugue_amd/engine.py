@@ -48,6 +48,19 @@ class fg_smc_result(C.Structure):
     _fields_ = [("log_evidence", C.c_double), ("n_steps", C.c_int32), ("n_model_runs", C.c_int64)]
 
 
+class fg_vi_factor(C.Structure):
+    _fields_ = [("family", C.c_int32), ("site", C.c_int32), ("a", C.c_double), ("b", C.c_double)]
+
+
+class fg_vi_config(C.Structure):
+    _fields_ = [("n_iterations", C.c_int32), ("convergence_window", C.c_int32), ("base_learning_rate", C.c_double), ("fd_eps", C.c_double),
+                ("convergence_tol", C.c_double), ("step_decay_exponent", C.c_double)]
+
+
+class fg_vi_result(C.Structure):
+    _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32)]
+
+
 RESAMPLE_MULTINOMIAL, RESAMPLE_SYSTEMATIC, RESAMPLE_STRATIFIED = range(3)
 PROP_AUTO, PROP_GAUSSIAN, PROP_LOGSPACE, PROP_REFLECT, PROP_PRIOR_RESAMPLE = range(5)
 
@@ -77,6 +90,7 @@ ABI_SYMBOLS = [
     "fg_diag_combine_reduced", "fg_diag_set_exchange", "fg_diag_exchange_bytes", "fg_hmc_last_kernel", "fg_mh_last_kernel", "fg_diag_quantiles",
     "fg_comm_unique_id", "fg_comm_init", "fg_comm_destroy", "fg_device_alloc", "fg_device_free", "fg_device_download", "fg_device_upload",
     "fg_dsl_compile", "fg_dsl_warning_count", "fg_dsl_warning",
+    "fg_vi_config_default", "fg_vi_elbo_batch", "fg_vi_optimize", "fg_vi_estimate_elbo",
 ]
 
 _lib = None
@@ -204,6 +218,10 @@ def lib():
     L.fg_device_free.argtypes = [vp, vp]
     L.fg_device_download.argtypes = [vp, vp, vp, C.c_size_t]
     L.fg_device_upload.argtypes = [vp, vp, vp, C.c_size_t]
+    L.fg_vi_config_default.argtypes = [C.POINTER(fg_vi_config)]
+    L.fg_vi_elbo_batch.argtypes = [vp, C.POINTER(fg_vi_factor), C.c_int, C.c_int, C.POINTER(C.c_uint32), dp, dp]
+    L.fg_vi_optimize.argtypes = [vp, C.POINTER(fg_vi_factor), C.c_int, C.POINTER(fg_vi_config), dp, C.POINTER(fg_vi_result)]
+    L.fg_vi_estimate_elbo.argtypes = [vp, C.c_uint32, dp]
     L.fg_dsl_compile.restype = vp
     L.fg_dsl_compile.argtypes = [C.c_char_p, C.c_char_p]
     L.fg_dsl_warning_count.argtypes = [vp]
@@ -613,6 +631,42 @@ class Engine:
         a = np.ascontiguousarray(log_w, dtype=np.float64)
         assert a.shape == (self.C,)
         _check(lib().fg_smc_set_log_weights(self.h, _dp(a)))
+
+    # ---- mean-field VI (fg_vi.hip) ------------------------------------------------------------
+    @staticmethod
+    def _vi_factors(rows):
+        """rows: [n_eval][n_factors] of (family, site, a, b) -> a flat fg_vi_factor array."""
+        flat = [q for row in rows for q in row]
+        arr = (fg_vi_factor * max(1, len(flat)))()
+        for i, (fam, site, a, b) in enumerate(flat):
+            arr[i] = fg_vi_factor(int(fam), int(site), float(a), float(b))
+        return arr
+
+    def vi_elbo_batch(self, rows, stream_ids, want_terms: bool = False):
+        """`elbo_with_guide` of every guide in `rows` ([n_eval][n_factors] of (family, site, a, b), address-sorted) over this
+        engine's chains as samples: ELBOs [n_eval] (and every sample's term [n_eval][C])."""
+        n_eval, n_factors = len(rows), (len(rows[0]) if rows else 0)
+        assert all(len(r) == n_factors for r in rows) and len(stream_ids) == n_eval
+        sid = np.ascontiguousarray(stream_ids, dtype=np.uint32)
+        elbo = np.zeros(max(1, n_eval))
+        terms = np.zeros((max(1, n_eval), self.C)) if want_terms else None
+        _check(lib().fg_vi_elbo_batch(self.h, self._vi_factors(rows), n_eval, n_factors, sid.ctypes.data_as(C.POINTER(C.c_uint32)), _dp(elbo),
+                                      _dp(terms) if want_terms else None))
+        return (elbo[:n_eval], terms[:n_eval]) if want_terms else elbo[:n_eval]
+
+    def vi_optimize(self, factors, cfg: fg_vi_config):
+        """`optimize_meanfield_vi_with_config`: -> (optimized factors [(family, site, a, b)], elbo_history, converged, iterations)."""
+        arr = self._vi_factors([factors])
+        hist = np.zeros(max(1, cfg.n_iterations))
+        res = fg_vi_result()
+        _check(lib().fg_vi_optimize(self.h, arr, len(factors), C.byref(cfg), _dp(hist), C.byref(res)))
+        out = [(arr[i].family, arr[i].site, arr[i].a, arr[i].b) for i in range(len(factors))]
+        return out, hist[:res.iterations], bool(res.converged), int(res.iterations)
+
+    def vi_estimate_elbo(self, iteration: int = 0) -> float:
+        out = C.c_double()
+        _check(lib().fg_vi_estimate_elbo(self.h, int(iteration), C.byref(out)))
+        return out.value
 
     # ---- diagnostics kernels -----------------------------------------------------------------
     def diag_chain_moments(self, d_draws: int, n: int, d: int, d_moments: int):

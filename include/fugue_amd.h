@@ -49,7 +49,7 @@ enum {
     FG_E_LIMIT = -7           /* model exceeds an engine limit (LDS budget, K > 64, ...) */
 };
 enum {
-    FG_ERR_INVALID_PROBABILITY = 102, FG_ERR_INVALID_COUNT = 106,
+    FG_ERR_INVALID_MEAN = 100, FG_ERR_INVALID_VARIANCE = 101, FG_ERR_INVALID_PROBABILITY = 102, FG_ERR_INVALID_SHAPE = 104, FG_ERR_INVALID_COUNT = 106,
     FG_ERR_ADDRESS_CONFLICT = 301, FG_ERR_UNEXPECTED_STRUCTURE = 302,
     FG_ERR_ADDRESS_NOT_FOUND = 500, FG_ERR_TYPE_MISMATCH = 600
 };
@@ -329,6 +329,43 @@ int fg_device_resample_indices(int device_ordinal, int method, const double *h_w
 int fg_device_smc_temper(int device_ordinal, double beta, const double *h_loglik, int64_t n, double target_ess,
                          int flags, double *out_beta, double *out_log_norm, double *h_log_w, double *h_weights,
                          int *out_need_sum);
+
+/* ------------------------------------------------------------------ mean-field variational inference
+ * Replaces src/inference/vi.rs:104-923 (MeanFieldGuide, elbo_with_guide, elbo_gradient_fd, optimize_meanfield_vi_with_config,
+ * estimate_elbo).  The engine's n_chains is the number of Monte Carlo samples per ELBO evaluation (VIConfig::n_samples_per_iter);
+ * sample n of an evaluation draws from the counter-based stream (seed, chain_offset + n, stream id of the evaluation), so two
+ * evaluations with one stream id see common random numbers -- the whole mechanism of elbo_gradient_fd (vi.rs:687-725).
+ * A guide is a row of factors in address-sorted order (MeanFieldGuide::sample_trace, vi.rs:609-630). */
+typedef struct fg_vi_factor {       /* VariationalParam, vi.rs:210-232 */
+    int32_t family;                 /* 0 Normal {mu, log_sigma}, 1 LogNormal {mu, log_sigma}, 2 Beta {log_alpha, log_beta} */
+    int32_t site;                   /* sorted site index, or -1: the address is no model site (drawn, adds nothing to log q: vi.rs:659-664) */
+    double  a, b;                   /* location coordinate, scale coordinate (ParamCoord, vi.rs:167-172) */
+} fg_vi_factor;
+typedef struct fg_vi_config {       /* VIConfig, vi.rs:729-759 (same defaults; n_samples_per_iter = the engine's n_chains) */
+    int32_t n_iterations;           /* 1000 */
+    int32_t convergence_window;     /* 20 */
+    double  base_learning_rate, fd_eps, convergence_tol, step_decay_exponent;   /* 0.1, 0.01, 1e-4, 0.6 */
+} fg_vi_config;
+typedef struct fg_vi_result { int32_t converged; int32_t iterations; } fg_vi_result;   /* VIResult minus guide and history, vi.rs:763-772 */
+void fg_vi_config_default(fg_vi_config *cfg);
+/* n_eval ELBO estimates (elbo_with_guide, vi.rs:639-669) in one launch: h_factors [n_eval][n_factors], h_stream_ids [n_eval],
+ * h_elbo [n_eval]; h_terms (optional) [n_eval][C] = every sample's log p(x, z) - log q(z); with h_terms the draws of evaluation 0
+ * are left in the engine's values (fg_engine_get_values: the guide traces, for inspection), otherwise the values are untouched.  The ELBO is the sum of the terms in the
+ * engine's fixed order (fg_vi.hip) over C.  Errors: FG_ERR_ADDRESS_NOT_FOUND when an f64 site has no factor (the panic of
+ * ScoreGivenTrace) or the program has a discrete sample site (GuideError::UnsupportedDiscreteLatent, vi.rs:136-144); a non-finite
+ * factor parameter is InvalidParameters with FG_ERR_INVALID_MEAN / _VARIANCE / _SHAPE; a family outside 0..2, a site out of range
+ * or factors out of address order are FG_E_BAD_ARG. */
+int fg_vi_elbo_batch(fg_engine *e, const fg_vi_factor *h_factors, int n_eval, int n_factors, const uint32_t *h_stream_ids,
+                     double *h_elbo, double *h_terms);
+/* optimize_meanfield_vi_with_config (vi.rs:784-864): h_factors [n_factors] is the initial guide and receives the optimized one,
+ * h_elbo_history [n_iterations] the monitor of every iteration run.  Iteration t draws the monitor from stream id t (2 n_factors + 1)
+ * and both signs of coordinate j = 2 factor + (0 location, 1 scale) from t (2 n_factors + 1) + 1 + j; FG_E_LIMIT when
+ * n_iterations (2 n_factors + 1) reaches 2^32. */
+int fg_vi_optimize(fg_engine *e, fg_vi_factor *h_factors, int n_factors, const fg_vi_config *cfg, double *h_elbo_history,
+                   fg_vi_result *h_result);
+/* estimate_elbo (vi.rs:905-923): the prior as the guide -- the mean over the engine's chains of log_likelihood + log_factors of a
+ * prior run (the draws of fg_prior_init at `iteration`), summed in the same fixed order. */
+int fg_vi_estimate_elbo(fg_engine *e, uint32_t iteration, double *h_elbo);
 
 /* ------------------------------------------------------------------ cross-chain diagnostics
  * Per-chain statistics behind r_hat_f64 / effective_sample_size_multichain

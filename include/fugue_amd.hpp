@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -352,6 +353,51 @@ SMCResult adaptive_smc(uint64_t seed, size_t num_particles, F model_fn, SMCConfi
         const bool is_f64 = fg_program_site_vtype(prog->raw(), (int)j) == FG_F64;
         for (size_t i = 0; i < num_particles; ++i) { double v; if (is_f64) std::memcpy(&v, &raw[j * num_particles + i], 8); else v = (double)raw[j * num_particles + i];
             out.values[j * num_particles + i] = v; } }
+    return out;
+}
+
+// ---- mean-field VI (vi.rs:104-923): thin wrappers of fg_vi_* --------------------------------------------------------
+struct VariationalParam { int family; double a, b;                      // vi.rs:210-232: a = location coordinate, b = scale coordinate
+    static VariationalParam Normal(double mu, double log_sigma) { return {0, mu, log_sigma}; }
+    static VariationalParam LogNormal(double mu, double log_sigma) { return {1, mu, log_sigma}; }
+    static VariationalParam Beta(double log_alpha, double log_beta) { return {2, log_alpha, log_beta}; } };
+using MeanFieldGuide = std::map<Address, VariationalParam>;             // byte-wise key order = Address order (address.rs:150-157)
+struct VIConfig { size_t n_iterations = 1000, n_samples_per_iter = 16; double base_learning_rate = 0.1, fd_eps = 0.01, convergence_tol = 1e-4;
+    size_t convergence_window = 20; double step_decay_exponent = 0.6; };  // vi.rs:729-759
+struct VIResult { MeanFieldGuide guide; std::vector<double> elbo_history; bool converged = false; size_t iterations = 0; };
+namespace detail {
+inline std::vector<fg_vi_factor> vi_row(const Program &p, const MeanFieldGuide &g) {
+    std::vector<fg_vi_factor> row;
+    for (auto &kv : g) { int site = -1; for (int j = 0; j < p.n_sites(); ++j) if (p.site_name(j) == kv.first) site = j;
+        row.push_back({(int32_t)kv.second.family, (int32_t)site, kv.second.a, kv.second.b}); }
+    return row;
+}
+}  // namespace detail
+/// elbo_with_guide (vi.rs:639-669) over `num_samples` samples.
+template <class A, class F> double elbo_with_guide(uint64_t seed, F model_fn, const MeanFieldGuide &guide, size_t num_samples, int device = 0) {
+    auto prog = flatten<A>(model_fn);
+    Engine eng(*prog, (int64_t)num_samples, seed, device);
+    auto row = detail::vi_row(*prog, guide); const uint32_t sid = 0; double out = 0.0;
+    check(fg_vi_elbo_batch(eng.raw(), row.data(), 1, (int)row.size(), &sid, &out, nullptr), "elbo_with_guide");
+    return out;
+}
+/// optimize_meanfield_vi_with_config (vi.rs:784-864); config.n_samples_per_iter samples per ELBO estimate.
+template <class A, class F> VIResult optimize_meanfield_vi_with_config(uint64_t seed, F model_fn, const MeanFieldGuide &initial_guide, VIConfig config, int device = 0) {
+    auto prog = flatten<A>(model_fn);
+    Engine eng(*prog, (int64_t)config.n_samples_per_iter, seed, device);
+    auto row = detail::vi_row(*prog, initial_guide);
+    fg_vi_config c{(int32_t)config.n_iterations, (int32_t)config.convergence_window, config.base_learning_rate, config.fd_eps, config.convergence_tol, config.step_decay_exponent};
+    fg_vi_result r{}; VIResult out; out.elbo_history.resize(std::max<size_t>(1, config.n_iterations));
+    check(fg_vi_optimize(eng.raw(), row.data(), (int)row.size(), &c, out.elbo_history.data(), &r), "optimize_meanfield_vi");
+    out.elbo_history.resize((size_t)r.iterations); out.converged = r.converged != 0; out.iterations = (size_t)r.iterations;
+    size_t k = 0; for (auto &kv : initial_guide) { out.guide[kv.first] = {row[k].family, row[k].a, row[k].b}; ++k; }
+    return out;
+}
+/// estimate_elbo (vi.rs:905-923): the prior as the guide.
+template <class A, class F> double estimate_elbo(uint64_t seed, F model_fn, size_t num_samples, int device = 0) {
+    auto prog = flatten<A>(model_fn);
+    Engine eng(*prog, (int64_t)num_samples, seed, device);
+    double out = 0.0; check(fg_vi_estimate_elbo(eng.raw(), 0, &out), "estimate_elbo");
     return out;
 }
 

@@ -48,6 +48,12 @@ pub struct fg_mh_stats { pub accept_rate: f64, pub n_steps: i64 }
 pub struct fg_smc_config { pub resampling_method: i32, pub ess_threshold: f64, pub rejuvenation_steps: i32, pub sequential_adaptation: i32 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct fg_smc_result { pub log_evidence: f64, pub n_steps: i32, pub n_model_runs: i64 }
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct fg_vi_factor { pub family: i32, pub site: i32, pub a: f64, pub b: f64 }
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct fg_vi_config { pub n_iterations: i32, pub convergence_window: i32, pub base_learning_rate: f64, pub fd_eps: f64, pub convergence_tol: f64, pub step_decay_exponent: f64 }
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct fg_vi_result { pub converged: i32, pub iterations: i32 }
 
 pub type fg_acov_fn = Option<unsafe extern "C" fn(user: *mut c_void, lag0: c_int, n_lags: c_int, h_sums: *mut f64) -> c_int>;
 pub type fg_reduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, stage: c_int, h_in: *const f64, h_out: *mut f64) -> c_int>;
@@ -133,6 +139,13 @@ extern "C" {
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
     pub fn fg_comm_destroy(comm: *mut c_void) -> c_int;
+    // ---- mean-field VI (vi.rs:104-923)
+    pub fn fg_vi_config_default(cfg: *mut fg_vi_config);
+    pub fn fg_vi_elbo_batch(e: *mut fg_engine, h_factors: *const fg_vi_factor, n_eval: c_int, n_factors: c_int, h_stream_ids: *const u32,
+                            h_elbo: *mut f64, h_terms: *mut f64) -> c_int;
+    pub fn fg_vi_optimize(e: *mut fg_engine, h_factors: *mut fg_vi_factor, n_factors: c_int, cfg: *const fg_vi_config, h_elbo_history: *mut f64,
+                          h_result: *mut fg_vi_result) -> c_int;
+    pub fn fg_vi_estimate_elbo(e: *mut fg_engine, iteration: u32, h_elbo: *mut f64) -> c_int;
     // ---- checkpoint / resume (HmcSession fields hmc.rs:643-661)
     pub fn fg_state_size(e: *mut fg_engine) -> i64;
     pub fn fg_state_export(e: *mut fg_engine, h_buf: *mut c_void, capacity: usize) -> c_int;
