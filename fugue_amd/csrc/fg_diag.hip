@@ -14,7 +14,9 @@
 // moments [d][6][C]: full-chain mean, sum of squared deviations; then the same for the first and second half (half = n/2,
 // the middle draw dropped when n is odd: split_f64_chains :240-253).  Two sweeps over the column: the three sums (each
 // the in-order sum the reference forms, values.iter().sum() :275-278), then the three sums of squared deviations (:292-296).
-__global__ void k_diag_moments(const double *draws, int n, int d, long long C, double *out) {
+// `resid` (may be NULL) [d][C]: sum_t (x_t - mean) of the full chain -- what the rounded in-order mean leaves over; zero for an
+// exact mean.  The pooled std needs it where the offset of the draws dwarfs their spread (fg_diag_rhat_ess).
+__global__ void k_diag_moments(const double *draws, int n, int d, long long C, double *out, double *resid) {
     const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int i = blockIdx.y;
     if (c >= C) return;
@@ -29,15 +31,16 @@ __global__ void k_diag_moments(const double *draws, int n, int d, long long C, d
         if (t >= half && t < 2 * half) s_h2 += v;
     }
     const double m_full = n > 0 ? s_full / (double)n : NAN, m_h1 = half > 0 ? s_h1 / (double)half : NAN, m_h2 = half > 0 ? s_h2 / (double)half : NAN;
-    double q_full = 0.0, q_h1 = 0.0, q_h2 = 0.0;
+    double q_full = 0.0, q_h1 = 0.0, q_h2 = 0.0, r_full = 0.0;
     for (int t = 0; t < n; ++t) {
         const double v = x[t * st];
-        const double a = v - m_full; q_full += a * a;
+        const double a = v - m_full; q_full += a * a; r_full += a;
         if (t < half) { const double b = v - m_h1; q_h1 += b * b; }
         else if (t < 2 * half) { const double b = v - m_h2; q_h2 += b * b; }
     }
     double *o = out + (long long)i * 6 * C + c;
     o[0] = m_full; o[C] = q_full; o[2 * C] = m_h1; o[3 * C] = q_h1; o[4 * C] = m_h2; o[5 * C] = q_h2;
+    if (resid) resid[(long long)i * C + c] = r_full;
 }
 
 // Sum over chains of the biased autocovariances acov_t = (1/n) sum_i c_i c_{i+t} (autocovariances, mcmc_utils.rs:231-244) for
@@ -113,6 +116,18 @@ __global__ __launch_bounds__(256) void k_diag_chain_sums(const double *mom, long
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) partial[(long long)r * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+// The cross term of the pooled sum of squares: row i: sum_c (mean_c - gm[i]) resid_c (same fixed tree as k_diag_chain_sums).
+__global__ __launch_bounds__(256) void k_diag_std_cross(const double *mom, const double *resid, long long C, const double *gm, double *partial /*[d][gridDim.x]*/) {
+    __shared__ double sh[4];
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    double v = 0.0;
+    if (c < C) v = (mom[(long long)i * 6 * C + c] - gm[i]) * resid[(long long)i * C + c];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[(long long)i * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 __global__ void k_diag_sum_partials(const double *partial, int nblk, int rows, double *out) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -261,7 +276,7 @@ int fg_diag_combine(const double *h_moments, int64_t m, int n, int d, fg_acov_fn
 int fg_diag_chain_moments(fg_engine *e, const double *d_draws, int n, int d, double *d_moments) {
     NEED_ENGINE(e);
     if (!d_draws || !d_moments || n <= 0 || d <= 0) return FG_E_BAD_ARG;
-    hipLaunchKernelGGL(k_diag_moments, dim3((unsigned)((e->C + 255) / 256), (unsigned)d), dim3(256), 0, e->stream, d_draws, n, d, e->C, d_moments);
+    hipLaunchKernelGGL(k_diag_moments, dim3((unsigned)((e->C + 255) / 256), (unsigned)d), dim3(256), 0, e->stream, d_draws, n, d, e->C, d_moments, (double *)nullptr);
     HIPCHK(hipGetLastError());
     return FG_OK;
 }
@@ -436,6 +451,44 @@ int fg_diag_quantiles(fg_engine *e, const double *d_draws, int n, int d, void *c
     return FG_OK;
 }
 
+// The pooled sum of squares sum_j [ssd_j + n (mean_j - gm)^2] that the combination forms is an identity only for exact chain
+// means; with the rounded in-order mean_j it lacks 2 sum_j (mean_j - gm) resid_j, resid_j = sum_t (x_t - mean_j).  For draws like
+// 1e8 + 1e-3 N(0, 1) that term is 3e-7 of the total, ten times what the reference's single sum over all m n values loses
+// (summarize_f64_parameter, diagnostics.rs:331-352).  Added here: one chain sum on the device, with a communicator one more
+// all-reduce of d doubles.  The total is recovered as std^2 (m n - 1): a rounding of 1e-16, nothing the combination did not have.
+static int std_cross_correct(fg_engine *e, const double *d_mom, const double *d_res, int n, int d, int64_t m, void *comm, const double *h_mean, double *h_std,
+                             long long *bytes) {
+    const double dof = (double)m * (double)n - 1.0;
+    if (!(dof > 0.0)) return FG_OK;
+    const unsigned nb = (unsigned)((e->C + 255) / 256);
+    double *d_buf = nullptr;                                        // [d] gm | [d] cross | [d][nb] partials
+    int rc = dev_alloc(&d_buf, (size_t)d * (2 + nb));
+    if (rc) return rc;
+    double *d_gm = d_buf, *d_cross = d_buf + d, *d_part = d_buf + 2 * (size_t)d;
+    std::vector<double> cross((size_t)d, 0.0);
+    hipError_t he = hipMemcpyAsync(d_gm, h_mean, (size_t)d * 8, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(k_diag_std_cross, dim3(nb, (unsigned)d), dim3(256), 0, e->stream, d_mom, d_res, e->C, (const double *)d_gm, d_part);
+        hipLaunchKernelGGL(k_diag_sum_partials, dim3((unsigned)((d + 127) / 128)), dim3(128), 0, e->stream, (const double *)d_part, (int)nb, d, d_cross);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess && comm) {
+        Rccl *R = rccl();
+        const int nr = R->AllReduce(d_cross, d_cross, (size_t)d, kNcclFloat64, kNcclSum, comm, e->stream);
+        if (nr) { (void)hipFree(d_buf); return rccl_fail(R, "ncclAllReduce", nr); }
+        *bytes += (long long)d * 8;
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(cross.data(), d_cross, (size_t)d * 8, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    (void)hipFree(d_buf);
+    if (he != hipSuccess) { fg_set_error(hipGetErrorString(he)); return FG_E_HIP; }
+    for (int i = 0; i < d; ++i) {
+        const double total = h_std[i] * h_std[i] * dof + 2.0 * cross[i];
+        h_std[i] = std::sqrt((total < 0.0 ? 0.0 : total) / dof);   // (a NaN total stays NaN)
+    }
+    return FG_OK;
+}
+
 int fg_diag_set_exchange(fg_engine *e, int mode) {
     NEED_ENGINE(e);
     if (mode != FG_DIAG_REDUCE && mode != FG_DIAG_GATHER) return FG_E_BAD_ARG;
@@ -456,10 +509,15 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *co
     int world = 1;
     if (comm) { const int rc = R->CommCount(comm, &world); if (rc) return rccl_fail(R, "ncclCommCount", rc); }
     const size_t per = (size_t)d * 6 * e->C;
-    double *d_mom = nullptr, *d_all = nullptr, *d_small = nullptr, *d_part = nullptr;
+    double *d_mom = nullptr, *d_all = nullptr, *d_small = nullptr, *d_part = nullptr, *d_res = nullptr;
     int rc = dev_alloc(&d_mom, per);
     if (rc) return rc;
-    rc = fg_diag_chain_moments(e, d_draws, n, d, d_mom);
+    if (h_std) rc = dev_alloc(&d_res, (size_t)d * e->C);
+    if (rc) { (void)hipFree(d_mom); return rc; }
+    hipLaunchKernelGGL(k_diag_moments, dim3((unsigned)((e->C + 255) / 256), (unsigned)d), dim3(256), 0, e->stream, d_draws, n, d, e->C, d_mom, d_res);
+    if (hipGetLastError() != hipSuccess) { fg_set_error("fg_diag_rhat_ess: the moments kernel did not launch"); rc = FG_E_HIP; }
+    std::vector<double> mean_buf;
+    if (h_std && !h_mean) { mean_buf.resize((size_t)d); h_mean = mean_buf.data(); }      // the correction needs the pooled means
     std::vector<double> mom;
     const int64_t m = (int64_t)world * e->C;
     e->diag_bytes = 0;
@@ -471,12 +529,14 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *co
         if (!rc) {
             AcovCtx A{ e, d_draws, n, d, d_mom, comm, d_small, d_part, 0 };
             rc = fg_diag_combine_reduced(m, n, d, reduce_cb, acov_cb, &A, h_rhat, h_ess, h_mean, h_std);
+            if (!rc && h_std) rc = std_cross_correct(e, d_mom, d_res, n, d, m, comm, h_mean, h_std, &A.bytes);
             e->diag_bytes = A.bytes;
         }
         if (d_small) (void)hipFree(d_small);
         if (d_part) (void)hipFree(d_part);
         if (out_total_chains) *out_total_chains = m;
         (void)hipFree(d_mom);
+        if (d_res) (void)hipFree(d_res);
         return rc;
     }
     if (!rc && comm) {                                              // FG_DIAG_GATHER: every rank gets every chain's moments (all-gather over RCCL / xGMI)
@@ -500,10 +560,12 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *co
     if (!rc) {
         AcovCtx A{ e, d_draws, n, d, d_mom, comm, nullptr, nullptr, 0 };
         rc = fg_diag_combine(mom.data(), m, n, d, acov_cb, &A, h_rhat, h_ess, h_mean, h_std);
+        if (!rc && h_std) rc = std_cross_correct(e, d_mom, d_res, n, d, m, comm, h_mean, h_std, &A.bytes);
         e->diag_bytes += A.bytes;
     }
     if (out_total_chains) *out_total_chains = m;
     (void)hipFree(d_mom);
+    if (d_res) (void)hipFree(d_res);
     if (d_all) (void)hipFree(d_all);
     return rc;
 }

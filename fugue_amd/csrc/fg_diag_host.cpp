@@ -74,7 +74,7 @@ static int ess_from_pooled(int64_t m, int n, double mean_var, double between, Ac
     }
     double sum_rho = 0.0;
     for (int k = 0; k <= max_t; k++) sum_rho += rho_hat[k];
-    const double tau = std::max(-1.0 + 2.0 * sum_rho, 1.0);
+    const double tau = std::fmax(-1.0 + 2.0 * sum_rho, 1.0);   // f64::max (:337): a NaN sum (one non-finite draw) gives 1.0; std::max would return the NaN
     out = (double)((long long)m * n) / tau;
     return FG_OK;
 }

@@ -401,7 +401,8 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *rc
 /* How the ranks of `rccl_comm` exchange chain statistics inside fg_diag_rhat_ess.  FG_DIAG_REDUCE (default): chains enter split
  * R-hat (diagnostics.rs:262-304), the pooled mean / std and the multi-chain ESS (mcmc_utils.rs:253-339) only through sums over
  * chains, so every rank reduces its own chains on the device and the ranks all-reduce 6 d + 2 d doubles plus 32 d per chunk of
- * lags -- nothing proportional to the chain count leaves a GPU.  FG_DIAG_GATHER: all-gather of every chain's moments
+ * lags (+ d when h_std is asked for: the cross term sum_j (mean_j - mean) sum_t (x_t - mean_j) that keeps the pooled std exact
+ * when the in-order chain means are rounded, in either mode) -- nothing proportional to the chain count leaves a GPU.  FG_DIAG_GATHER: all-gather of every chain's moments
  * ([d][6][C] per rank) and the combination in global chain order on every rank, as a single process would sum them.  The two
  * agree to rounding of the sums over chains (~1e-15 relative).  fg_diag_exchange_bytes: bytes this rank contributed to
  * collectives during the last fg_diag_rhat_ess (0 without a communicator). */

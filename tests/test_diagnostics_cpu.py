@@ -107,9 +107,10 @@ dist.destroy_process_group()
         assert out["mean"][i] == pytest.approx(s["mean"], rel=1e-11, abs=1e-12) and out["std"][i] == pytest.approx(s["std"], rel=1e-10)
 
 
-def test_combine_is_native_and_needs_no_gpu():
+def test_combine_is_native_and_needs_no_gpu(oracle):
     """The R-hat / Geyer-ESS combination runs in the library (fg_diag_combine, C++): same numbers as the oracle on ragged
-    sizes, NaN / degenerate inputs follow the reference's rules (diagnostics.rs:262-270, mcmc_utils.rs:259-279)."""
+    sizes, NaN / degenerate inputs follow the reference's rules (diagnostics.rs:262-270, mcmc_utils.rs:259-279, and
+    f64::max at :337: a NaN autocorrelation sum gives tau = 1, so one non-finite draw reports ESS = m n, not NaN)."""
     from fugue_amd import engine as E
     rng = np.random.default_rng(5)
     x = np.stack([ar1(rng, 120, 6, 0.5), np.ones((120, 6))], axis=1)
@@ -119,5 +120,17 @@ def test_combine_is_native_and_needs_no_gpu():
     one = NumpyMoments(x[:, :1, :1])
     r1 = E.diag_combine(one.moments(), 120, one.autocov_sums)
     assert np.isfinite(r1["r_hat"][0])                                      # one chain still splits into two halves
+    for bad in (np.nan, np.inf, -np.inf):                                   # one non-finite draw in one chain of coordinate 0
+        y = x.copy()
+        y[37, 0, 2] = bad
+        want = oracle.ess_multichain(_chains(y, 0))
+        assert want == 720.0
+        bm = NumpyMoments(y)
+        with np.errstate(invalid="ignore"):                                  # numpy moments of a non-finite draw: the input of this case
+            rb = E.diag_combine(bm.moments(), 120, bm.autocov_sums)
+            cd = D.ChainDiagnostics(bm, exchange="reduce")                   # fg_diag_combine_reduced: the same rule
+            assert cd.ess()[0] == want and np.isnan(cd.split_rhat()[0])
+        assert rb["ess"][0] == want and np.isnan(rb["r_hat"][0]) and np.isnan(oracle.split_rhat(_chains(y, 0)))
+        assert rb["ess"][1] == 720.0 and cd.ess()[1] == 720.0               # the other coordinate does not see it
     tiny = NumpyMoments(rng.standard_normal((1, 1, 3)))
     assert E.diag_combine(tiny.moments(), 1, tiny.autocov_sums)["r_hat"][0] == pytest.approx(D.ChainDiagnostics(tiny).classic_rhat()[0], nan_ok=True)

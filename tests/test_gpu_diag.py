@@ -64,7 +64,8 @@ def test_native_rhat_ess_entry_point_and_geweke(oracle, exchange):
         E.comm_destroy(comm)
     for k in ("r_hat", "ess", "mean", "std"):
         assert np.array_equal(r[k], r1[k])
-    lag_bytes = r1["exchange_bytes"] - (8 * cp.d * 8 if exchange == E.DIAG_REDUCE else 6 * cp.d * C * 8)
+    # 6 d + 2 d chain sums (reduce) or every chain's six moments (gather), + d for the pooled std's cross term, + the lag chunks
+    lag_bytes = r1["exchange_bytes"] - (9 * cp.d * 8 if exchange == E.DIAG_REDUCE else 6 * cp.d * C * 8 + cp.d * 8)
     assert lag_bytes > 0 and lag_bytes % (32 * cp.d * 8) == 0                  # what the rank put into collectives: O(d) in the reduce mode
     eng.device_free(d_draws)
 
