@@ -26,6 +26,15 @@ static __global__ void k_fill(double *p, long long n, double v) {
     if (i < n) p[i] = v;
 }
 
+// The multi-wave MH launchers' once-per-engine state (fg_mh.hip): the parts of the plan (fg_mh_mw_plan.h) made at the first launch and their device copies.
+struct FgMhMwUnit { int state = 0; hipModule_t mod = nullptr; hipFunction_t fn = nullptr; double *d_tab = nullptr; };   // the kernel with statements compiled at run time: 0 not tried, 1 loaded, -1 unavailable; its constant tables (fg_jit_bind_tables)
+struct FgMhMwState {
+    FgGradRec *d_srt = nullptr; int cls_off[7] = {0, 0, 0, 0, 0, 0, 0};   // kind-sorted score stream, class boundaries
+    int ncu = -1, catu_same = 0; double catu_c0 = 0.0; double *d_catu_c = nullptr; void *d_catu = nullptr;   // row-less uniform Categorical terms (FgMhSeg; -1: not decided)
+    int baked[7] = {0, 0, 0, 0, 0, 0, 0}; bool has_baked = false;   // the launch shape the unit was generated for (FgMhJitSpec::baked)
+    FgMhMwUnit unit, unit_ns;    // of a program with a score stream, phase B generated / of a program without one
+};
+
 struct fg_engine {
     const fg_program *prog = nullptr;
     int device = 0;
@@ -40,7 +49,6 @@ struct fg_engine {
     FgCoord *d_coord = nullptr;
     FgGradRec *d_gstream = nullptr, *d_sstream = nullptr;
     FgSepRec *d_sep = nullptr; FgSepCoord *d_sep_coord = nullptr; FgSepFree *d_sep_free = nullptr; uint32_t *d_sobs = nullptr; int *d_site_rec = nullptr;
-    FgGradRec *d_mh_srt = nullptr; int mh_cls_off[7] = {0, 0, 0, 0, 0, 0, 0};   // kind-sorted score stream of the multi-wave MH kernel (fg_mh.hip), class boundaries
     bool mh_mw_disabled = false;  // FG_MH_MW=0: keep every program on the one-wave-per-tile MH kernel (A/B tests)
     bool mh_has_prior_resample = false;   // an override asks for PriorResample on some site (needs the model-driven proposal path)
     bool sep_disabled = false;   // FG_HMC_SEP=0: keep independent-sites programs on the gradient-stream kernel (A/B tests)
@@ -88,10 +96,7 @@ struct fg_engine {
     int mhi_W = 0, mhi_n_stmt = 0, mhi_occ = 2; bool mhi_setup_done = false; size_t mhi_lds = 0; std::vector<int> mhi_ins_off, mhi_stmt_off; unsigned char *d_mhi_acc = nullptr; int *d_mhi_site_ins = nullptr; std::vector<int> mhi_stmt_end; std::vector<unsigned char> mhi_acc_host;   // statement split of k_mh_interp_mw_steps (fg_mh_interp.hip)
     int jit_state = 0;           // run-time compiled HMC kernel of this program: 0 not tried, 1 loaded, -1 unavailable (fg_jit.cpp; FG_JIT=0 switches it off)
     hipModule_t jit_mod = nullptr; hipFunction_t jit_fn = nullptr, jit_fn_eps = nullptr, jit_fn_rejuv = nullptr, jit_fn_prior = nullptr, jit_fn_lj = nullptr; std::string jit_log; bool jit_lds_attr = false, jit_rejuv_attr = false, jit_has_ad = false, jit_has_dense = false, an_jit = false /* FG_GRAD_ANALYTIC runs on the compiled unit's derivative code */; double *d_jit_tab = nullptr, *d_jit_mh_tab = nullptr;   // the modules' constant tables (fg_jit_bind_tables)
-    int mh_ncu = -1, mh_catu_same = 0; double mh_catu_c0 = 0.0; double *d_mh_catu_c = nullptr; void *d_mh_catu = nullptr;   // row-less uniform Categorical terms of the multi-wave MH kernel (FgMhSeg; -1: not decided)
-    int jit_mhns_state = 0, jit_mhns_split = 0; hipModule_t jit_mhns_mod = nullptr; hipFunction_t jit_mhns_fn = nullptr; double *d_jit_mhns_tab = nullptr;   // ... the same kernel for a program without a score stream
-    int jit_mhmw_baked[7] = {0, 0, 0, 0, 0, 0, 0}; bool jit_mhmw_has_baked = false;   // the launch shape the unit below was generated for (fg_jit_mhmw_source)
-    int jit_mhmw_state = 0; hipModule_t jit_mhmw_mod = nullptr; hipFunction_t jit_mhmw_fn = nullptr; double *d_jit_mhmw_tab = nullptr;   // ... the multi-wave stream MH kernel with phase B generated (fg_mh.hip)
+    FgMhMwState mhmw;            // what the multi-wave MH launchers decide once per engine (fg_mh.hip)
     int jit_mh_state = 0, jit_mh_W = 1, jit_mh_direct = 0; size_t jit_mh_lds = 0; hipModule_t jit_mh_mod = nullptr; hipFunction_t jit_mh_fn[2] = {nullptr, nullptr};   // ... and its MH kernel (128- and 256-VGPR builds)
     std::string last_mh_kernel;  // kernel the last fg_mh_step launch ran (fg_mh_last_kernel)
     // mean-field VI (fg_vi.hip): factor table, stream ids, per-sample terms, per-wave sums, ELBOs, global tiles -- grown on demand

@@ -794,8 +794,6 @@ struct FgSepVariant { FgSepKey key; FgSepKernel fn; unsigned long long raised; }
 static FgSepVariant fg_sep_variants[] = { FG_SEP_VARIANTS(FG_SEP_ENTRY) };
 #undef FG_SEP_ENTRY
 
-static FgSwitch fg_env_switch(const char *name) { const char *v = std::getenv(name); return FgSwitch{ v != nullptr, v ? std::atoi(v) : 0 }; }
-
 // Launch for `n` transitions from iteration `iter0`; returns FG_E_UNSUPPORTED when the program / configuration is not an
 // independent-sites FD-sparse run (the caller then takes the gradient-stream kernel).  Plan (fg_hmc_sep_plan.h), look up, launch, name.
 int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "fg_ir.h"
+#include "fg_switch.h"
 #include "../../include/fugue_amd.h"
 
 #define FG_SEP_WMAX 16
@@ -32,7 +33,6 @@ inline bool operator==(const FgSepKey &a, const FgSepKey &b) {
     return a.mass == b.mass && a.mode == b.mode && a.half == b.half && a.nc == b.nc && a.nobs == b.nobs && a.u0 == b.u0 && a.fold == b.fold;
 }
 
-struct FgSwitch { bool set; int v; };                      // an environment switch read at launch time: unset, or its integer value
 struct FgSepPlanIn {
     long long C; int d, n_simd, n_slots, n_sep_free, n_sstream;
     int grad_mode; bool use_mass; int mw_override;         // (FG_HMC_WAVES)

@@ -31,6 +31,7 @@
 
 #include "fg_program.h"
 #include "fg_jit.h"
+#include "fg_mh_mw_plan.h"
 #include "_fg_jit_embed.inc"      // FG_JIT_EMBED: fg_ir.h, fg_math.h, fg_cold.h, fg_dev_types.h and fg_hmc_jit_body.h as text (fugue_amd/build.py)
 
 namespace {
@@ -830,8 +831,13 @@ void k_mh_jit_steps_occ##OCC(FgProgramDev P, FgChainCtx X, FgMhDev M, FgMhi seg,
 // wave, in-order sums, the operand-pattern runs of plain Normal records -- all of it the hand-written kernel's) with the GENERAL
 // records of phase B (generated[k] != 0: statement k's log-density term into its LDS row) as FG_JIT_NSEG generated statement
 // segments instead of fg_score_one over the record stream.
-std::string fg_jit_mhmw_source(const fg_program *p, const std::vector<long long> &ins_cost, const std::vector<char> &generated, int rk, int split, std::vector<double> *ctab_out,
-                               const std::vector<int> *rows_in, int n_pri, int n_fac, bool no_stream, bool pipe, int nseg, int ctl_share16, int sum_pri, int sum_lik, const int *baked, int sums_form) {
+std::string fg_jit_mhmw_source(const fg_program *p, const std::vector<long long> &ins_cost, const FgMhJitSpec &spec, std::vector<double> *ctab_out) {
+    if (!spec.unit) return "";
+    const std::vector<char> &generated = spec.generated;
+    const std::vector<int> &rows = spec.rows;
+    const int rk = spec.rk, split = spec.split, n_pri = spec.n_pri, n_fac = spec.n_fac, nseg = spec.nseg, ctl_share16 = spec.ctl16, sum_pri = spec.sum_pri, sum_lik = spec.sum_lik;
+    const bool no_stream = spec.no_stream, pipe = spec.pipe;
+    const int *baked = spec.bake ? spec.baked : nullptr;
     // statement segments: sixteen dealt to the waves (sg = wave, wave + W, ...), or -- nseg = the launch's waves per tile -- ONE per wave:
     // a wave's statements are then one straight-line function whose LDS reads are all in flight together
     const int NSEG = (nseg >= 2 && nseg <= 16) ? nseg : 16;
@@ -842,9 +848,7 @@ std::string fg_jit_mhmw_source(const fg_program *p, const std::vector<long long>
     for (int k = 0; k < p->n_ins; ++k) if (Gen::ends_statement(p->ins_fast[(size_t)k])) stmt_end.push_back(k + 1);
     const int n_stmt = (int)stmt_end.size();
     if (n_stmt < 1 || stmt_end.back() != p->n_ins || (int)generated.size() != n_stmt) return "";
-    if (rows_in ? (int)rows_in->size() != n_stmt : n_stmt != p->n_sstream) return "";         // one record per statement, in program order
-    std::vector<int> rows((size_t)n_stmt);
-    for (int k = 0; k < n_stmt; ++k) rows[(size_t)k] = rows_in ? (*rows_in)[(size_t)k] : (int)p->sstream[(size_t)k].coord;
+    if ((int)rows.size() != n_stmt || (!no_stream && n_stmt != p->n_sstream)) return "";         // one record per statement, in program order
     std::vector<long long> cum((size_t)n_stmt + 1, 0);
     for (int k = 0, i = 0; k < n_stmt; ++k) {             // work before statement k (the generated statements only)
         long long cs = 0; for (; i < stmt_end[(size_t)k]; ++i) cs += ins_cost[(size_t)i];
@@ -966,7 +970,7 @@ std::string fg_jit_mhmw_source(const fg_program *p, const std::vector<long long>
     // added in program order from 0.0 -- fg_inorder_sums2's additions -- without chunk loops, tails of selected zeros or address arithmetic)
     if (!no_stream && sum_pri >= 0 && sum_lik >= 0 && sum_pri + sum_lik <= 48) {     // (short programs: reference_model(50) and normal32 -- 64 and 99 rows -- measured 8-12 % slower with straight-line sums than with the chunked loops)
         std::string f = "static __device__ __forceinline__ void fg_jit_sums2(const FG_LDSQ double *terms, double &pri_out, double &lik_out) {\n    double a = 0.0, b = 0.0;\n";   // (inline: a call would drain the control wave's adaptation-state gather, which is in flight across the sums)
-        const int form = std::getenv("FG_MH_SUMS_FORM") ? std::atoi(std::getenv("FG_MH_SUMS_FORM")) : sums_form;   // (0: plain statements; 3: pinned, no prefetch; n >= 4: pinned, rows n pairs ahead -- profiles/round4_mh_sums_form.txt)
+        const int form = spec.sums_form;   // (0: plain statements; 3: pinned, no prefetch; n >= 4: pinned, rows n pairs ahead -- profiles/round4_mh_sums_form.txt)
         if (form >= 3) {         // (every row requested first instead -- 78 live VGPRs -- spilled 36 registers and lost 7 %: profiles/round4_mh_sums_form.txt)
             // the two chains pinned side by side (b is only used behind the branches that follow: the sink pass moves its whole chain there, and the scheduler
             // runs a to its end first -- 39 dependent additions where 20 pairs do); loads do not cross the pins, so the rows are requested `form` pairs ahead
@@ -1004,7 +1008,7 @@ std::string fg_jit_mhmw_source(const fg_program *p, const std::vector<long long>
     // what every launch of this unit passes anyway (the engine checks it does): row counts, tile layout, waves per tile and the mode bits as literals --
     // the step loop loses their scalar tests and branches, LDS addresses become instruction offsets
     if (baked && !pipe) {
-        if (!no_stream && !(std::getenv("FG_MH_BAKE") && std::atoi(std::getenv("FG_MH_BAKE")) == 2)) src += "#define FG_MHMW_K_NCU " + std::to_string(baked[0]) + "\n#define FG_MHMW_K_NS " + std::to_string(baked[1]) + "\n#define FG_MHMW_K_NPRI " + std::to_string(baked[2]) + "\n";
+        if (!no_stream && spec.bake_rows) src += "#define FG_MHMW_K_NCU " + std::to_string(baked[0]) + "\n#define FG_MHMW_K_NS " + std::to_string(baked[1]) + "\n#define FG_MHMW_K_NPRI " + std::to_string(baked[2]) + "\n";
         src += "#define FG_MHMW_K_NSLOTS " + std::to_string(baked[3]) + "\n#define FG_MHMW_K_W " + std::to_string(baked[4]) + "\n#define FG_MHMW_K_EXP " + std::to_string(baked[5]) +
                "\n#define FG_MHMW_K_POOLN " + std::to_string(baked[6]) + "\n";
     }
@@ -1175,19 +1179,32 @@ extern "C" int fg_debug_jit_compile(const fg_program *p, char *src_out, long lon
     const bool mh = std::getenv("FG_DEBUG_JIT_MH") != nullptr;            // the MH unit instead of the HMC one
     if (std::getenv("FG_DEBUG_JIT_MHMW")) {                                // the multi-wave stream MH unit
         std::string s2;
-        // FG_DEBUG_JIT_BAKE="exp_mask": the launch shape as literals (FG_DEBUG_JIT_NSEG waves per tile, no row-less terms, no staged pool)
-        const int dbg_baked[7] = { 0, p->n_sstream, p->n_prior_terms, p->n_slots, std::getenv("FG_DEBUG_JIT_NSEG") ? std::atoi(std::getenv("FG_DEBUG_JIT_NSEG")) : 0, std::getenv("FG_DEBUG_JIT_BAKE") ? std::atoi(std::getenv("FG_DEBUG_JIT_BAKE")) : 0, 0 };
-        if (p->n_sstream > 0) s2 = fg_jit_mhmw_source(p, std::vector<long long>((size_t)p->n_ins, 1), std::vector<char>((size_t)p->n_sstream, 1), p->sstream_has_gen ? (p->sstream_has_genrec ? 2 : 3) : 0, p->n_sstream >= 64, nullptr, nullptr, -1, 0, false, std::getenv("FG_MH_PIPE") && std::atoi(std::getenv("FG_MH_PIPE")) == 1, std::getenv("FG_DEBUG_JIT_NSEG") ? std::atoi(std::getenv("FG_DEBUG_JIT_NSEG")) : 0, 16, p->n_prior_terms, p->n_sstream - p->n_prior_terms, std::getenv("FG_DEBUG_JIT_BAKE") ? dbg_baked : nullptr, std::getenv("FG_MH_SUMS_FORM") ? std::atoi(std::getenv("FG_MH_SUMS_FORM")) : 0);
-        else {                                                             // a program without a score stream: rows in accumulator order (fg_mh_mw_nostream_launch)
-            std::vector<int> rows; int n_pri = 0, n_lik = 0, n_fac = 0;
+        FgMhJitSpec sp;
+        sp.tried = sp.unit = true;
+        sp.sums_form = std::getenv("FG_MH_SUMS_FORM") ? std::atoi(std::getenv("FG_MH_SUMS_FORM")) : 0;
+        if (p->n_sstream > 0) {
+            // FG_DEBUG_JIT_BAKE="exp_mask": the launch shape as literals (FG_DEBUG_JIT_NSEG waves per tile, no row-less terms, no staged pool)
+            sp.nseg = std::getenv("FG_DEBUG_JIT_NSEG") ? std::atoi(std::getenv("FG_DEBUG_JIT_NSEG")) : 0;
+            const int dbg_baked[7] = { 0, p->n_sstream, p->n_prior_terms, p->n_slots, sp.nseg, std::getenv("FG_DEBUG_JIT_BAKE") ? std::atoi(std::getenv("FG_DEBUG_JIT_BAKE")) : 0, 0 };
+            std::memcpy(sp.baked, dbg_baked, sizeof dbg_baked);
+            sp.bake = std::getenv("FG_DEBUG_JIT_BAKE") != nullptr; sp.bake_rows = !(std::getenv("FG_MH_BAKE") && std::atoi(std::getenv("FG_MH_BAKE")) == 2);
+            sp.generated.assign((size_t)p->n_sstream, 1);
+            for (int k = 0; k < p->n_sstream; ++k) sp.rows.push_back((int)p->sstream[(size_t)k].coord);
+            sp.rk = p->sstream_has_gen ? (p->sstream_has_genrec ? 2 : 3) : 0; sp.split = p->n_sstream >= 64;
+            sp.pipe = std::getenv("FG_MH_PIPE") && std::atoi(std::getenv("FG_MH_PIPE")) == 1;
+            sp.sum_pri = p->n_prior_terms; sp.sum_lik = p->n_sstream - p->n_prior_terms;
+        } else {                                                           // a program without a score stream: rows in accumulator order (fg_mh_mw_nostream_launch)
+            std::vector<int> &rows = sp.rows; int n_pri = 0, n_lik = 0, n_fac = 0;
             for (int k = 0; k < p->n_ins; ++k) if (Gen::ends_statement(p->ins_fast[(size_t)k])) {
                 const uint32_t code = FG_INS_OPCODE(p->ins_fast[(size_t)k].op);
                 const int a = code == FG_OP_FACTOR ? 2 : ((p->ins_fast[(size_t)k].op & FG_F_OBSERVE) != 0 || code == FG_OP_CONSTLIK) ? 1 : 0;
                 rows.push_back(a); (a == 0 ? n_pri : a == 1 ? n_lik : n_fac) += 1;
             }
             for (int k = 0, a = 0, b = n_pri, c = n_pri + n_lik; k < (int)rows.size(); ++k) rows[(size_t)k] = rows[(size_t)k] == 0 ? a++ : rows[(size_t)k] == 1 ? b++ : c++;
-            s2 = fg_jit_mhmw_source(p, std::vector<long long>((size_t)p->n_ins, 1), std::vector<char>(rows.size(), 1), 3, rows.size() >= 64, nullptr, &rows, n_pri, n_fac, true);
+            sp.generated.assign(rows.size(), 1);
+            sp.rk = 3; sp.split = rows.size() >= 64; sp.n_pri = n_pri; sp.n_fac = n_fac; sp.no_stream = true;
         }
+        s2 = fg_jit_mhmw_source(p, std::vector<long long>((size_t)p->n_ins, 1), sp, nullptr);
         if (src_out && src_cap > 0) std::snprintf(src_out, (size_t)src_cap, "%s", s2.c_str());
         if (code_bytes) *code_bytes = 0;
         if (s2.empty()) return FG_E_UNSUPPORTED;
