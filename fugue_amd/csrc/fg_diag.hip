@@ -8,6 +8,7 @@
 // RCCL: an all-gather of the per-chain moments and an all-reduce of the pooled lag sums; the Geyer / R-hat combination
 // is C++ (fg_diag_host.cpp).  RCCL is bound at run time (dlopen): the copy that sits next to the HIP runtime this library runs on.
 #include "fg_engine_internal.h"
+#include "fg_diag_internal.h"
 
 #include <dlfcn.h>
 
@@ -262,8 +263,6 @@ int rccl_fail(Rccl *R, const char *what, int rc) {
     return FG_E_HIP;
 }
 const int kNcclFloat64 = 8, kNcclUint64 = 5, kNcclSum = 0;
-
-struct AcovCtx { fg_engine *e; const double *d_draws; int n, d; const double *d_mom; void *comm; double *d_small; double *d_part; long long bytes; };
 }  // namespace
 
 extern "C" {
@@ -304,6 +303,16 @@ static int acov_sums_device(fg_engine *e, const double *d_draws, int n, int d, c
     if (he != hipSuccess) { fg_set_error(hipGetErrorString(he)); return FG_E_HIP; }
     return FG_OK;
 }
+
+}  // extern "C"
+int fg_diag_finish_lag_sums(fg_engine *e, const double *d_part, int nblk, int n_lags, int d, double *d_sums) {
+    hipLaunchKernelGGL(k_diag_acov_finish, dim3((unsigned)((d * n_lags + 127) / 128)), dim3(128), 0, e->stream, d_part, nblk, n_lags, d, d_sums);
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he != hipSuccess) { fg_set_error(hipGetErrorString(he)); return FG_E_HIP; }
+    return FG_OK;
+}
+extern "C" {
 
 int fg_diag_autocov_sums(fg_engine *e, const double *d_draws, int n, int d, const double *d_moments, int lag0, int n_lags, double *h_sums) {
     NEED_ENGINE(e);
@@ -356,7 +365,7 @@ static int acov_cb(void *user, int lag0, int n_lags, double *h_sums) {
     double *d_sums = nullptr;
     int rc = dev_alloc(&d_sums, (size_t)A->d * FG_ACOV_LAGS);
     if (rc) return rc;
-    rc = acov_sums_device(e, A->d_draws, A->n, A->d, A->d_mom, lag0, n_lags, d_sums);
+    rc = A->sums ? A->sums(A, lag0, n_lags, d_sums) : acov_sums_device(e, A->d_draws, A->n, A->d, A->d_mom, lag0, n_lags, d_sums);
     if (!rc && A->comm) {                                          // pooled over every rank's chains: all-reduce over RCCL / xGMI
         Rccl *R = rccl();
         const int nr = R->AllReduce(d_sums, d_sums, (size_t)A->d * n_lags, kNcclFloat64, kNcclSum, A->comm, e->stream);
@@ -504,30 +513,47 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *co
                      int64_t *out_total_chains) {
     NEED_ENGINE(e);
     if (!d_draws || n <= 0 || d <= 0) return FG_E_BAD_ARG;
-    Rccl *R = comm ? rccl() : nullptr;
-    if (comm && !R) { fg_set_error("RCCL is not available (librccl.so not found)"); return FG_E_UNSUPPORTED; }
-    int world = 1;
-    if (comm) { const int rc = R->CommCount(comm, &world); if (rc) return rccl_fail(R, "ncclCommCount", rc); }
+    if (comm && !rccl()) { fg_set_error("RCCL is not available (librccl.so not found)"); return FG_E_UNSUPPORTED; }
     const size_t per = (size_t)d * 6 * e->C;
-    double *d_mom = nullptr, *d_all = nullptr, *d_small = nullptr, *d_part = nullptr, *d_res = nullptr;
+    double *d_mom = nullptr, *d_res = nullptr;
     int rc = dev_alloc(&d_mom, per);
     if (rc) return rc;
     if (h_std) rc = dev_alloc(&d_res, (size_t)d * e->C);
     if (rc) { (void)hipFree(d_mom); return rc; }
     hipLaunchKernelGGL(k_diag_moments, dim3((unsigned)((e->C + 255) / 256), (unsigned)d), dim3(256), 0, e->stream, d_draws, n, d, e->C, d_mom, d_res);
     if (hipGetLastError() != hipSuccess) { fg_set_error("fg_diag_rhat_ess: the moments kernel did not launch"); rc = FG_E_HIP; }
+    if (!rc) rc = fg_diag_rhat_ess_from_moments(e, n, d, comm, d_mom, d_res, AcovCtx{ e, d_draws, n, d, d_mom, comm, nullptr, nullptr, 0 }, h_rhat, h_ess, h_mean, h_std,
+                                                out_total_chains);
+    (void)hipFree(d_mom);
+    if (d_res) (void)hipFree(d_res);
+    return rc;
+}
+
+}  // extern "C"
+
+int fg_diag_rhat_ess_from_moments(fg_engine *e, int n, int d, void *comm, const double *d_mom, const double *d_res, const AcovCtx &proto,
+                                  double *h_rhat, double *h_ess, double *h_mean, double *h_std, int64_t *out_total_chains) {
+    Rccl *R = comm ? rccl() : nullptr;
+    if (comm && !R) { fg_set_error("RCCL is not available (librccl.so not found)"); return FG_E_UNSUPPORTED; }
+    int world = 1;
+    if (comm) { const int rc = R->CommCount(comm, &world); if (rc) return rccl_fail(R, "ncclCommCount", rc); }
+    const size_t per = (size_t)d * 6 * e->C;
+    double *d_all = nullptr, *d_small = nullptr, *d_part = nullptr;
+    int rc = FG_OK;
     std::vector<double> mean_buf;
     if (h_std && !h_mean) { mean_buf.resize((size_t)d); h_mean = mean_buf.data(); }      // the correction needs the pooled means
     std::vector<double> mom;
     const int64_t m = (int64_t)world * e->C;
     e->diag_bytes = 0;
-    if (!rc && e->diag_mode == FG_DIAG_REDUCE) {
+    AcovCtx A = proto;
+    A.e = e; A.n = n; A.d = d; A.d_mom = d_mom; A.comm = comm; A.bytes = 0;
+    if (e->diag_mode == FG_DIAG_REDUCE) {
         // the default exchange: chains enter R-hat, the pooled moments and the ESS only through sums over chains -- all-reduces of
         // 6 d, 2 d and 32 d (per lag chunk) doubles, nothing proportional to the chain count leaves the GPU
         rc = dev_alloc(&d_small, (size_t)10 * d);
         if (!rc) rc = dev_alloc(&d_part, (size_t)6 * d * ((e->C + 255) / 256));
         if (!rc) {
-            AcovCtx A{ e, d_draws, n, d, d_mom, comm, d_small, d_part, 0 };
+            A.d_small = d_small; A.d_part = d_part;
             rc = fg_diag_combine_reduced(m, n, d, reduce_cb, acov_cb, &A, h_rhat, h_ess, h_mean, h_std);
             if (!rc && h_std) rc = std_cross_correct(e, d_mom, d_res, n, d, m, comm, h_mean, h_std, &A.bytes);
             e->diag_bytes = A.bytes;
@@ -535,11 +561,9 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *co
         if (d_small) (void)hipFree(d_small);
         if (d_part) (void)hipFree(d_part);
         if (out_total_chains) *out_total_chains = m;
-        (void)hipFree(d_mom);
-        if (d_res) (void)hipFree(d_res);
         return rc;
     }
-    if (!rc && comm) {                                              // FG_DIAG_GATHER: every rank gets every chain's moments (all-gather over RCCL / xGMI)
+    if (comm) {                                                     // FG_DIAG_GATHER: every rank gets every chain's moments (all-gather over RCCL / xGMI)
         rc = dev_alloc(&d_all, per * world);
         if (!rc) { const int nr = R->AllGather(d_mom, d_all, per, kNcclFloat64, comm, e->stream); if (nr) rc = rccl_fail(R, "ncclAllGather", nr); }
         e->diag_bytes += (long long)per * 8;
@@ -558,16 +582,12 @@ int fg_diag_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, void *co
         }
     }
     if (!rc) {
-        AcovCtx A{ e, d_draws, n, d, d_mom, comm, nullptr, nullptr, 0 };
+        A.d_small = nullptr; A.d_part = nullptr;
         rc = fg_diag_combine(mom.data(), m, n, d, acov_cb, &A, h_rhat, h_ess, h_mean, h_std);
         if (!rc && h_std) rc = std_cross_correct(e, d_mom, d_res, n, d, m, comm, h_mean, h_std, &A.bytes);
         e->diag_bytes += A.bytes;
     }
     if (out_total_chains) *out_total_chains = m;
-    (void)hipFree(d_mom);
-    if (d_res) (void)hipFree(d_res);
     if (d_all) (void)hipFree(d_all);
     return rc;
 }
-
-}  // extern "C"

@@ -52,6 +52,24 @@ class EngineMoments:
             self._d_mom = 0
 
 
+class StreamMoments:
+    """MomentProvider over an `engine.DiagStream` that has taken all its draws: the run was handed to the stream one chunk at a
+    time and is stored nowhere.  `ChainDiagnostics(StreamMoments(stream), group, device, exchange)` works as with any other
+    provider; a lag beyond the stream's K surfaces as `EngineError` (FG_E_LIMIT), never as a figure."""
+
+    def __init__(self, stream):
+        self.stream, self.n, self.d = stream, int(stream.n), int(stream.d)
+        self._mom: Optional[np.ndarray] = None
+
+    def moments(self) -> np.ndarray:
+        if self._mom is None:
+            self._mom = self.stream.moments()
+        return self._mom
+
+    def autocov_sums(self, lag0: int, n_lags: int) -> np.ndarray:
+        return self.stream.autocov_sums(lag0, n_lags)
+
+
 class HostMoments:
     """MomentProvider over host draws [n][d][C] (numpy): the same statistics the GPU kernels produce, for callers that
     already hold the draws on the host (fugue_amd.validation) and for CPU tests of the combination logic."""

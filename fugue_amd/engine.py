@@ -91,6 +91,8 @@ ABI_SYMBOLS = [
     "fg_comm_unique_id", "fg_comm_init", "fg_comm_destroy", "fg_device_alloc", "fg_device_free", "fg_device_download", "fg_device_upload",
     "fg_dsl_compile", "fg_dsl_warning_count", "fg_dsl_warning",
     "fg_vi_config_default", "fg_vi_elbo_batch", "fg_vi_optimize", "fg_vi_estimate_elbo",
+    "fg_diag_stream_new", "fg_diag_stream_update", "fg_diag_stream_count", "fg_diag_stream_moments", "fg_diag_stream_autocov_sums",
+    "fg_diag_stream_rhat_ess", "fg_diag_stream_free",
 ]
 
 _lib = None
@@ -206,6 +208,14 @@ def lib():
     L.fg_diag_set_exchange.argtypes = [vp, C.c_int]
     L.fg_diag_exchange_bytes.restype = C.c_int64
     L.fg_diag_exchange_bytes.argtypes = [vp]
+    L.fg_diag_stream_new.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.fg_diag_stream_update.argtypes = [vp, vp, C.c_int]
+    L.fg_diag_stream_count.argtypes = [vp]
+    L.fg_diag_stream_moments.argtypes = [vp, vp]
+    L.fg_diag_stream_autocov_sums.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.fg_diag_stream_rhat_ess.argtypes = [vp, vp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
+    L.fg_diag_stream_free.restype = None
+    L.fg_diag_stream_free.argtypes = [vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
     L.fg_mh_last_kernel.restype = C.c_char_p
@@ -705,6 +715,11 @@ class Engine:
         _check(lib().fg_diag_quantiles(self.h, d_draws, int(n), int(d), comm, _dp(pr), len(pr), _dp(out)))
         return out
 
+    def diag_stream(self, n_total: int, d: int, max_lag: int = 64) -> "DiagStream":
+        """A `fg_diag_stream`: the figures of `diag_rhat_ess` for `n_total` draws of `d` coordinates that arrive one chunk at a time
+        and are never stored; `max_lag` (rounded up to a multiple of 32, at most 2 048) is the deepest lag Geyer's sequence may reach."""
+        return DiagStream(self, n_total, d, max_lag)
+
     def hmc_last_kernel(self) -> str:
         """Kernel (and waves per tile) the engine's last HMC launch ran."""
         return (lib().fg_hmc_last_kernel(self.h) or b"").decode()
@@ -732,6 +747,89 @@ class Engine:
         out = np.zeros(shape, dtype=dtype)
         _check(lib().fg_device_download(self.h, out.ctypes.data, ptr, out.nbytes))
         return out
+
+    def upload(self, array: np.ndarray, ptr: Optional[int] = None) -> int:
+        """Copy a host array into device memory (`ptr`, or a fresh `device_alloc` of its size); returns the device pointer."""
+        a = np.ascontiguousarray(array)
+        if ptr is None:
+            ptr = self.device_alloc(max(1, a.nbytes))
+        _check(lib().fg_device_upload(self.h, ptr, a.ctypes.data, a.nbytes))
+        return ptr
+
+
+class DiagStream:
+    """`fg_diag_stream` (fg_diag_stream.hip): split R-hat, multi-chain ESS and the pooled mean / std of a run handed over in chunks.
+    Constant memory per (coordinate, chain): (3 K + 7) doubles, K = `max_lag` rounded up to a multiple of 32.  Close it before its
+    engine."""
+
+    def __init__(self, engine: Engine, n_total: int, d: int, max_lag: int = 64):
+        for name, v in (("n_total", n_total), ("d", d), ("max_lag", max_lag)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        if n_total < 1:
+            raise ValueError("n_total must be at least 1")
+        if not 1 <= d <= 65535:
+            raise ValueError("d must lie in [1, 65535]")
+        if not 1 <= max_lag <= 2048:
+            raise ValueError("max_lag must lie in [1, 2048]")
+        self.engine, self.n, self.d = engine, int(n_total), int(d)
+        self.K = (int(max_lag) + 31) // 32 * 32
+        self.h = None
+        out = C.c_void_p()
+        _check(lib().fg_diag_stream_new(engine.h, self.n, self.d, int(max_lag), C.byref(out)))
+        self.h = out.value
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the stream is closed")
+        return self.h
+
+    def update(self, d_draws: int, n_chunk: int):
+        """The next `n_chunk` draws, a device buffer [n_chunk][d][C]."""
+        _check(lib().fg_diag_stream_update(self._handle(), d_draws, int(n_chunk)))
+
+    @property
+    def count(self) -> int:
+        return int(lib().fg_diag_stream_count(self._handle()))
+
+    def moments(self) -> np.ndarray:
+        """[d][6][C] as `Engine.diag_chain_moments` gives for a stored buffer."""
+        eng = self.engine
+        d_mom = eng.device_alloc(max(1, self.d * 6 * eng.C) * 8)
+        try:
+            _check(lib().fg_diag_stream_moments(self._handle(), d_mom))
+            return eng.download(d_mom, (self.d, 6, eng.C))
+        finally:
+            eng.device_free(d_mom)
+
+    def autocov_sums(self, lag0: int, n_lags: int) -> np.ndarray:
+        out = np.zeros((self.d, int(n_lags)))
+        _check(lib().fg_diag_stream_autocov_sums(self._handle(), int(lag0), int(n_lags), _dp(out)))
+        return out
+
+    def rhat_ess(self, comm: Optional[int] = None, exchange: Optional[int] = None, want_ess: bool = True):
+        """As `Engine.diag_rhat_ess`.  An ESS whose Geyer sequence runs past the stream's K lags raises EngineError (FG_E_LIMIT);
+        `want_ess=False` asks for no lag and returns R-hat / mean / std alone (ess = None)."""
+        d = self.d
+        rhat, ess, mean, std = (np.zeros(d) for _ in range(4))
+        tot = C.c_int64()
+        if exchange is not None:
+            _check(lib().fg_diag_set_exchange(self.engine.h, int(exchange)))
+        _check(lib().fg_diag_stream_rhat_ess(self._handle(), comm, _dp(rhat), _dp(ess) if want_ess else None, _dp(mean), _dp(std), C.byref(tot)))
+        return dict(r_hat=rhat, ess=ess if want_ess else None, mean=mean, std=std, chains=tot.value,
+                    exchange_bytes=int(lib().fg_diag_exchange_bytes(self.engine.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
+                lib().fg_diag_stream_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---- population-wide device primitives (no program needed) -----------------------------------

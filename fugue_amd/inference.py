@@ -4,6 +4,7 @@
     adaptive_mcmc_chain(seed, model_fn, n_samples, n_warmup, n_chains)        mh.rs:921-944
     adaptive_mcmc_chain_with_overrides(..., overrides)                        mh.rs:946-1014
     adaptive_smc(seed, num_particles, model_fn, config)                       smc.rs:455-581
+    hmc_chain_summary / adaptive_mcmc_chain_summary                           the same runs, summarised in chunks (ChainSummary)
 
 `model_fn` is what the reference passes (`Fn() -> Model<A>`): here a zero-argument callable returning a
 `fugue_amd.model.Model`, or an already traced `Program`.  The reference threads `&mut R`; the engine's RNG is
@@ -130,9 +131,7 @@ def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Option
     return out
 
 
-def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_warmup: int, overrides: Sequence[Tuple[str, SiteProposal]],
-                                       n_chains: int = 1, device: int = 0) -> ChainBatch:
-    cp = _compile(model_fn)
+def _override_rows(cp, overrides):
     ov = None
     if overrides:
         ov = [None] * cp.S
@@ -140,6 +139,13 @@ def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_wa
             if a not in cp.site_names:
                 raise M.FugueError(f"address not found: {a}", M.ErrorCode.TraceAddressNotFound)
             ov[cp.site_names.index(a)] = (p.kind, p.lower, p.upper)
+    return ov
+
+
+def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_warmup: int, overrides: Sequence[Tuple[str, SiteProposal]],
+                                       n_chains: int = 1, device: int = 0) -> ChainBatch:
+    cp = _compile(model_fn)
+    ov = _override_rows(cp, overrides)
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     rec = list(range(cp.S))
     buf = eng.device_alloc(max(1, n_samples * cp.S * n_chains) * 8)
@@ -153,6 +159,98 @@ def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_wa
 
 def adaptive_mcmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1, device: int = 0) -> ChainBatch:
     return adaptive_mcmc_chain_with_overrides(seed, model_fn, n_samples, n_warmup, (), n_chains, device)
+
+
+@dataclass
+class ChainSummary:
+    """What `summarize_f64_parameter` (diagnostics.rs:320-392) reports for every f64 site of a run whose draws were never stored:
+    pooled mean / std, split R-hat, multi-chain ESS, each [n_sites] in the order of `sites`.  No quantiles: selecting them takes
+    eight passes over draws that no longer exist."""
+    sites: List[str]
+    mean: np.ndarray
+    std: np.ndarray
+    r_hat: np.ndarray
+    ess: np.ndarray
+    n_samples: int
+    n_chains: int
+    accept_rate: float = 0.0
+    mean_step_size: float = float("nan")
+    n_divergent: int = 0
+
+
+def _summary_args(n_samples: int, chunk: int, max_lag: int):
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1")
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    if not 1 <= max_lag <= 2048:
+        raise ValueError("max_lag must lie in [1, 2048]")
+
+
+def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int):
+    """step(n, buf) records n draws [n][d][C] into buf; one chunk buffer is alive at a time."""
+    chunk = min(chunk, n_samples)
+    stream = eng.diag_stream(n_samples, d, max_lag)
+    buf = eng.device_alloc(chunk * d * eng.C * 8)
+    try:
+        done = 0
+        while done < n_samples:
+            n = min(chunk, n_samples - done)
+            step(n, buf)
+            stream.update(buf, n)
+            done += n
+        r = stream.rhat_ess()
+    finally:
+        eng.synchronize()
+        eng.device_free(buf)
+        stream.close()
+    return ChainSummary(list(sites), r["mean"], r["std"], r["r_hat"], r["ess"], n_samples, int(r["chains"]))
+
+
+def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
+                      chunk: int = 64, max_lag: int = 64, device: int = 0) -> ChainSummary:
+    """`hmc_chain` for runs longer than memory: the same transitions (`fg_hmc_step` is incremental), `chunk` at a time into one
+    draw buffer that a diagnostics stream consumes, and the summary of every f64 site instead of the draws.  `max_lag` bounds how
+    far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  Quantiles are out of scope: radix select
+    needs eight passes over the draws."""
+    _summary_args(n_samples, chunk, max_lag)
+    cp = _compile(model_fn)
+    if cp.d == 0:
+        raise ValueError("hmc_chain_summary: the model has no f64 site to summarise")
+    cfg = config or HMCConfig()
+    eng = E.Engine(cp, n_chains, seed=seed, device=device)
+    try:
+        eng.hmc_init(cfg.raw(), n_warmup)
+        eng.hmc_step(n_warmup)
+        out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag)
+        st = eng.hmc_stats()
+        out.accept_rate, out.mean_step_size, out.n_divergent = st.accept_rate, st.mean_step_size, int(st.n_divergent)
+    finally:
+        eng.close()
+    return out
+
+
+def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1,
+                                overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
+                                device: int = 0) -> ChainSummary:
+    """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
+    only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  Quantiles are out of scope
+    (see `hmc_chain_summary`)."""
+    _summary_args(n_samples, chunk, max_lag)
+    cp = _compile(model_fn)
+    rec = list(cp.f64_sites)
+    if not rec:
+        raise ValueError("adaptive_mcmc_chain_summary: the model has no f64 site to summarise")
+    ov = _override_rows(cp, overrides)
+    eng = E.Engine(cp, n_chains, seed=seed, device=device)
+    try:
+        eng.mh_init(n_warmup, ov)
+        eng.mh_step(n_warmup)
+        out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in rec], len(rec), n_samples, chunk, max_lag)
+        out.accept_rate = eng.mh_stats().accept_rate
+    finally:
+        eng.close()
+    return out
 
 
 def adaptive_smc(seed: int, num_particles: int, model_fn, config: Optional[SMCConfig] = None, device: int = 0) -> SMCResult:

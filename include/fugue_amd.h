@@ -430,6 +430,31 @@ int fg_diag_combine(const double *h_moments, int64_t m, int n, int d, fg_acov_fn
 typedef int (*fg_reduce_fn)(void *user, int stage, const double *h_in, double *h_out);
 int fg_diag_combine_reduced(int64_t m, int n, int d, fg_reduce_fn reduce, fg_acov_fn acov, void *user, double *h_rhat,
                             double *h_ess, double *h_mean, double *h_std);
+/* ------------------------------------------------------------------ diagnostics without stored draws
+ * The figures of fg_diag_rhat_ess -- r_hat_f64 (diagnostics.rs:218-224,240-304), effective_sample_size_multichain
+ * (mcmc_utils.rs:214-339), the pooled mean / std of summarize_f64_parameter (diagnostics.rs:331-352) -- for a run that is handed
+ * over one chunk of draws at a time and never stored.  Per (coordinate, chain) the stream keeps (3 K + 7) doubles, K = max_lag
+ * rounded up to a multiple of 32 (at most 2 048, the reference's lag cap, mcmc_utils.rs:266): in-order sums about the column's
+ * first draw, so the result does not depend on where the chunk boundaries fall.  Quantiles need the draws and are not offered. */
+typedef struct fg_diag_stream fg_diag_stream;
+/* FG_E_BAD_ARG: n_total < 1, d outside [1, 65535], max_lag outside [1, 2048].  The stream must be freed before its engine. */
+int  fg_diag_stream_new(fg_engine *e, int n_total, int d, int max_lag, fg_diag_stream **out);
+/* The next n_chunk draws d_draws [n_chunk][d][C] (e.g. what fg_hmc_step / fg_mh_step just recorded); asynchronous on the engine's
+ * stream.  FG_E_STATE when the chunk would pass n_total. */
+int  fg_diag_stream_update(fg_diag_stream *s, const double *d_draws, int n_chunk);
+int  fg_diag_stream_count(const fg_diag_stream *s);                       /* draws taken so far */
+/* The read-outs below are FG_E_STATE before n_total draws have arrived.  d_moments [d][6][C] as fg_diag_chain_moments
+ * (split_f64_chains, diagnostics.rs:240-253: the middle draw dropped when n_total is odd). */
+int  fg_diag_stream_moments(fg_diag_stream *s, double *d_moments);
+/* h_sums [d][n_lags] as fg_diag_autocov_sums (autocovariances, mcmc_utils.rs:231-244); lags >= n_total are 0, a lag >= K below
+ * n_total is FG_E_LIMIT. */
+int  fg_diag_stream_autocov_sums(fg_diag_stream *s, int lag0, int n_lags, double *h_sums);
+/* fg_diag_rhat_ess over the stream: the same combination (ess_from_chains, mcmc_utils.rs:253-339; r_hat_from_f64_chains,
+ * diagnostics.rs:262-304), exchange mode and communicator.  FG_E_LIMIT when Geyer's sequence asks for a lag >= K: a figure is never
+ * computed from missing lags; with h_ess == NULL no lag is asked for.  K >= min(n_total - 1, 2048) never hits the limit. */
+int  fg_diag_stream_rhat_ess(fg_diag_stream *s, void *rccl_comm, double *h_rhat, double *h_ess, double *h_mean,
+                             double *h_std, int64_t *out_total_chains);
+void fg_diag_stream_free(fg_diag_stream *s);
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

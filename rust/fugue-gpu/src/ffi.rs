@@ -6,6 +6,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)] pub struct fg_program { _p: [u8; 0] }
 #[repr(C)] pub struct fg_engine { _p: [u8; 0] }
+#[repr(C)] pub struct fg_diag_stream { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -135,6 +136,15 @@ extern "C" {
     pub fn fg_diag_quantiles(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, rccl_comm: *mut c_void, h_probs: *const f64, n_probs: c_int,
                              h_out: *mut f64) -> c_int;
     pub fn fg_diag_set_exchange(e: *mut fg_engine, mode: c_int) -> c_int;
+    // ---- the same figures without stored draws, one chunk at a time (fg_diag_stream.hip)
+    pub fn fg_diag_stream_new(e: *mut fg_engine, n_total: c_int, d: c_int, max_lag: c_int, out: *mut *mut fg_diag_stream) -> c_int;
+    pub fn fg_diag_stream_update(s: *mut fg_diag_stream, d_draws: *const f64, n_chunk: c_int) -> c_int;
+    pub fn fg_diag_stream_count(s: *const fg_diag_stream) -> c_int;
+    pub fn fg_diag_stream_moments(s: *mut fg_diag_stream, d_moments: *mut f64) -> c_int;
+    pub fn fg_diag_stream_autocov_sums(s: *mut fg_diag_stream, lag0: c_int, n_lags: c_int, h_sums: *mut f64) -> c_int;
+    pub fn fg_diag_stream_rhat_ess(s: *mut fg_diag_stream, rccl_comm: *mut c_void, h_rhat: *mut f64, h_ess: *mut f64, h_mean: *mut f64,
+                                   h_std: *mut f64, out_total_chains: *mut i64) -> c_int;
+    pub fn fg_diag_stream_free(s: *mut fg_diag_stream);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
