@@ -11,6 +11,7 @@
 // One block = one wave of 64 chains; the wave's working set (site values + expression
 // temporaries + momentum) is a [(n_slots + d)][64] tile of doubles in LDS.
 #include "fg_engine_internal.h"
+#include "fg_hmc_sep_plan.h"
 #include "fg_gradstream.h"
 #include "fg_cold.h"
 
@@ -811,7 +812,7 @@ void fg_engine_free(fg_engine *e) {
     if (e->jit_mh_mod) (void)hipModuleUnload(e->jit_mh_mod);
     if (e->mhmw.unit.mod) (void)hipModuleUnload(e->mhmw.unit.mod);
     if (e->mhmw.unit_ns.mod) (void)hipModuleUnload(e->mhmw.unit_ns.mod);
-    void *ptrs[] = { e->mhmw.d_catu_c, e->mhmw.d_catu, e->d_jit_tab, e->d_jit_mh_tab, e->mhmw.unit.d_tab, e->mhmw.unit_ns.d_tab, e->d_mhi_acc, e->d_mhi_site_ins, e->d_mwi_order, e->d_mwi_prof, e->d_gtile, e->d_lin_tab, e->d_lin_meta, e->mhmw.d_srt, e->d_sep, e->d_sep_coord, e->d_sep_free, e->d_site_rec, e->d_sobs, e->d_ins, e->d_ins_fast, e->d_coord, e->d_gstream, e->d_sstream, e->d_sub, e->d_sub_off, e->d_f64_slot, e->d_site_slot, e->d_vtype, e->d_site_cat, e->d_pool, e->d_values, e->d_acc, e->d_logp,
+    void *ptrs[] = { e->mhmw.d_catu_c, e->mhmw.d_catu, e->d_jit_tab, e->d_jit_mh_tab, e->mhmw.unit.d_tab, e->mhmw.unit_ns.d_tab, e->d_mhi_acc, e->d_mhi_site_ins, e->hsplit.d_mwi_order, e->hsplit.d_mwi_prof, e->d_gtile, e->d_lin_tab, e->d_lin_meta, e->mhmw.d_srt, e->d_sep, e->d_sep_coord, e->d_sep_free, e->d_site_rec, e->d_sobs, e->d_ins, e->d_ins_fast, e->d_coord, e->d_gstream, e->d_sstream, e->d_sub, e->d_sub_off, e->d_f64_slot, e->d_site_slot, e->d_vtype, e->d_site_cat, e->d_pool, e->d_values, e->d_acc, e->d_logp,
                      e->d_tmp, e->d_itmp };
     for (void *q : ptrs) if (q) hipFree(q);
     if (e->stream && e->own_stream) hipStreamDestroy(e->stream);
@@ -950,25 +951,14 @@ void fg_internal_hmc_set_cfg(fg_engine *e, const fg_hmc_config *cfg) {
     e->H.grad_mode = cfg->grad_mode;
 }
 
-// does fg_hmc_step run this program through the kernel compiled at run time (hmc_launch_steps' order: independent sites, dense regressions,
-// then the compiled form where it is the faster one, the stream kernel, the compiled form, the interpreter)?
-static bool hmc_jit_preferred(const fg_engine *e) {
-    if (e->cfg.grad_mode != FG_GRAD_FD_SPARSE || e->jit_state < 0) return false;
-    if (!e->P.gstream) return true;
-    if (e->gt || e->tw != FG_WAVE) return false;
-    if (e->P.sep && !e->sep_disabled && e->d >= 1) return false;                                     // fg_hmc_sep_launch takes it
-    if (e->P.lin_tab && !e->lin_disabled && e->d >= 2 && e->d <= 64) return false;   // fg_hmc_lin_launch takes it
-    // Every other gradient-stream program, at every chain count.  Round 3 sent only linear-predictor / general / option-select records here, round 4 first
-    // added programs of fewer than eight coordinates and launches of two tiles per CU or fewer (the stream kernel kept 16 % on reference_model(8) at
-    // 65 536 chains).  Since the unit holds its task split as straight-line code per wave (fg_jit_wave_tasks: no task list in memory, no dispatch on the
-    // coordinate, short sub-programs inlined) it wins everywhere measured -- reference_model(8) 1.85e10 -> 2.26e10 leapfrog-steps/s at 65 536 chains,
-    // 2.48e10 -> 2.57e10 at 524 288; reference_model(20) 8.4e9 -> 1.07e10; reference_model(32) 4.5e9 -> 7.2e9 (profiles/round4_jit_vs_stream_tasks.txt).
-    // FG_JIT=0 keeps k_hmc_stream_steps (bit-identity tests, a box without hiprtc).
-    return true;
+// does fg_hmc_step run this program through the kernel compiled at run time ahead of the stream kernel (fg_hmc_jit_first, fg_hmc_split_plan.h)?
+static bool hmc_jit_first(const fg_engine *e) {
+    const FgJitFirstIn in = { e->cfg.grad_mode, e->jit_state, e->P.gstream != nullptr, e->gt, e->tw, fg_hmc_sep_gate(e->gt, e->P.sep != nullptr, e->sep_disabled, e->d), fg_hmc_lin_gate(e) };
+    return fg_hmc_jit_first(in);
 }
 
 static int hmc_find_eps(fg_engine *e, uint32_t instance, int injected, double *d_eps_out) {
-    if (hmc_jit_preferred(e)) {                              // the step-size search on the compiled kernel too (k_hmc_jit_find_eps)
+    if (hmc_jit_first(e)) {                                  // the step-size search on the compiled kernel too (k_hmc_jit_find_eps)
         const int rc = fg_hmc_jit_find_eps(e, instance, injected, d_eps_out);
         if (rc != FG_E_UNSUPPORTED) return rc;
     }
@@ -1035,7 +1025,6 @@ int fg_hmc_init(fg_engine *e, const fg_hmc_config *cfg, int n_warmup) {
 static int hmc_launch_steps(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t,
                             double *pos_all = nullptr, double *info = nullptr) {
     const unsigned tiles = (unsigned)((e->C + e->tw - 1) / e->tw);
-    const bool dense_stream = e->cfg.grad_mode == FG_GRAD_FD_DENSE && e->P.sstream != nullptr && e->P.sstream_kinds == 0;
     const bool analytic = e->cfg.grad_mode == FG_GRAD_ANALYTIC;
     if (analytic && e->an_jit) {                              // the analytic gradient of a program without closed-form records: the compiled unit
         const int rc = fg_hmc_jit_launch(e, iter0, n, welford_on, draws, first_sample_t, pos_all, info);
@@ -1050,74 +1039,39 @@ static int hmc_launch_steps(fg_engine *e, int iter0, int n, int welford_on, doub
         const int rc = fg_hmc_lin_launch(e, iter0, n, welford_on, draws, first_sample_t, pos_all, info);
         if (rc != FG_E_UNSUPPORTED) return rc;
     }
-    if (e->cfg.grad_mode == FG_GRAD_FD_SPARSE && e->P.gstream && e->jit_state >= 0) {
+    if (e->P.gstream && (e->cfg.grad_mode == FG_GRAD_FD_DENSE || hmc_jit_first(e))) {
         // Gradient-stream programs: the program compiled at run time (fg_jit.cpp) is faster than the stream kernel wherever records are more
         // than fast Normals (linear predictors, general distributions, option selects: hier_scale 1.2e9 -> 3.7e9, linreg 2.8e9 -> 2.0e10
         // leapfrog-steps/s, bit-identical -- tools/bench_jit_vs_stream.py), and for fast-Normal programs when the tiles do not fill the GPU
         // (reference_model(8) at 8 192 chains: 3.6e9 -> 6.2e9; at 65 536 chains the stream kernel keeps 13 %).  FG_JIT=2 forces it.
-        if (hmc_jit_preferred(e)) {
-            const int rc = fg_hmc_jit_launch(e, iter0, n, welford_on, draws, first_sample_t, pos_all, info);
-            if (rc != FG_E_UNSUPPORTED) return rc;
-        }
-    }
-    if (e->cfg.grad_mode == FG_GRAD_FD_DENSE && e->P.gstream && e->jit_state >= 0) {
-        // The dense mode of gradient-stream programs: the whole program per (coordinate, sign) as generated code (fg_jit_full_k) beats the dense
+        // Their dense mode: the whole program per (coordinate, sign) as generated code (fg_jit_full_k) beats the dense
         // stream at every size measured (reference_model(32) 3.6e8 -> 7.6e8 leapfrog-steps/s, reference_model(8) 4.6e9 -> 8.9e9, hier 2.6e9 ->
         // 5.5e9; at 8 192 chains 1.7e8 -> 3.7e8, 1.1e9 -> 3.6e9, 4.4e8 -> 2.5e9: profiles/round4_jit_dense.txt), bit-identical; FG_JIT=0 (or
         // a program whose d copies are too much to compile) keeps the dense stream / the interpreter kernels.
         const int rc = fg_hmc_jit_launch(e, iter0, n, welford_on, draws, first_sample_t, pos_all, info);
         if (rc != FG_E_UNSUPPORTED) return rc;
     }
-    if ((((e->cfg.grad_mode == FG_GRAD_FD_SPARSE || analytic) && e->P.gstream) || dense_stream) && e->tw == FG_WAVE && !e->gt) {
-        // waves per tile: aim at 4 waves per SIMD (16 per CU, see k_hmc_stream_steps).  The LDS tile caps the tiles
-        // resident on a CU (160 KB / lds_bytes -- 4 for the 32-site model), so the waves have to come from sharing
-        // a tile, whatever the chain count; each wave should still own at least 2 coordinates
-        int W = e->mw_override > 0 ? std::min(e->mw_override, FG_MW_MAX) : 1;
-        if (e->mw_override <= 0) {
-            const long long n_cu = std::max(1, e->n_simd / 4);
-            const long long resident = std::max(1LL, std::min<long long>((160 * 1024) / (long long)e->lds_bytes, ((long long)tiles + n_cu - 1) / n_cu));
-            while (W < FG_MW_MAX && resident * W < 16 && e->d >= 4 * W) W *= 2;
-        }
-        FgSeg seg;
-        const std::vector<FgGradRec> &gs = e->prog->gstream;
-        const int nrec = e->prog->n_gstream;
-        std::vector<int> cstart(e->d + 1, nrec);                 // first record of each coordinate
-        for (int k = nrec - 1; k >= 0; --k) cstart[gs[k].coord] = k;
-        std::vector<long long> cum(nrec + 1, 0);                 // work before record k: a linear predictor costs its terms
-        for (int k = 0; k < nrec; ++k) cum[k + 1] = cum[k] + ((gs[k].flags & FG_G_LIN) ? 1 + gs[k].maskm / 2 : 1);
-        for (int w = 0; w <= FG_MW_MAX; ++w) { seg.c[w] = e->d; seg.g[w] = nrec; }
-        seg.c[0] = 0; seg.g[0] = 0;
-        for (int w = 1, k = 0; w < W; ++w) {
-            if (dense_stream) { seg.c[w] = (int)((long long)e->d * w / W); seg.g[w] = 0; continue; }   // every coordinate costs one whole-program pass
-            const long long target = cum[nrec] * w / W;           // cut at the coordinate boundary nearest to w/W of the work
-            while (k < e->d && cum[cstart[k]] < target) ++k;
-            seg.c[w] = k; seg.g[w] = cstart[k];
-        }
-        // do the waves interact inside a trajectory?  Not when every record only reads coordinates of its own wave.
-        seg.separable = 1;
-        for (int w = 0; w < W && !dense_stream; ++w)
-            for (int k = seg.g[w]; k < seg.g[w + 1]; ++k) {
-                const FgGradRec &r = gs[k];
-                const bool x_ok = (r.flags & FG_G_X_CONST) || ((int)r.xi >= seg.c[w] && (int)r.xi < seg.c[w + 1]);
-                const bool m_ok = (r.flags & FG_G_M_CONST) || ((int)r.mi >= seg.c[w] && (int)r.mi < seg.c[w + 1]);
-                if (!x_ok || !m_ok || (r.flags & FG_G_LIN)) seg.separable = 0;   // a linear predictor reads many coordinates
-            }
-        int rk = e->P.sstream_kinds;                             // record kinds present in either stream
-        for (int k = 0; k < nrec && rk < 2; ++k) rk = std::max(rk, (gs[k].flags & FG_G_GEN) ? 2 : ((gs[k].flags & FG_G_LIN) ? 1 : 0));
-        using FgStreamKernel = void (*)(FgProgramDev, FgChainCtx, FgHmcDev, FgSeg, int, int, int, int, double *, int, double *, double *);
-        struct FgStreamVariant { int rk; bool an, ss; FgStreamKernel fn; unsigned long long raised; };       // record kinds, analytic gradient, the program has a score stream
+    {   // the gradient-stream kernel: plan (fg_hmc_stream_plan), look up, launch, name
+        const FgStreamPlanIn in = { e->d, tiles, e->n_simd, e->lds_bytes, e->mw_override, e->tw, e->gt, e->P.gstream ? e->prog->gstream.data() : nullptr, e->P.gstream ? e->prog->n_gstream : 0,
+                                    e->P.sstream_kinds, e->P.sstream != nullptr, e->cfg.grad_mode };
+        FgStreamPlan pl;
+        if (fg_hmc_stream_plan(in, &pl) == FG_OK) {
+            FgSeg seg;
+            for (int w = 0; w <= FG_MW_MAX; ++w) { seg.c[w] = pl.c[w]; seg.g[w] = pl.g[w]; }
+            seg.separable = pl.separable;
+            using FgStreamKernel = void (*)(FgProgramDev, FgChainCtx, FgHmcDev, FgSeg, int, int, int, int, double *, int, double *, double *);
+            struct FgStreamVariant { int rk; bool an, ss; FgStreamKernel fn; unsigned long long raised; };       // record kinds, analytic gradient, the program has a score stream
 #define FG_STREAM_ENTRIES(SS) { 0, false, SS, k_hmc_stream_steps<0, false, SS> }, { 1, false, SS, k_hmc_stream_steps<1, false, SS> }, { 2, false, SS, k_hmc_stream_steps<2, false, SS> }, \
                               { 0, true, SS, k_hmc_stream_steps<0, true, SS> }, { 1, true, SS, k_hmc_stream_steps<1, true, SS> }
-        static FgStreamVariant variants[] = { FG_STREAM_ENTRIES(true), FG_STREAM_ENTRIES(false) };
+            static FgStreamVariant variants[] = { FG_STREAM_ENTRIES(true), FG_STREAM_ENTRIES(false) };
 #undef FG_STREAM_ENTRIES
-        const bool ss = e->P.sstream != nullptr;
-        if (analytic && rk == 2) rk = 0;                         // (the analytic gradient has no general-record instantiation: such a launch has always taken the plain one)
-        FgStreamVariant *v = std::find_if(std::begin(variants), std::end(variants), [&](const FgStreamVariant &q) { return q.rk == rk && q.an == analytic && q.ss == ss; });
-        if (v == std::end(variants)) return FG_E_UNSUPPORTED;
-        const int rc = fg_launch(e, v->fn, v->raised, dim3(tiles), dim3(FG_WAVE * W), e->lds_bytes, e->P, e->X, e->H, seg, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
-        if (rc != FG_OK) return rc;
-        e->last_hmc_kernel = std::string(dense_stream ? "k_hmc_stream_steps (dense stream) W=" : "k_hmc_stream_steps W=") + std::to_string(W);
-        return FG_OK;
+            FgStreamVariant *v = std::find_if(std::begin(variants), std::end(variants), [&](const FgStreamVariant &q) { return q.rk == pl.rk && q.an == pl.analytic && q.ss == pl.ss; });
+            if (v == std::end(variants)) return FG_E_UNSUPPORTED;
+            const int rc = fg_launch(e, v->fn, v->raised, dim3(tiles), dim3(FG_WAVE * pl.W), e->lds_bytes, e->P, e->X, e->H, seg, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
+            if (rc != FG_OK) return rc;
+            e->last_hmc_kernel = pl.name;
+            return FG_OK;
+        }
     }
     {   // programs without a record stream, compiled at run time (fg_jit.cpp)
         const int rc = fg_hmc_jit_launch(e, iter0, n, welford_on, draws, first_sample_t, pos_all, info);

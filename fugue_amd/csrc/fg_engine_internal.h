@@ -14,6 +14,7 @@
 #include "fg_interp.h"
 #include "fg_program.h"
 #include "fg_dev_types.h"
+#include "fg_hmc_split_plan.h"
 
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
     fg_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return FG_E_HIP; } } while (0)
@@ -33,6 +34,15 @@ struct FgMhMwState {
     int ncu = -1, catu_same = 0; double catu_c0 = 0.0; double *d_catu_c = nullptr; void *d_catu = nullptr;   // row-less uniform Categorical terms (FgMhSeg; -1: not decided)
     int baked[7] = {0, 0, 0, 0, 0, 0, 0}; bool has_baked = false;   // the launch shape the unit was generated for (FgMhJitSpec::baked)
     FgMhMwUnit unit, unit_ns;    // of a program with a score stream, phase B generated / of a program without one
+};
+
+// The wave-split HMC launchers' once-per-engine state (fg_hmc_interp.hip): the split made at the first launch of a key (fg_hmc_split_plan.h) and
+// its device copy, shared by the interpreter kernel and the unit compiled at run time; the splits that unit was generated behind.
+enum FgSplitKey { FG_SPLIT_NONE = -1, FG_SPLIT_INTERP_DENSE, FG_SPLIT_INTERP_SPARSE, FG_SPLIT_JIT_SPARSE /* and FG_GRAD_ANALYTIC: off_an */, FG_SPLIT_JIT_DENSE };
+struct FgHmcSplitState {
+    FgSplitKey key = FG_SPLIT_NONE; FgTaskSplit split; std::vector<long long> cost;   // whose split is cached, the split, the per-coordinate costs it was dealt by
+    FgTaskSplit gen_sparse, gen_dense;   // what the compiled unit holds as straight-line code (W = 0: nothing -- FG_JIT_TASKS=0, or no unit yet)
+    int *d_mwi_order = nullptr; long long *d_mwi_prof = nullptr; int mwi_calibrated = 0;   // split.order on the device; FG_HMC_INTERP_DEBUG: cycles per task, 0 not clocked / 1 clocked / 2 printed
 };
 
 struct fg_engine {
@@ -91,8 +101,7 @@ struct fg_engine {
     long long diag_bytes = 0;  // bytes this rank put into collectives during the last fg_diag_rhat_ess
     std::string last_hmc_kernel;   // kernel (and waves per tile) the last fg_hmc_step launch ran (fg_hmc_last_kernel)
     bool interp_mw_disabled = false;   // FG_HMC_INTERP_MW=0: keep interpreter programs on the one-wave-per-tile HMC kernel (A/B tests)
-    std::vector<std::vector<int>> jit_baked_bins, jit_baked_cbins, jit_baked_cbins_dense; bool mwi_baked = false, mwi_fused = false;   // the task split the compiled HMC unit was generated behind; does the current split equal it
-    int *d_mwi_order = nullptr; long long *d_mwi_prof = nullptr; std::vector<int> mwi_off, mwi_off_an; std::vector<long long> mwi_cost; int mwi_W = 0, mwi_sparse = -1, mwi_calibrated = 0;   // coordinate split of k_hmc_interp_mw_steps (fg_hmc_interp.hip)
+    FgHmcSplitState hsplit;      // what the wave-split HMC launchers decide once per engine and gradient mode (fg_hmc_interp.hip)
     int mhi_W = 0, mhi_n_stmt = 0, mhi_occ = 2; bool mhi_setup_done = false; size_t mhi_lds = 0; std::vector<int> mhi_ins_off, mhi_stmt_off; unsigned char *d_mhi_acc = nullptr; int *d_mhi_site_ins = nullptr; std::vector<int> mhi_stmt_end; std::vector<unsigned char> mhi_acc_host;   // statement split of k_mh_interp_mw_steps (fg_mh_interp.hip)
     int jit_state = 0;           // run-time compiled HMC kernel of this program: 0 not tried, 1 loaded, -1 unavailable (fg_jit.cpp; FG_JIT=0 switches it off)
     hipModule_t jit_mod = nullptr; hipFunction_t jit_fn = nullptr, jit_fn_eps = nullptr, jit_fn_rejuv = nullptr, jit_fn_prior = nullptr, jit_fn_lj = nullptr; std::string jit_log; bool jit_lds_attr = false, jit_rejuv_attr = false, jit_has_ad = false, jit_has_dense = false, an_jit = false /* FG_GRAD_ANALYTIC runs on the compiled unit's derivative code */; double *d_jit_tab = nullptr, *d_jit_mh_tab = nullptr;   // the modules' constant tables (fg_jit_bind_tables)
@@ -181,6 +190,7 @@ bool fg_hmc_jit_has_ad(fg_engine *e);      // the compiled module holds the forw
 int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info);
 
 // fg_hmc_lin.hip: observation-major finite-difference gradient for dense regressions (FG_E_UNSUPPORTED: not applicable)
+bool fg_hmc_lin_gate(const fg_engine *e);   // the static part of what fg_hmc_lin_launch takes (hmc_jit_first asks too)
 int fg_hmc_lin_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info);
 
 // fg_hmc_interp.hip: the program compiled at run time (fg_jit.cpp) behind the same multi-wave kernel (FG_E_UNSUPPORTED: not applicable)

@@ -215,210 +215,71 @@ FG_MWI_KERNEL(4, false, k_hmc_interp_mw_steps_occ4)
 FG_MWI_KERNEL(2, true, k_hmc_interp_mw_steps_lds_occ2)
 FG_MWI_KERNEL(4, true, k_hmc_interp_mw_steps_lds_occ4)
 
-// cost of one interpreted instruction in the split (relative: an out-of-line density with its logs / lgammas against an add)
-static long long mwi_ins_cost(const FgIns &in) {
-    const uint32_t code = FG_INS_OPCODE(in.op);
-    if (code == FG_OP_NORMAL_FAST) return 3;
-    if (code < 17u) return (in.op & FG_F_HOISTED) ? 10 : 16;
-    switch (code) {
-    case FG_OP_EXP: case FG_OP_LN: case FG_OP_SIN: case FG_OP_COS: case FG_OP_TANH: return 6;
-    case FG_OP_POW: case FG_OP_RPOW: return 14;
-    case FG_OP_DIV: case FG_OP_RDIV: case FG_OP_SQRT: return 3;
-    case FG_OP_DOT: return 1 + (long long)in.opnd[1] / 2;
-    default: return 1;
-    }
-}
-
-// longest-processing-time split of the 2 d tasks (task 2 k + sign costs cost[k]) over W waves; returns the makespan.
-// plus_only: the "-" tasks cost nothing and are left out of the bins (FG_GRAD_ANALYTIC in the compiled kernel: one task per coordinate)
-static long long mwi_split(const std::vector<long long> &cost, int W, std::vector<std::vector<int>> *bins_out, bool plus_only = false) {
-    const int n_tasks = 2 * (int)cost.size();
-    std::vector<int> by;
-    for (int k = 0; k < n_tasks; ++k) if (!plus_only || !(k & 1)) by.push_back(k);
-    std::stable_sort(by.begin(), by.end(), [&](int a, int b) { return cost[a >> 1] > cost[b >> 1]; });
-    std::vector<std::vector<int>> bins(W);
-    std::vector<long long> load(W, 0);
-    for (int k : by) {
-        int best = 0;
-        for (int w = 1; w < W; ++w) if (load[w] < load[best]) best = w;
-        bins[best].push_back(k); load[best] += cost[k >> 1];
-    }
-    int lightest = 0;                                           // wave 0 also runs the endpoint score: it gets the lightest bin
-    for (int w = 1; w < W; ++w) if (load[w] < load[lightest]) lightest = w;
-    std::swap(bins[0], bins[lightest]);
-    if (bins_out) *bins_out = bins;
-    return *std::max_element(load.begin(), load.end());
-}
-
+// Plan (fg_hmc_split_plan.h: the split once per engine and gradient mode, the shape per launch), upload, launch, name.
 int fg_hmc_interp_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {
     if (e->interp_mw_disabled || e->gt || e->tw != FG_WAVE || e->d < 2) return FG_E_UNSUPPORTED;
     const unsigned tiles = (unsigned)((e->C + e->tw - 1) / e->tw);
     const bool sparse = e->cfg.grad_mode != FG_GRAD_FD_DENSE;
     for (int j = 0; j < e->S; ++j) if (e->prog->site_slot[j] >= e->S) return FG_E_UNSUPPORTED;    // site rows first, the private rows above them
     for (int k = 0; k < e->d; ++k) if (e->prog->coord[k].slot != k) return FG_E_UNSUPPORTED;
-    // the program in LDS (instruction fetch by ds_read_b32: -5 ... -10 % time) when that does not cost a resident tile: with two or more
-    // tiles per CU the workgroup must stay under half the LDS, a CU's only tile may take all of it
-    const size_t prog_bytes = (e->prog->sub.size() + e->prog->ins_fast.size()) * sizeof(FgIns);
-    const long long n_cu = std::max(1, e->n_simd / 4), per_cu = ((long long)tiles + n_cu - 1) / n_cu;
-    auto rows_for = [&](int W) { return (size_t)((long long)e->S + (long long)W * (e->n_slots - e->S + 1) + 3LL * e->d + 2 + W) * FG_WAVE * sizeof(double); };
-    auto lds_for = rows_for;
-    int occ = 4;                                               // measured (tools/bench_interp_mw.py): 128 VGPRs with the cold paths spilling beats 168 and 198 -- the waves hide more than the spills cost
-    if (const char *sp = std::getenv("FG_HMC_INTERP_OCC")) occ = std::atoi(sp) <= 2 ? 2 : 4;
-    const int wmax = 4 * occ;                                  // a workgroup's waves must fit one CU at that occupancy
-    const int wcap = std::min(wmax, 2 * e->d);
+    FgHmcSplitState &st = e->hsplit;
+    const FgTaskSwitches sw = fg_task_switches();
     const int n_tasks = 2 * e->d;
-    int forced = e->mw_override;
-    if (const char *sp = std::getenv("FG_HMC_INTERP_WAVES")) forced = std::atoi(sp);
-    if (!e->d_mwi_order) {
-        HIPCHK(hipMalloc((void **)&e->d_mwi_order, (size_t)2 * n_tasks * sizeof(int)));
-        HIPCHK(hipMalloc((void **)&e->d_mwi_prof, (size_t)n_tasks * sizeof(long long)));
-        HIPCHK(hipMemsetAsync(e->d_mwi_prof, 0, (size_t)n_tasks * sizeof(long long), e->stream));
+    if (!st.d_mwi_order) {
+        HIPCHK(hipMalloc((void **)&st.d_mwi_order, (size_t)2 * n_tasks * sizeof(int)));
+        HIPCHK(hipMalloc((void **)&st.d_mwi_prof, (size_t)n_tasks * sizeof(long long)));
+        HIPCHK(hipMemsetAsync(st.d_mwi_prof, 0, (size_t)n_tasks * sizeof(long long), e->stream));
     }
     const bool debug = std::getenv("FG_HMC_INTERP_DEBUG") != nullptr;
-    if (debug && e->mwi_calibrated == 1) {                      // FG_HMC_INTERP_DEBUG: the cycles the previous launch clocked per task, beside the static costs
+    if (debug && st.mwi_calibrated == 1) {                      // FG_HMC_INTERP_DEBUG: the cycles the previous launch clocked per task, beside the static costs
         std::vector<long long> prof(n_tasks, 0);
-        HIPCHK(hipMemcpyAsync(prof.data(), e->d_mwi_prof, (size_t)n_tasks * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(prof.data(), st.d_mwi_prof, (size_t)n_tasks * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
-        for (int k = 0; k < e->d; ++k) fprintf(stderr, "coord %d static %lld measured %lld %lld sub_n %d\n", k, e->mwi_cost[k], prof[2 * k], prof[2 * k + 1], e->prog->coord[k].sub_n);
-        e->mwi_calibrated = 2;
+        for (int k = 0; k < e->d; ++k) fprintf(stderr, "coord %d static %lld measured %lld %lld sub_n %d\n", k, st.cost[k], prof[2 * k], prof[2 * k + 1], e->prog->coord[k].sub_n);
+        st.mwi_calibrated = 2;
     }
-    if (e->mwi_sparse != (int)sparse || e->mwi_cost.empty() || e->mwi_W <= 0) {
-        // task costs: static weights per interpreted instruction (they track the measured cycles within ~30 %: FG_HMC_INTERP_DEBUG)
-        e->mwi_cost.assign(e->d, 1);
-        if (sparse)
-            for (int k = 0; k < e->d; ++k) {
-                long long cs = 0;
-                for (int q = 0; q < e->prog->coord[k].sub_n; ++q) cs += mwi_ins_cost(e->prog->sub[e->prog->coord[k].sub_off + q]);
-                e->mwi_cost[k] = std::max(1LL, cs);
-            }
-        // waves per tile: eight (two tiles fill a CU's sixteen wave slots, one tile still gives every SIMD two waves), a power of two
-        // (measured: 6 and 12 lose to 4 and 8 on every model), never more than the 2 d tasks
-        int W = 2;
-        if (forced > 0) W = std::max(2, std::min(forced, wcap));
-        else while (2 * W <= std::min(8, wcap) && lds_for(2 * W) <= 160 * 1024) W *= 2;
-        while (W > 1 && lds_for(W) > 160 * 1024) --W;
-        if (W < 2) return FG_E_UNSUPPORTED;
-        std::vector<std::vector<int>> bins;
-        mwi_split(e->mwi_cost, W, &bins);
-        std::vector<int> order;
-        e->mwi_off.assign(FG_MWI_MAX + 1, n_tasks);
-        for (int w = 0; w < W; ++w) {
-            e->mwi_off[w] = (int)order.size();
-            std::sort(bins[w].begin(), bins[w].end());
-            order.insert(order.end(), bins[w].begin(), bins[w].end());
-        }
-        HIPCHK(hipMemcpyAsync(e->d_mwi_order, order.data(), (size_t)n_tasks * sizeof(int), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));                // `order` is a local
-        e->mwi_W = W; e->mwi_sparse = (int)sparse; e->mwi_calibrated = 0;
+    const FgSplitKey key = sparse ? FG_SPLIT_INTERP_SPARSE : FG_SPLIT_INTERP_DENSE;
+    if (st.key != key) {
+        std::vector<long long> tcost;
+        st.cost.assign(e->d, 1);
+        if (sparse) fg_task_coord_costs(e->prog->coord.data(), e->d, e->prog->sub.data(), st.cost, tcost);
+        const FgMwiTaskIn in = { e->d, e->S, e->n_slots, e->mw_override, &st.cost, sw };
+        if (int rc = fg_mwi_task_plan(in, &st.split)) return rc;
+        HIPCHK(hipMemcpyAsync(st.d_mwi_order, st.split.order.data(), (size_t)n_tasks * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        st.key = key; st.mwi_calibrated = 0;
     }
-    const int W = e->mwi_W;
+    const int W = st.split.W;
     FgMwi seg;
-    for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = e->mwi_off[w];
-    seg.order = e->d_mwi_order;
-    seg.prof = (debug && e->mwi_calibrated == 0) ? e->d_mwi_prof : nullptr;
-    if (debug && e->mwi_calibrated == 0) e->mwi_calibrated = 1;
+    for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = st.split.off[w];
+    seg.order = st.d_mwi_order;
+    seg.prof = (debug && st.mwi_calibrated == 0) ? st.d_mwi_prof : nullptr;
+    if (debug && st.mwi_calibrated == 0) st.mwi_calibrated = 1;
     seg.n_sub_ins = (int)e->prog->sub.size(); seg.n_fast_ins = (int)e->prog->ins_fast.size();
-    bool pl = rows_for(W) + prog_bytes <= (size_t)(per_cu >= 2 ? 80 : 160) * 1024;
-    if (const char *sp = std::getenv("FG_HMC_INTERP_LDSPROG")) pl = std::atoi(sp) != 0 && rows_for(W) + prog_bytes <= 160 * 1024;
-    const size_t lds = rows_for(W) + (pl ? prog_bytes : 0);
-#define FG_MWI_LAUNCH(K) do { if (int rc = set_lds(K, lds)) return rc; \
-    hipLaunchKernelGGL(K, dim3(tiles), dim3(FG_WAVE * W), lds, e->stream, e->P, e->X, e->H, seg, iter0, n, e->n_warmup, welford_on, \
+    const FgMwiLaunchIn lin = { e->d, e->S, e->n_slots, W, (e->prog->sub.size() + e->prog->ins_fast.size()) * sizeof(FgIns), tiles, e->n_simd, sw };
+    const FgMwiLaunchShape sh = fg_mwi_launch_shape(lin);
+#define FG_MWI_LAUNCH(K) do { if (int rc = set_lds(K, sh.lds)) return rc; \
+    hipLaunchKernelGGL(K, dim3(tiles), dim3(FG_WAVE * W), sh.lds, e->stream, e->P, e->X, e->H, seg, iter0, n, e->n_warmup, welford_on, \
                        draws, first_sample_t, pos_all, info); } while (0)
-    if (pl) { if (occ == 4) FG_MWI_LAUNCH(k_hmc_interp_mw_steps_lds_occ4); else FG_MWI_LAUNCH(k_hmc_interp_mw_steps_lds_occ2); }
-    else { if (occ == 4) FG_MWI_LAUNCH(k_hmc_interp_mw_steps_occ4); else FG_MWI_LAUNCH(k_hmc_interp_mw_steps_occ2); }
+    if (sh.pl) { if (sh.occ == 4) FG_MWI_LAUNCH(k_hmc_interp_mw_steps_lds_occ4); else FG_MWI_LAUNCH(k_hmc_interp_mw_steps_lds_occ2); }
+    else { if (sh.occ == 4) FG_MWI_LAUNCH(k_hmc_interp_mw_steps_occ4); else FG_MWI_LAUNCH(k_hmc_interp_mw_steps_occ2); }
 #undef FG_MWI_LAUNCH
     HIPCHK(hipGetLastError());
-    e->last_hmc_kernel = "k_hmc_interp_mw_steps W=" + std::to_string(W) + (occ != 4 ? " occ=" + std::to_string(occ) : std::string()) + (pl ? std::string() : std::string(" (program in global memory)"));
+    e->last_hmc_kernel = sh.name;
     return FG_OK;
 }
 
 // ---- the same kernel around a model compiled at run time (fg_jit.cpp, fg_hmc_jit_body.h) --------------------------------------
 struct FgJitSeg { int off[FG_MWI_MAX + 1]; const int *order; int baked; };   // (fg_hmc_jit_body.h's)
 
-// waves per tile of the compiled HMC kernels and the split of the sparse finite difference's 2 d tasks over them -- a function of the engine alone
-// (program, chain count, FG_HMC_WAVES / FG_HMC_INTERP_WAVES / FG_HMC_JIT_OCC at the time): the unit is generated BEHIND it (fg_jit_wave_tasks)
-static int jit_sparse_split(fg_engine *e, unsigned tiles, std::vector<long long> &cost, std::vector<std::vector<int>> &bins, std::vector<std::vector<int>> *cbins = nullptr) {
-    const int n_tasks = 2 * e->d;
-    cost.assign(e->d, 1);
-    for (int k = 0; k < e->d; ++k) {
-        long long cs = 0;
-        for (int q = 0; q < e->prog->coord[k].sub_n; ++q) cs += mwi_ins_cost(e->prog->sub[e->prog->coord[k].sub_off + q]);
-        cost[k] = std::max(1LL, cs);
-    }
-    int forced = e->mw_override;
-    if (const char *sp = std::getenv("FG_HMC_INTERP_WAVES")) forced = std::atoi(sp);
-    int jocc = 4;
-    if (const char *oc = std::getenv("FG_HMC_JIT_OCC")) { const int o = std::atoi(oc); if (o >= 2 && o <= 4) jocc = o; }
-    const int wcap = std::min(std::min(FG_MWI_MAX, 4 * jocc), n_tasks);
-    int W = 1;
-    const long long n_cu = std::max(1, e->n_simd / 4);
-    if (forced > 0) W = std::max(1, std::min(forced, wcap));
-    else if ((long long)tiles <= n_cu) W = wcap;             // a CU has at most one tile: a wave per task (logistic regression, 8 192 chains: W = 6 beats 4 by 45 %)
-    else {
-        // several tiles per CU: sixteen waves per CU is all that is ever resident (128 VGPRs), so four tiles of four waves where the LDS holds four tiles and a tile has at most sixteen tasks --
-        // fewer, longer task lists per wave and half the waves at every barrier (reference_model(8) at 65 536 chains 2.32e10 -> 2.81e10 leapfrog-steps/s,
-        // hier 1.75e10 -> 2.05e10, mixture +6 %) -- and eight waves where it holds two or three (reference_model(20): 1.02e10 with four, 1.12e10 with eight;
-        // reference_model(32) 6.1e9 / 7.4e9): profiles/round4_hmc_jit_waves.txt
-        const long long lds8 = ((long long)e->S + 3LL * e->d + 2 + 8) * FG_WAVE * (long long)sizeof(double);
-        const long long resident = std::min<long long>((160 * 1024) / std::max<long long>(1, lds8), ((long long)tiles + n_cu - 1) / n_cu);
-        const int target = (resident >= 4 && n_tasks <= 16) ? 4 : 8;     // (alldists, 24 heavy tasks, four tiles per CU: 9.3e8 with eight waves, 8.7e8 with four)
-        while (2 * W <= std::min(target, wcap)) W *= 2;
-        if (std::getenv("FG_JIT_VERBOSE")) { long long tot = 0; for (long long c : cost) tot += 2 * c; fprintf(stderr, "fugue_amd: compiled HMC unit: d %d, task cost %lld, resident %lld, W %d\n", e->d, tot, resident, W); }
-    }
-    const long long span_tasks = mwi_split(cost, W, &bins);
-    for (int w = 0; w < W; ++w) std::sort(bins[w].begin(), bins[w].end());
-    if (cbins) {
-        // whole coordinates per wave (the one-barrier gradient of fg_jit_wave_grad): both evaluations of a coordinate on one wave.  Taken where the coarser
-        // split stretches the longest wave by less than a barrier costs; FG_JIT_FUSED=0 / 1 forces.
-        std::vector<std::vector<int>> pb;
-        mwi_split(cost, W, &pb, true);
-        // the stretch in the units the rule below was measured in: the split's costs are the interpreter's, where a general density is 10 - 16 against a fast
-        // Normal's 3; compiled, the ratio is about twice that
-        std::vector<long long> tcost((size_t)e->d, 1);
-        for (int k = 0; k < e->d; ++k) {
-            long long cs = 0;
-            for (int q = 0; q < e->prog->coord[k].sub_n; ++q) { const FgIns &in = e->prog->sub[e->prog->coord[k].sub_off + q]; cs += mwi_ins_cost(in) * ((FG_INS_OPCODE(in.op) < 17u) ? 2 : 1); }
-            tcost[(size_t)k] = std::max(1LL, cs);
-        }
-        long long span_tasks_t = 0, span_coords_t = 0;
-        for (int w = 0; w < W; ++w) {
-            long long a = 0, b = 0;
-            for (int t : bins[(size_t)w]) a += tcost[(size_t)(t >> 1)];
-            for (int t : pb[(size_t)w]) b += 2 * tcost[(size_t)(t >> 1)];
-            span_tasks_t = std::max(span_tasks_t, a); span_coords_t = std::max(span_coords_t, b);
-        }
-        const long long span_coords = span_coords_t; (void)span_tasks;
-        cbins->assign((size_t)W, std::vector<int>());
-        for (int w = 0; w < W; ++w) { for (int t : pb[w]) (*cbins)[(size_t)w].push_back(t >> 1); std::sort((*cbins)[(size_t)w].begin(), (*cbins)[(size_t)w].end()); }
-        const long long lds1 = ((long long)e->S + 3LL * e->d + 2 + W) * FG_WAVE * (long long)sizeof(double), lds2 = lds1 + (long long)e->S * FG_WAVE * (long long)sizeof(double);
-        const long long per_cu = ((long long)tiles + n_cu - 1) / n_cu;
-        // (a barrier is worth about 96 such units of the longest wave: reference_model(8) 36 -> 48 units +8 %, reference_model(20) 60 -> 120 +7 % / +15 % at 8 192
-        // chains, reference_model(32) 96 -> 192 +8 %, hier_scale 74 -> 148 of the split's units (general densities) -8 %, logistic regression 465 -> 930 -29 %; the second copy may cost a resident tile but not the last but one:
-        // reference_model(32), two tiles -> one, -14 % -- profiles/round4_hmc_jit_one_barrier.txt)
-        const long long t1 = std::min<long long>((160 * 1024) / lds1, per_cu), t2 = lds2 <= 160 * 1024 ? std::min<long long>((160 * 1024) / lds2, per_cu) : 0;
-        bool ok = t2 >= std::min<long long>(2, t1) && span_coords_t - span_tasks_t <= 96;
-        if (std::getenv("FG_JIT_VERBOSE")) fprintf(stderr, "fugue_amd: compiled HMC unit: W %d, longest wave %lld (tasks) / %lld (whole coordinates), tiles per CU %lld / %lld\n", W, span_tasks_t, span_coords,
-                                                   std::min<long long>((160 * 1024) / lds1, per_cu), std::min<long long>((160 * 1024) / lds2, per_cu));
-        if (const char *fv = std::getenv("FG_JIT_FUSED")) ok = std::atoi(fv) != 0 && lds2 <= 160 * 1024;
-        if (!ok) cbins->clear();
-    }
-    return W;
-}
-
-// the dense mode's one-barrier gradient: every (coordinate, sign) task is the whole program, so whole coordinates per wave cost nothing exactly when
-// 2 ceil(d / W) = ceil(2 d / W); the second copy of the site rows under the same LDS rule as the sparse form's
-static void jit_dense_coord_split(fg_engine *e, unsigned tiles, int W, std::vector<std::vector<int>> &cbins) {
-    cbins.clear();
-    const int d = e->d;
-    if (W < 1 || 2 * ((d + W - 1) / W) != (2 * d + W - 1) / W) return;
-    const long long n_cu = std::max(1, e->n_simd / 4), per_cu = ((long long)tiles + n_cu - 1) / n_cu;
-    const long long lds1 = ((long long)e->S + 3LL * d + 2 + W) * FG_WAVE * (long long)sizeof(double), lds2 = lds1 + (long long)e->S * FG_WAVE * (long long)sizeof(double);
-    const long long t1 = std::min<long long>((160 * 1024) / lds1, per_cu), t2 = lds2 <= 160 * 1024 ? std::min<long long>((160 * 1024) / lds2, per_cu) : 0;
-    bool ok = t2 >= std::min<long long>(2, t1);
-    if (const char *fv = std::getenv("FG_JIT_FUSED")) ok = std::atoi(fv) != 0 && lds2 <= 160 * 1024;
-    if (!ok) return;
-    cbins.assign((size_t)W, std::vector<int>());
-    for (int k = 0; k < d; ++k) cbins[(size_t)(k % W)].push_back(k);
+// the plan of this engine's chain count under the switches `sw` (fg_jit_task_plan); FG_JIT_VERBOSE's lines
+static FgJitTaskPlan jit_task_plan(fg_engine *e, unsigned tiles, int grad_mode, const FgTaskSwitches &sw, bool say) {
+    std::vector<long long> cost, tcost;
+    fg_task_coord_costs(e->prog->coord.data(), e->d, e->prog->sub.data(), cost, tcost);
+    const FgJitTaskIn in = { e->d, e->S, tiles, e->n_simd, e->mw_override, &cost, &tcost, grad_mode, sw };
+    const FgJitTaskPlan p = fg_jit_task_plan(in);
+    if (say && sw.verbose.set) fputs(fg_jit_task_say(p, e->d).c_str(), stderr);
+    return p;
 }
 
 // the program's compiled module (once per engine): HMC transitions, the step-size search, adaptive_smc's rejuvenation move
@@ -432,17 +293,18 @@ static int jit_hmc_module(fg_engine *e) {
         if (e->prog->sub.size() + e->prog->ins_fast.size() > 64000000) return FG_E_UNSUPPORTED;
         std::vector<double> ctab;
         bool has_ad = false, has_dense = false;
-        std::vector<long long> cost0;
-        e->jit_baked_bins.clear();
-        e->jit_baked_cbins.clear();
-        e->jit_baked_cbins_dense.clear();
-        if (!(std::getenv("FG_JIT_TASKS") && std::atoi(std::getenv("FG_JIT_TASKS")) == 0)) {
+        FgHmcSplitState &st = e->hsplit;
+        std::vector<std::vector<int>> bins;
+        st.gen_sparse = st.gen_dense = FgTaskSplit();
+        const FgTaskSwitches sw = fg_task_switches();
+        if (!fg_switch_is(sw.tasks, 0)) {                         // the unit is generated behind the split of this chain count under these switches
             const unsigned tiles0 = (unsigned)((e->C + e->tw - 1) / e->tw);
-            const int W0 = jit_sparse_split(e, tiles0, cost0, e->jit_baked_bins, &e->jit_baked_cbins);
-            jit_dense_coord_split(e, tiles0, W0, e->jit_baked_cbins_dense);
+            const FgJitTaskPlan p = jit_task_plan(e, tiles0, FG_GRAD_FD_SPARSE, sw, true);
+            bins = p.bins; st.gen_sparse = p.split;
+            st.gen_dense = jit_task_plan(e, tiles0, FG_GRAD_FD_DENSE, sw, false).split;
         }
-        const std::string src = fg_jit_hmc_source(e->prog, &ctab, &has_ad, &has_dense, e->jit_baked_bins.empty() ? nullptr : &e->jit_baked_bins, e->jit_baked_cbins.empty() ? nullptr : &e->jit_baked_cbins,
-                                                  e->jit_baked_cbins_dense.empty() ? nullptr : &e->jit_baked_cbins_dense);
+        const std::string src = fg_jit_hmc_source(e->prog, &ctab, &has_ad, &has_dense, bins.empty() ? nullptr : &bins, st.gen_sparse.cbins.empty() ? nullptr : &st.gen_sparse.cbins,
+                                                  st.gen_dense.cbins.empty() ? nullptr : &st.gen_dense.cbins);
         if (src.empty() || src.size() > (6u << 20)) return FG_E_UNSUPPORTED;                            // plates roll into loops; what stays straight-line must stay compilable in seconds
         std::vector<char> code;
         const int rc = fg_jit_get_code(src, code, e->jit_log);
@@ -526,46 +388,24 @@ static int jit_hmc_prepare(fg_engine *e, unsigned tiles) {
     if (dense && !e->jit_has_dense) return FG_E_UNSUPPORTED;      // (d copies of the program were too much to compile: the interpreter kernels)
     const int n_tasks = 2 * e->d;
     {   // LDS: S site rows + d momentum rows + 2 d evaluation rows + exchange rows; beyond 64 KB the module's functions need the attribute
-        const size_t lds_max = (size_t)((long long)e->S + 3LL * e->d + 2 + FG_MWI_MAX) * FG_WAVE * sizeof(double);
-        if (lds_max > 160 * 1024) return FG_E_UNSUPPORTED;
-        if (lds_max + (size_t)e->S * FG_WAVE * sizeof(double) > 64 * 1024 && !e->jit_lds_attr) {      // (+ the second copy of the site rows of the one-barrier gradient)
+        if (fg_task_lds(e->S, e->d, FG_MWI_MAX) > 160 * 1024) return FG_E_UNSUPPORTED;
+        if (fg_task_lds(e->S, e->d, FG_MWI_MAX, 0, true) > 64 * 1024 && !e->jit_lds_attr) {      // (+ the second copy of the site rows of the one-barrier gradient)
             if (hipFuncSetAttribute((const void *)e->jit_fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
                 hipFuncSetAttribute((const void *)e->jit_fn_eps, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); e->jit_state = -1; return FG_E_UNSUPPORTED; }
             e->jit_lds_attr = true;
         }
     }
-    if (!e->d_mwi_order) {
-        HIPCHK(hipMalloc((void **)&e->d_mwi_order, (size_t)2 * n_tasks * sizeof(int)));      // (the second half: the split of the analytic mode)
-        HIPCHK(hipMalloc((void **)&e->d_mwi_prof, (size_t)n_tasks * sizeof(long long)));
+    FgHmcSplitState &st = e->hsplit;
+    if (!st.d_mwi_order) {
+        HIPCHK(hipMalloc((void **)&st.d_mwi_order, (size_t)2 * n_tasks * sizeof(int)));      // (the second half: the split of the analytic mode)
+        HIPCHK(hipMalloc((void **)&st.d_mwi_prof, (size_t)n_tasks * sizeof(long long)));
     }
-    const int split_key = dense ? 4 : 2;                   // (2: the split of the compiled kernel; 4: its dense mode -- every task is the whole program)
-    if (e->mwi_sparse != split_key || e->mwi_W <= 0) {
-        std::vector<std::vector<int>> bins, cbins;
-        int W = jit_sparse_split(e, tiles, e->mwi_cost, bins, &cbins);
-        e->mwi_fused = !dense && !cbins.empty() && cbins == e->jit_baked_cbins;
-        if (dense) { std::vector<std::vector<int>> dc; jit_dense_coord_split(e, tiles, W, dc); e->mwi_fused = !dc.empty() && dc == e->jit_baked_cbins_dense; }
-        if (dense) { e->mwi_cost.assign(e->d, 1); mwi_split(e->mwi_cost, W, &bins); }      // (every task is the whole program)
-        e->mwi_baked = !dense && !e->jit_baked_bins.empty() && (int)e->jit_baked_bins.size() == W;
-        for (int w = 0; w < W && e->mwi_baked; ++w) { std::vector<int> b = bins[w]; std::sort(b.begin(), b.end()); e->mwi_baked = b == e->jit_baked_bins[w]; }
-        std::vector<int> order;
-        e->mwi_off.assign(FG_MWI_MAX + 1, n_tasks);
-        for (int w = 0; w < W; ++w) {
-            e->mwi_off[w] = (int)order.size();
-            std::sort(bins[w].begin(), bins[w].end());
-            order.insert(order.end(), bins[w].begin(), bins[w].end());
-        }
-        // FG_GRAD_ANALYTIC: one derivative task per coordinate, dealt over the same W waves (the step-size search keeps the split above)
-        mwi_split(e->mwi_cost, W, &bins, true);
-        e->mwi_off_an.assign(FG_MWI_MAX + 1, n_tasks + e->d);
-        order.resize(n_tasks);
-        for (int w = 0; w < W; ++w) {
-            e->mwi_off_an[w] = (int)order.size();
-            std::sort(bins[w].begin(), bins[w].end());
-            order.insert(order.end(), bins[w].begin(), bins[w].end());
-        }
-        HIPCHK(hipMemcpyAsync(e->d_mwi_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->mwi_W = W; e->mwi_sparse = split_key;
+    const FgSplitKey key = dense ? FG_SPLIT_JIT_DENSE : FG_SPLIT_JIT_SPARSE;      // (dense: every task is the whole program)
+    if (st.key != key) {
+        FgJitTaskPlan p = jit_task_plan(e, tiles, e->cfg.grad_mode, fg_task_switches(), true);
+        HIPCHK(hipMemcpyAsync(st.d_mwi_order, p.split.order.data(), p.split.order.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));                // `p` is a local
+        st.split = std::move(p.split); st.cost = std::move(p.cost); st.key = key;
     }
     return FG_OK;
 }
@@ -575,11 +415,12 @@ int fg_hmc_jit_find_eps(fg_engine *e, uint32_t instance, int injected, double *d
     const unsigned tiles = (unsigned)((e->C + e->tw - 1) / e->tw);
     // the choice of kernel must be the one fg_hmc_step will make: only programs the compiled form takes by default or by force
     if (int rc = jit_hmc_prepare(e, tiles)) return rc;
-    const int W = e->mwi_W;
+    const FgTaskSplit &sp = e->hsplit.split;
+    const int W = sp.W;
     FgJitSeg seg;
-    for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = e->mwi_off[w];
-    seg.order = e->d_mwi_order; seg.baked = 0;
-    const size_t lds = (size_t)((long long)e->S + 3LL * e->d + 2 + W) * FG_WAVE * sizeof(double);
+    for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = sp.off[w];
+    seg.order = e->hsplit.d_mwi_order; seg.baked = 0;
+    const size_t lds = (size_t)fg_task_lds(e->S, e->d, W);
     void *args[] = { &e->P, &e->X, &e->H, &seg, &instance, &injected, &d_eps_out };
     HIPCHK(hipModuleLaunchKernel(e->jit_fn_eps, tiles, 1, 1, FG_WAVE * W, 1, 1, (unsigned)lds, e->stream, args, nullptr));
     return FG_OK;
@@ -588,19 +429,14 @@ int fg_hmc_jit_find_eps(fg_engine *e, uint32_t instance, int injected, double *d
 int fg_hmc_jit_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {
     const unsigned tiles = (unsigned)((e->C + e->tw - 1) / e->tw);
     if (int rc = jit_hmc_prepare(e, tiles)) return rc;
-    auto lds_for = [&](int W) { return (size_t)((long long)e->S + 3LL * e->d + 2 + W) * FG_WAVE * sizeof(double); };
-    const int W = e->mwi_W;
+    const FgHmcSplitState &st = e->hsplit;
+    const FgJitLaunchShape sh = fg_jit_launch_shape(st.split, e->cfg.grad_mode == FG_GRAD_FD_DENSE ? st.gen_dense : st.gen_sparse, e->cfg.grad_mode, e->jit_has_ad, e->S, e->d);
     FgJitSeg seg;
-    for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = e->mwi_off[w];
-    seg.order = e->d_mwi_order;
-    seg.baked = (e->mwi_baked && e->cfg.grad_mode == FG_GRAD_FD_SPARSE) ? 1 : 0;      // the unit holds this very split as straight-line code (fg_jit_wave_tasks)
-    const bool fused = e->mwi_fused && (e->cfg.grad_mode == FG_GRAD_FD_SPARSE || e->cfg.grad_mode == FG_GRAD_FD_DENSE);   // ... or whole coordinates per wave (fg_jit_wave_grad / _dense): a second copy of the site rows
-    if (fused) seg.baked = e->cfg.grad_mode == FG_GRAD_FD_DENSE ? 3 : 2;
-    if (e->cfg.grad_mode == FG_GRAD_ANALYTIC && e->jit_has_ad) for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = e->mwi_off_an[w];
+    for (int w = 0; w <= FG_MWI_MAX; ++w) seg.off[w] = sh.analytic_off ? st.split.off_an[w] : st.split.off[w];
+    seg.order = st.d_mwi_order; seg.baked = sh.baked;
     int n_warmup = e->n_warmup;
     void *args[] = { &e->P, &e->X, &e->H, &seg, &iter0, &n, &n_warmup, &welford_on, &draws, &first_sample_t, &pos_all, &info };
-    const size_t lds = lds_for(W) + (fused ? (size_t)e->S * FG_WAVE * sizeof(double) : 0);
-    HIPCHK(hipModuleLaunchKernel(e->jit_fn, tiles, 1, 1, FG_WAVE * W, 1, 1, (unsigned)lds, e->stream, args, nullptr));
-    e->last_hmc_kernel = "k_hmc_jit_steps W=" + std::to_string(W) + (e->cfg.grad_mode == FG_GRAD_FD_DENSE ? (fused ? " (dense; compiled at run time, one barrier per gradient)" : " (dense; compiled at run time)") : fused ? " (compiled at run time, one barrier per gradient)" : " (compiled at run time)");
+    HIPCHK(hipModuleLaunchKernel(e->jit_fn, tiles, 1, 1, FG_WAVE * st.split.W, 1, 1, (unsigned)sh.lds, e->stream, args, nullptr));
+    e->last_hmc_kernel = sh.name;
     return FG_OK;
 }

@@ -481,10 +481,10 @@ void k_hmc_lin_steps(FgProgramDev P, FgChainCtx X, FgHmcDev H, int iter0, int n_
 
 // Launch for `n` transitions from iteration `iter0`; FG_E_UNSUPPORTED when the program / configuration is not a dense
 // regression in the sparse finite-difference mode (the caller then takes the gradient-stream kernel).
+// the part of that which no launch changes (tiles in global memory: the one-wave-per-tile kernels of fg_engine.hip; the table exists for d <= 64: fg_program.cpp)
+bool fg_hmc_lin_gate(const fg_engine *e) { return !e->gt && e->P.lin_tab && !e->lin_disabled && e->tw == FG_WAVE && e->d >= 2 && e->d <= 64; }
 int fg_hmc_lin_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {
-    if (e->gt) return FG_E_UNSUPPORTED;                       // tiles in global memory: the one-wave-per-tile kernels (fg_engine.hip)
-    if (!e->P.lin_tab || e->cfg.grad_mode != FG_GRAD_FD_SPARSE || e->lin_disabled || e->tw != FG_WAVE) return FG_E_UNSUPPORTED;
-    if (e->d < 2 || e->d > 64) return FG_E_UNSUPPORTED;      // (the table exists for d <= 64: fg_program.cpp)
+    if (!fg_hmc_lin_gate(e) || e->cfg.grad_mode != FG_GRAD_FD_SPARSE) return FG_E_UNSUPPORTED;
     const int D = e->d <= 8 ? 8 : (e->d <= 16 ? 16 : (e->d <= 32 ? 32 : 64));     // term positions of the build that takes it (padded with +0.0 terms)
     const long long n_cu = std::max(1, e->n_simd / 4);
     const long long tiles64 = (e->C + FG_WAVE - 1) / FG_WAVE;

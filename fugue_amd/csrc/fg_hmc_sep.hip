@@ -797,7 +797,7 @@ static FgSepVariant fg_sep_variants[] = { FG_SEP_VARIANTS(FG_SEP_ENTRY) };
 // Launch for `n` transitions from iteration `iter0`; returns FG_E_UNSUPPORTED when the program / configuration is not an
 // independent-sites FD-sparse run (the caller then takes the gradient-stream kernel).  Plan (fg_hmc_sep_plan.h), look up, launch, name.
 int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {
-    if (e->gt || !e->P.sep || e->sep_disabled) return FG_E_UNSUPPORTED;   // (fg_hmc_sep_plan says so too: every HMC launch asks here first, most read no switch)
+    if (!fg_hmc_sep_gate(e->gt, e->P.sep != nullptr, e->sep_disabled, e->d)) return FG_E_UNSUPPORTED;   // (fg_hmc_sep_plan says so too: every HMC launch asks here first, most read no switch)
     const FgSepPlanIn in = { e->C, e->d, e->n_simd, e->n_slots, e->P.n_sep_free, e->P.n_sstream, e->cfg.grad_mode, e->H.use_mass != 0, e->mw_override,
                              e->gt, e->sep_disabled, e->sep_res_disabled, e->sep_fold_disabled, e->prog->sep_fold, &e->prog->sep_coord, &e->prog->sep,
                              fg_env_switch("FG_HMC_SEP_HALF"), fg_env_switch("FG_HMC_DENSE_FAST"), fg_env_switch("FG_HMC_SUM4"), fg_env_switch("FG_HMC_PRIO"),

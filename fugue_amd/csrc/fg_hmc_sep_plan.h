@@ -48,6 +48,9 @@ struct FgSepPlan {
     std::string name;                                        // fg_hmc_last_kernel
 };
 
+// the static part of that: fg_hmc_sep_launch's first early-out, and what fg_hmc_jit_first (fg_hmc_split_plan.h) asks
+inline bool fg_hmc_sep_gate(bool gt, bool has_sep, bool sep_disabled, int d) { return !gt && has_sep && !sep_disabled && d >= 1; }
+
 // FG_E_UNSUPPORTED when the program / configuration is not an independent-sites run this kernel takes.
 inline int fg_hmc_sep_plan(const FgSepPlanIn &in, FgSepPlan *out) {
     const int d = in.d;

@@ -1,4 +1,4 @@
-// fg_switch.h -- an environment switch as the launch plans (fg_hmc_sep_plan.h, fg_mh_mw_plan.h) take it: unset, or its integer value.
+// fg_switch.h -- an environment switch as the launch plans (fg_hmc_sep_plan.h, fg_mh_mw_plan.h, fg_hmc_split_plan.h) take it: unset, or its integer value.
 // The launchers read the environment (fg_env_switch); the plans only see the values.
 #pragma once
 #include <cstdlib>
