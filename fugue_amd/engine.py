@@ -93,6 +93,8 @@ ABI_SYMBOLS = [
     "fg_vi_config_default", "fg_vi_elbo_batch", "fg_vi_optimize", "fg_vi_estimate_elbo",
     "fg_diag_stream_new", "fg_diag_stream_update", "fg_diag_stream_count", "fg_diag_stream_moments", "fg_diag_stream_autocov_sums",
     "fg_diag_stream_rhat_ess", "fg_diag_stream_free",
+    "fg_diag_qstream_new", "fg_diag_qstream_update", "fg_diag_qstream_count", "fg_diag_qstream_end_pass", "fg_diag_qstream_passes",
+    "fg_diag_qstream_result", "fg_diag_qstream_free",
 ]
 
 _lib = None
@@ -216,6 +218,14 @@ def lib():
     L.fg_diag_stream_rhat_ess.argtypes = [vp, vp, dp, dp, dp, dp, C.POINTER(C.c_int64)]
     L.fg_diag_stream_free.restype = None
     L.fg_diag_stream_free.argtypes = [vp]
+    L.fg_diag_qstream_new.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int64, C.POINTER(vp)]
+    L.fg_diag_qstream_update.argtypes = [vp, vp, C.c_int]
+    L.fg_diag_qstream_count.argtypes = [vp]
+    L.fg_diag_qstream_end_pass.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fg_diag_qstream_passes.argtypes = [vp]
+    L.fg_diag_qstream_result.argtypes = [vp, dp, C.POINTER(C.c_int32)]
+    L.fg_diag_qstream_free.restype = None
+    L.fg_diag_qstream_free.argtypes = [vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
     L.fg_mh_last_kernel.restype = C.c_char_p
@@ -720,6 +730,11 @@ class Engine:
         and are never stored; `max_lag` (rounded up to a multiple of 32, at most 2 048) is the deepest lag Geyer's sequence may reach."""
         return DiagStream(self, n_total, d, max_lag)
 
+    def diag_qstream(self, n_total: int, d: int, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digit_bits: int = 12, capacity: int = 65536) -> "DiagQuantileStream":
+        """A `fg_diag_qstream`: the quantiles of `diag_quantiles` for `n_total` draws of `d` coordinates that are never stored but
+        presented once per pass (the sampling phase replayed from `state_export`'s blob), until `end_pass()` returns True."""
+        return DiagQuantileStream(self, n_total, d, probs, digit_bits, capacity)
+
     def hmc_last_kernel(self) -> str:
         """Kernel (and waves per tile) the engine's last HMC launch ran."""
         return (lib().fg_hmc_last_kernel(self.h) or b"").decode()
@@ -823,6 +838,80 @@ class DiagStream:
         if getattr(self, "h", None):
             if getattr(self.engine, "h", None):          # the state lives in the engine's device context
                 lib().fg_diag_stream_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DiagQuantileStream:
+    """`fg_diag_qstream` (fg_diag_qstream.hip): summarize_f64_parameter's quantiles (diagnostics.rs:355-371) by exact radix select
+    over a run that is presented once per pass.  A pass is `n_total` draws through `update`, then `end_pass()`; while that returns
+    False the same draws must be presented again (in any chunking).  A pass that does not reproduce the previous one raises
+    EngineError (FG_E_STATE).  Device memory: d x len(probs) x (2^digit_bits counters + capacity keys).  Close it before its engine."""
+
+    def __init__(self, engine: Engine, n_total: int, d: int, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digit_bits: int = 12, capacity: int = 65536):
+        for name, v in (("n_total", n_total), ("d", d), ("digit_bits", digit_bits), ("capacity", capacity)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        if n_total < 1:
+            raise ValueError("n_total must be at least 1")
+        if not 1 <= d <= 65535:
+            raise ValueError("d must lie in [1, 65535]")
+        if not 1 <= pr.size <= 8:
+            raise ValueError("between 1 and 8 probabilities")
+        if not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError("probabilities must lie in [0, 1]")
+        if not 1 <= digit_bits <= 12:
+            raise ValueError("digit_bits must lie in [1, 12]")
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        self.engine, self.n, self.d, self.probs = engine, int(n_total), int(d), pr
+        self.h = None
+        out = C.c_void_p()
+        _check(lib().fg_diag_qstream_new(engine.h, self.n, self.d, _dp(pr), pr.size, int(digit_bits), int(capacity), C.byref(out)))
+        self.h = out.value
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the stream is closed")
+        return self.h
+
+    def update(self, d_draws: int, n_chunk: int):
+        """The next `n_chunk` draws of the current pass, a device buffer [n_chunk][d][C]."""
+        _check(lib().fg_diag_qstream_update(self._handle(), d_draws, int(n_chunk)))
+
+    @property
+    def count(self) -> int:
+        """Draws taken in the current pass."""
+        return int(lib().fg_diag_qstream_count(self._handle()))
+
+    def end_pass(self) -> bool:
+        """Ends the pass; True when every quantile is selected, False when the run must be presented again."""
+        done = C.c_int()
+        _check(lib().fg_diag_qstream_end_pass(self._handle(), C.byref(done)))
+        return bool(done.value)
+
+    @property
+    def passes(self) -> int:
+        """Passes completed."""
+        return int(lib().fg_diag_qstream_passes(self._handle()))
+
+    def result(self):
+        """(values [d][len(probs)], slot_passes [d][len(probs)]: the passes each quantile took part in)."""
+        out = np.zeros((self.d, self.probs.size))
+        sp = np.zeros((self.d, self.probs.size), dtype=np.int32)
+        _check(lib().fg_diag_qstream_result(self._handle(), _dp(out), sp.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, sp
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
+                lib().fg_diag_qstream_free(self.h)
             self.h = None
 
     def __del__(self):

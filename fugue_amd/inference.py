@@ -161,11 +161,15 @@ def adaptive_mcmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, n_ch
     return adaptive_mcmc_chain_with_overrides(seed, model_fn, n_samples, n_warmup, (), n_chains, device)
 
 
+QUANTILE_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)      # summarize_f64_parameter's "2.5%", "25%", "50%", "75%", "97.5%"
+
+
 @dataclass
 class ChainSummary:
     """What `summarize_f64_parameter` (diagnostics.rs:320-392) reports for every f64 site of a run whose draws were never stored:
-    pooled mean / std, split R-hat, multi-chain ESS, each [n_sites] in the order of `sites`.  No quantiles: selecting them takes
-    eight passes over draws that no longer exist."""
+    pooled mean / std, split R-hat, multi-chain ESS, each [n_sites] in the order of `sites`.  With `quantiles=True` the drivers
+    also select `quantiles` [n_sites][5] at `quantile_probs` (diagnostics.rs:355-371: "2.5%" ... "97.5%"), exactly the elements a
+    sort of all draws would give, by replaying the sampling phase: `passes` counts how often it ran (1 without quantiles)."""
     sites: List[str]
     mean: np.ndarray
     std: np.ndarray
@@ -176,6 +180,9 @@ class ChainSummary:
     accept_rate: float = 0.0
     mean_step_size: float = float("nan")
     n_divergent: int = 0
+    quantiles: Optional[np.ndarray] = None
+    quantile_probs: Tuple[float, ...] = QUANTILE_PROBS
+    passes: int = 1
 
 
 def _summary_args(n_samples: int, chunk: int, max_lag: int):
@@ -187,32 +194,60 @@ def _summary_args(n_samples: int, chunk: int, max_lag: int):
         raise ValueError("max_lag must lie in [1, 2048]")
 
 
-def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int):
-    """step(n, buf) records n draws [n][d][C] into buf; one chunk buffer is alive at a time."""
+def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
+                    after_first_pass=None):
+    """step(n, buf) records n draws [n][d][C] into buf; one chunk buffer is alive at a time.  quantiles: the state after warmup is
+    exported, the first sampling pass feeds the diagnostics stream and a quantile stream, `after_first_pass()` reads the sampler's
+    statistics, and while the quantile stream wants another pass the blob is imported into the same engine and the same chunks are
+    stepped again for the quantile stream alone."""
     chunk = min(chunk, n_samples)
     stream = eng.diag_stream(n_samples, d, max_lag)
-    buf = eng.device_alloc(chunk * d * eng.C * 8)
+    qs, buf = None, None
     try:
-        done = 0
-        while done < n_samples:
-            n = min(chunk, n_samples - done)
-            step(n, buf)
-            stream.update(buf, n)
-            done += n
+        blob = None
+        if quantiles:
+            qs = eng.diag_qstream(n_samples, d, QUANTILE_PROBS, capacity=quantile_capacity)
+            blob = eng.state_export()
+        buf = eng.device_alloc(chunk * d * eng.C * 8)
+
+        def one_pass(consumers):
+            done = 0
+            while done < n_samples:
+                n = min(chunk, n_samples - done)
+                step(n, buf)
+                for c in consumers:
+                    c.update(buf, n)
+                done += n
+
+        one_pass([stream, qs] if quantiles else [stream])
         r = stream.rhat_ess()
+        out = ChainSummary(list(sites), r["mean"], r["std"], r["r_hat"], r["ess"], n_samples, int(r["chains"]))
+        if after_first_pass:
+            after_first_pass(out)
+        if quantiles:
+            while not qs.end_pass():
+                eng.state_import(blob)
+                one_pass([qs])
+            out.quantiles, out.passes = qs.result()[0], qs.passes
     finally:
         eng.synchronize()
-        eng.device_free(buf)
+        if buf is not None:
+            eng.device_free(buf)
         stream.close()
-    return ChainSummary(list(sites), r["mean"], r["std"], r["r_hat"], r["ess"], n_samples, int(r["chains"]))
+        if qs is not None:
+            qs.close()
+    return out
 
 
 def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
-                      chunk: int = 64, max_lag: int = 64, device: int = 0) -> ChainSummary:
+                      chunk: int = 64, max_lag: int = 64, device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536) -> ChainSummary:
     """`hmc_chain` for runs longer than memory: the same transitions (`fg_hmc_step` is incremental), `chunk` at a time into one
     draw buffer that a diagnostics stream consumes, and the summary of every f64 site instead of the draws.  `max_lag` bounds how
-    far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  Quantiles are out of scope: radix select
-    needs eight passes over the draws."""
+    far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  `quantiles=True` adds the five quantiles
+    of summarize_f64_parameter by exact radix select (`Engine.diag_qstream`): the draws are not kept, so every pass beyond the
+    first REPEATS THE SAMPLING PHASE from the state exported after warmup -- about three passes for a long run at the default
+    `quantile_capacity` (keys collected per quantile once that few candidates are left; device memory 8 x 5 x n_sites x capacity
+    bytes), `ChainSummary.passes` reports the count.  Every other figure is the one `quantiles=False` gives."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     if cp.d == 0:
@@ -222,9 +257,11 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
     try:
         eng.hmc_init(cfg.raw(), n_warmup)
         eng.hmc_step(n_warmup)
-        out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag)
-        st = eng.hmc_stats()
-        out.accept_rate, out.mean_step_size, out.n_divergent = st.accept_rate, st.mean_step_size, int(st.n_divergent)
+        def stats(out):
+            st = eng.hmc_stats()
+            out.accept_rate, out.mean_step_size, out.n_divergent = st.accept_rate, st.mean_step_size, int(st.n_divergent)
+
+        out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag, quantiles, quantile_capacity, stats)
     finally:
         eng.close()
     return out
@@ -232,10 +269,11 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
 
 def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1,
                                 overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
-                                device: int = 0) -> ChainSummary:
+                                device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536) -> ChainSummary:
     """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
-    only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  Quantiles are out of scope
-    (see `hmc_chain_summary`)."""
+    only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  `quantiles=True` adds the five
+    quantiles as `hmc_chain_summary` does: every pass beyond the first REPEATS THE SAMPLING PHASE from the state exported after
+    warmup (`ChainSummary.passes`)."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     rec = list(cp.f64_sites)
@@ -246,8 +284,11 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
     try:
         eng.mh_init(n_warmup, ov)
         eng.mh_step(n_warmup)
-        out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in rec], len(rec), n_samples, chunk, max_lag)
-        out.accept_rate = eng.mh_stats().accept_rate
+        def stats(out):
+            out.accept_rate = eng.mh_stats().accept_rate
+
+        out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in rec], len(rec), n_samples, chunk, max_lag,
+                              quantiles, quantile_capacity, stats)
     finally:
         eng.close()
     return out

@@ -435,7 +435,8 @@ int fg_diag_combine_reduced(int64_t m, int n, int d, fg_reduce_fn reduce, fg_aco
  * (mcmc_utils.rs:214-339), the pooled mean / std of summarize_f64_parameter (diagnostics.rs:331-352) -- for a run that is handed
  * over one chunk of draws at a time and never stored.  Per (coordinate, chain) the stream keeps (3 K + 7) doubles, K = max_lag
  * rounded up to a multiple of 32 (at most 2 048, the reference's lag cap, mcmc_utils.rs:266): in-order sums about the column's
- * first draw, so the result does not depend on where the chunk boundaries fall.  Quantiles need the draws and are not offered. */
+ * first draw, so the result does not depend on where the chunk boundaries fall.  Quantiles need the draws: fg_diag_qstream below selects
+ * them from a run that is presented again, once per pass. */
 typedef struct fg_diag_stream fg_diag_stream;
 /* FG_E_BAD_ARG: n_total < 1, d outside [1, 65535], max_lag outside [1, 2048].  The stream must be freed before its engine. */
 int  fg_diag_stream_new(fg_engine *e, int n_total, int d, int max_lag, fg_diag_stream **out);
@@ -455,6 +456,34 @@ int  fg_diag_stream_autocov_sums(fg_diag_stream *s, int lag0, int n_lags, double
 int  fg_diag_stream_rhat_ess(fg_diag_stream *s, void *rccl_comm, double *h_rhat, double *h_ess, double *h_mean,
                              double *h_std, int64_t *out_total_chains);
 void fg_diag_stream_free(fg_diag_stream *s);
+/* ------------------------------------------------------------------ quantiles without stored draws
+ * The quantiles of summarize_f64_parameter (diagnostics.rs:355-371), sorted[round((len - 1) p)] over the len = n_total x C draws
+ * of a coordinate, for a run that is never stored but can be presented again: the random streams are keyed by (seed, chain,
+ * iteration), so fg_state_import of the blob taken after warmup followed by the same fg_hmc_step / fg_mh_step calls reproduces
+ * every draw.  A pass is one presentation of all n_total draws, in any chunking.  Exact radix select on fg_diag_quantiles' key
+ * (-0.0 below +0.0, positive NaN above +inf): a pass counts the next digit_bits bits of the elements that still match each
+ * quantile's prefix; once at most `capacity` elements match, the next pass collects them (d x n_probs x capacity keys of device
+ * memory) and the host picks the element.  The result is the element a sort would give.  Every pass must present the same draws:
+ * the count of matching elements is checked against the previous pass at every end_pass (FG_E_STATE: a replay that diverged never
+ * yields a quantile).  These entry points cover this engine's chains only and take no communicator; runs sharded over ranks keep
+ * fg_diag_quantiles on stored draws. */
+typedef struct fg_diag_qstream fg_diag_qstream;
+/* diagnostics.rs:355-371.  FG_E_BAD_ARG: n_total < 1, d outside [1, 65535], n_probs outside [1, 8], a probability outside [0, 1],
+ * digit_bits outside [1, 12], capacity < 0.  The stream must be freed before its engine. */
+int  fg_diag_qstream_new(fg_engine *e, int n_total, int d, const double *h_probs, int n_probs,
+                         int digit_bits, int64_t capacity, fg_diag_qstream **out);
+/* diagnostics.rs:355-371: the next n_chunk draws d_draws [n_chunk][d][C] of the current pass; asynchronous on the engine's stream.
+ * FG_E_STATE when the chunk would pass n_total, or once every quantile is selected. */
+int  fg_diag_qstream_update(fg_diag_qstream *s, const double *d_draws, int n_chunk);
+int  fg_diag_qstream_count(const fg_diag_qstream *s);          /* diagnostics.rs:355-371: draws taken in the current pass */
+/* diagnostics.rs:355-371: ends the pass (FG_E_STATE before n_total draws, or when it did not reproduce the previous pass);
+ * *out_done = 1 when every quantile is selected, else the next pass has begun. */
+int  fg_diag_qstream_end_pass(fg_diag_qstream *s, int *out_done);
+int  fg_diag_qstream_passes(const fg_diag_qstream *s);         /* diagnostics.rs:355-371: passes completed */
+/* diagnostics.rs:355-371: h_out [d][n_probs]; h_slot_passes [d][n_probs] (or NULL) = the passes each quantile took part in.
+ * FG_E_STATE before the stream is done. */
+int  fg_diag_qstream_result(fg_diag_qstream *s, double *h_out, int32_t *h_slot_passes);
+void fg_diag_qstream_free(fg_diag_qstream *s);                 /* diagnostics.rs:355-371 */
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

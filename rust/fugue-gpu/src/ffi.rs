@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_program { _p: [u8; 0] }
 #[repr(C)] pub struct fg_engine { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_stream { _p: [u8; 0] }
+#[repr(C)] pub struct fg_diag_qstream { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -145,6 +146,15 @@ extern "C" {
     pub fn fg_diag_stream_rhat_ess(s: *mut fg_diag_stream, rccl_comm: *mut c_void, h_rhat: *mut f64, h_ess: *mut f64, h_mean: *mut f64,
                                    h_std: *mut f64, out_total_chains: *mut i64) -> c_int;
     pub fn fg_diag_stream_free(s: *mut fg_diag_stream);
+    // ---- quantiles without stored draws: exact radix select over replayed passes (fg_diag_qstream.hip)
+    pub fn fg_diag_qstream_new(e: *mut fg_engine, n_total: c_int, d: c_int, h_probs: *const f64, n_probs: c_int, digit_bits: c_int, capacity: i64,
+                               out: *mut *mut fg_diag_qstream) -> c_int;
+    pub fn fg_diag_qstream_update(s: *mut fg_diag_qstream, d_draws: *const f64, n_chunk: c_int) -> c_int;
+    pub fn fg_diag_qstream_count(s: *const fg_diag_qstream) -> c_int;
+    pub fn fg_diag_qstream_end_pass(s: *mut fg_diag_qstream, out_done: *mut c_int) -> c_int;
+    pub fn fg_diag_qstream_passes(s: *const fg_diag_qstream) -> c_int;
+    pub fn fg_diag_qstream_result(s: *mut fg_diag_qstream, h_out: *mut f64, h_slot_passes: *mut i32) -> c_int;
+    pub fn fg_diag_qstream_free(s: *mut fg_diag_qstream);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
