@@ -394,7 +394,11 @@ fg_program *fg_dsl_compile(const char *source_utf8, const char *data_json_utf8) 
         Env env; env.warnings = &b.warnings;
         bind_data(data_json_utf8 ? data_json_utf8 : "", env.vars);
         b.run(stmts, env);
-        (void)eval(ret, env);                       // validates the names used by pure(..)
+        const Val rv = eval(ret, env);              // validates the names used by pure(..)
+        if (rv.k == Val::SYM || rv.numeric()) {     // a numeric return value is the model's one result (an array is not: still ignored)
+            const std::vector<fg_tok> rt = rv.toks();
+            (void)fg_program_result(p, "result", rt.data(), (int)rt.size());
+        }
         p->dsl_warnings = b.warnings;
         const int rc = fg_program_finalize(p);
         if (rc) { fg_program_free(p); return nullptr; }

@@ -113,6 +113,10 @@ struct fg_engine {
     void *d_vi_tab = nullptr; uint32_t *d_vi_sid = nullptr; double *d_vi_terms = nullptr, *d_vi_partial = nullptr, *d_vi_elbo = nullptr, *d_vi_gtile = nullptr;
     size_t vi_cap_tab = 0, vi_cap_eval = 0, vi_cap_terms = 0;
     int mw_override = 0;       // FG_HMC_WAVES env: force waves per tile of the multi-wave HMC kernel (tests)
+    // the model's return value (fg_result.hip): device copies of the result program, made at the first fg_result_eval; the row of the draw
+    // each used site comes from as last uploaded; the global scratch of programs whose slice exceeds a CU's LDS, grown on demand
+    FgIns *d_res_ins = nullptr; double *d_res_pool = nullptr; int *d_res_site = nullptr, *d_res_row = nullptr; std::vector<int> res_row_host;
+    double *d_res_gtile = nullptr; size_t res_gtile_bytes = 0;
 };
 
 // p0 ~ N(0, M): hmc.rs:436-441.  Box-Muller pairs from the chain's (iteration) stream.

@@ -128,7 +128,9 @@ struct FgGen {
     const fg_program &P;
     std::vector<FgIns> &out;
     int temp_next, temp_max;
+    const std::vector<int> *slot_of = nullptr;             // results: their own slot of each sorted site (compile_results), else the program's site_slot
     FgGen(const fg_program &p, std::vector<FgIns> &o) : P(p), out(o), temp_next(p.n_samples), temp_max(p.n_samples) {}
+    FgGen(const fg_program &p, std::vector<FgIns> &o, const std::vector<int> &slots, int first_temp) : P(p), out(o), temp_next(first_temp), temp_max(first_temp), slot_of(&slots) {}
 
     int new_temp(int n = 1) { int t = temp_next; temp_next += n; temp_max = std::max(temp_max, temp_next); return t; }
     static FgIns blank(uint32_t op) { FgIns I; std::memset(&I, 0, sizeof(I)); I.op = op; return I; }
@@ -138,7 +140,7 @@ struct FgGen {
         const FgNode &n = P.nodes[node];
         if (n.op == FG_T_CONST) { word = FG_OPND(FG_OPND_IMM, 0); imm = n.cval; return; }
         const int site = P.handle_to_sorted[n.a];
-        word = FG_OPND(P.site_vtype[site] == FG_F64 ? FG_OPND_SLOT_F : FG_OPND_SLOT_I, P.site_slot[site]);
+        word = FG_OPND(P.site_vtype[site] == FG_F64 ? FG_OPND_SLOT_F : FG_OPND_SLOT_I, slot_of ? (*slot_of)[site] : P.site_slot[site]);
         imm = 0.0;
     }
     void emit1(uint32_t op, int operand_node) {          // op with one leaf operand
@@ -351,6 +353,38 @@ void fg_program::compile_stmt(const FgStmt &s, std::vector<FgIns> &out, int &tem
     out.push_back(I);
     temp_max = std::max(temp_max, G.temp_max);
     fuse_dots(out, start, pool);
+}
+
+// The results (fg_program_result), after the statements and apart from them: every result is compiled as compile_stmt compiles the
+// factor statement of its expression -- the expression into the accumulator, a temporary when it is no leaf, one FG_OP_FACTOR that
+// reads it, then the same MAC -> FG_OP_DOT fusion -- over a slot file of its own, so that no array a sampler kernel reads changes.
+void fg_program::compile_results() {
+    res_ins.clear(); res_pool.clear(); res_sites.clear(); res_n_ins = 0; res_n_slots = 0;
+    if (results.empty()) return;
+    const int S = (int)sorted_stmt.size();
+    std::vector<int> slot((size_t)std::max(1, S), -1);
+    {
+        std::vector<int> hs;
+        for (const FgResult &r : results) collect_sites(r.root, hs);
+        std::vector<char> used((size_t)std::max(1, S), 0);
+        for (int h : hs) used[handle_to_sorted[h]] = 1;
+        for (int j = 0; j < S; j++) if (used[j]) { slot[j] = (int)res_sites.size(); res_sites.push_back(j); }
+    }
+    int temp_max = (int)res_sites.size();
+    for (const FgResult &r : results) {
+        FgGen G(*this, res_ins, slot, (int)res_sites.size());
+        const size_t start = res_ins.size();
+        FgIns I = FgGen::blank(FG_OP_FACTOR);
+        G.operand(r.root, I.opnd[0], I.imm[0]);
+        res_ins.push_back(I);
+        temp_max = std::max(temp_max, G.temp_max);
+        fuse_dots(res_ins, start, res_pool);
+    }
+    res_n_slots = temp_max + 1;                            // slot temp_max: the always-zero slot
+    res_n_ins = (int)res_ins.size();
+    if (res_pool.empty()) res_pool.push_back(0.0);
+    for (int q = 0; q < 8; q++) res_pool.push_back(0.0);
+    for (int q = 0; q < 2; ++q) res_ins.push_back(FgGen::blank(0xffu));
 }
 
 int fg_program::finalize() {
@@ -782,6 +816,7 @@ int fg_program::finalize() {
     // the kernels prefetch two instructions ahead: keep two readable no-ops past each array
     n_ins = (int)ins.size();
     for (int q = 0; q < 2; ++q) { ins.push_back(FgGen::blank(0xffu)); ins_fast.push_back(FgGen::blank(0xffu)); sub.push_back(FgGen::blank(0xffu)); }
+    compile_results();
     finalized = true;
     return FG_OK;
 }
@@ -861,6 +896,33 @@ int fg_program_factor(fg_program *p, const fg_tok *toks, int n) {
     return FG_OK;
 }
 int fg_program_finalize(fg_program *p) { if (!p) return FG_E_BAD_ARG; return p->finalize(); }
+
+// one scalar of the model's return value: `A` of Model<A>, the payload of `pure` (model.rs), handed back per draw (hmc.rs:566-583)
+int fg_program_result(fg_program *p, const char *name, const fg_tok *toks, int n) {
+    if (!p) { fg_set_error("fg_program_result: null program"); return FG_E_BAD_ARG; }
+    if (p->finalized) { fg_set_error("fg_program_result: the program is finalized"); return FG_E_STATE; }
+    if (!name || !*name) { fg_set_error("fg_program_result: empty name"); return FG_E_BAD_ARG; }
+    if (!toks || n <= 0) { fg_set_error("fg_program_result: empty expression"); return FG_E_BAD_ARG; }
+    for (const FgResult &r : p->results) if (r.name == name) { fg_set_error(std::string("fg_program_result: duplicate name `") + name + "`"); return FG_E_BAD_ARG; }
+    const int root = p->parse(toks, n);
+    if (root < 0) return FG_E_BAD_ARG;
+    FgResult r; r.name = name; r.root = root;
+    p->results.push_back(r);
+    return (int)p->results.size() - 1;
+}
+int fg_program_n_results(const fg_program *p) { if (!p) return FG_E_BAD_ARG; return (int)p->results.size(); }
+int fg_program_result_name(const fg_program *p, int r, char *buf, int len) {
+    if (!p) return FG_E_BAD_ARG;
+    if (r < 0 || r >= (int)p->results.size()) return FG_ERR_ADDRESS_NOT_FOUND;
+    const std::string &a = p->results[r].name;
+    if (buf && len > 0) { int n = std::min<int>(len - 1, (int)a.size()); std::memcpy(buf, a.data(), n); buf[n] = 0; }
+    return (int)a.size() + 1;
+}
+int fg_program_result_sites(const fg_program *p, int32_t *h_sites, int cap) {
+    if (!p || !p->finalized) { fg_set_error("program is not finalized"); return FG_E_NOT_FINALIZED; }
+    for (int k = 0; h_sites && k < cap && k < (int)p->res_sites.size(); k++) h_sites[k] = p->res_sites[k];
+    return (int)p->res_sites.size();
+}
 
 #define NEED_FINAL(p) do { if (!(p) || !(p)->finalized) { fg_set_error("program is not finalized"); return FG_E_NOT_FINALIZED; } } while (0)
 int fg_program_n_sites(const fg_program *p) { NEED_FINAL(p); return (int)p->sorted_stmt.size(); }

@@ -21,6 +21,7 @@ struct FgStmt {
     int handle = -1, sorted = -1;
     bool exact_bounds = false; long long lo = 0, hi = 0;   // DiscreteUniform with exact i64 bounds
 };
+struct FgResult { std::string name; int root = -1; };   // one scalar of the model's return value (`pure(..)`): a named expression root
 struct fg_program {
     std::vector<std::vector<double>> data;
     std::vector<std::string> data_names;
@@ -54,11 +55,19 @@ struct fg_program {
     int n_slots = 0, n_ins = 0;
     std::vector<int> site_cat;               // [S][2] {pool base, K} of Categorical sites with a valid constant table, else -1
     std::vector<std::string> dsl_warnings;   // fg_dsl.cpp
+    // the model's return value (fg_program_result): compiled apart from the statements -- an instruction list, a constant pool and a compact
+    // slot numbering of their own (the sites some result reads, then the temporaries, then the always-zero slot); one FG_OP_FACTOR per result
+    // hands its value over, as the factor statement of the same expression would
+    std::vector<FgResult> results;
+    std::vector<FgIns> res_ins; int res_n_ins = 0, res_n_slots = 0;
+    std::vector<double> res_pool;
+    std::vector<int> res_sites;              // sorted site indices the results read, ascending: slot k holds site res_sites[k]
 
     int  parse(const fg_tok *toks, int n);
     void collect_sites(int node, std::vector<int> &out) const;
     void compile_stmt(const FgStmt &s, std::vector<FgIns> &out, int &temp_max);
     int  finalize();
+    void compile_results();
 };
 void fg_set_error(const std::string &s);
 bool fg_categorical_const_valid(const std::vector<double> &p);

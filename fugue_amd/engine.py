@@ -95,6 +95,7 @@ ABI_SYMBOLS = [
     "fg_diag_stream_rhat_ess", "fg_diag_stream_free",
     "fg_diag_qstream_new", "fg_diag_qstream_update", "fg_diag_qstream_count", "fg_diag_qstream_end_pass", "fg_diag_qstream_passes",
     "fg_diag_qstream_result", "fg_diag_qstream_free",
+    "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
 ]
 
 _lib = None
@@ -142,6 +143,11 @@ def lib():
     L.fg_program_site_name.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
     for f in ("fg_program_site_vtype", "fg_program_site_of_handle", "fg_program_f64_site", "fg_program_dep_count", "fg_program_stream_records"):
         getattr(L, f).argtypes = [vp, C.c_int]
+    L.fg_program_result.argtypes = [vp, C.c_char_p, tp, C.c_int]
+    L.fg_program_n_results.argtypes = [vp]
+    L.fg_program_result_name.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+    L.fg_program_result_sites.argtypes = [vp, ip, C.c_int]
+    L.fg_result_eval.argtypes = [vp, vp, C.c_int, ip, C.c_int, vp]
     L.fg_engine_new.restype = vp
     L.fg_engine_new.argtypes = [vp, C.c_int64, C.c_uint64, C.c_uint32, C.c_int]
     L.fg_engine_free.argtypes = [vp]
@@ -305,6 +311,7 @@ class CompiledProgram:
         L = lib()
         self.program = program
         self.warnings: List[str] = []
+        self.result_skipped: List[str] = []      # leaves of the model's return value that are no expression (or that the builder refused)
         if _handle is not None:           # already finalized by a native front-end (fg_dsl_compile)
             self.h = _handle
             self._describe()
@@ -340,6 +347,17 @@ class CompiledProgram:
                 _postfix(st.value, vt)
                 _check(L.fg_program_observe(self.h, st.addr.encode("utf-8"), st.dist.kind, _tok_array(toks), plen,
                                             len(lens), _tok_array(vt), len(vt)))
+        # the model's return value (`pure(..)`, model.rs; hmc.rs:566-583 hands it back per draw): one result per scalar leaf
+        names, exprs, self.result_skipped = M.flatten_result(program.result)
+        for name, ex in zip(names, exprs):
+            rt: List[fg_tok] = []
+            try:
+                _postfix(ex, rt)
+                rc = L.fg_program_result(self.h, name.encode("utf-8"), _tok_array(rt), len(rt))
+            except (KeyError, RecursionError):
+                rc = FG_E_BAD_ARG
+            if rc < 0:
+                self.result_skipped.append(name)
         rc = L.fg_program_finalize(self.h)
         if rc != 0:
             msg = last_error()
@@ -378,6 +396,13 @@ class CompiledProgram:
         self.f64_sites = [L.fg_program_f64_site(self.h, k) for k in range(self.d)]
         self.dep_counts = [L.fg_program_dep_count(self.h, k) for k in range(self.d)]
         self.stream_records = tuple(L.fg_program_stream_records(self.h, w) for w in range(3))   # (gradient, score, kinds)
+        self.R = L.fg_program_n_results(self.h)
+        self.result_names = []
+        for r in range(self.R):
+            L.fg_program_result_name(self.h, r, buf, 4096)
+            self.result_names.append(buf.value.decode("utf-8"))
+        rs = (C.c_int32 * max(1, self.S))()
+        self.result_sites = list(rs[:L.fg_program_result_sites(self.h, rs, self.S)])   # sorted site indices some result reads
 
     def site_of_handle(self, h: int) -> int:
         return lib().fg_program_site_of_handle(self.h, h)
@@ -455,6 +480,31 @@ class Engine:
         logp = np.zeros((max(1, self.S), self.C)) if want_logp else None
         _check(lib().fg_log_joint(self.h, _dp(acc), _dp(logp) if want_logp else None))
         return (acc, logp[:self.S]) if want_logp else acc
+
+    def result_eval(self, d_draws: Optional[int], n: int, rows: Optional[Sequence[int]] = None, out: Optional[int] = None) -> int:
+        """`fg_result_eval`: the model's return value for every draw and chain of the device buffer d_draws [n][n_rows][C] (row j =
+        sorted site rows[j]; rows=None: the HMC draw layout, the d f64 sites) into the device buffer `out` [n][R][C] (allocated here
+        when None: the caller frees it), asynchronously.  d_draws=None with n=1 evaluates at the engine's current values."""
+        n = int(n)
+        if out is None:
+            out = self.device_alloc(max(1, n * self.cp.R * self.C) * 8)
+        if d_draws is None:
+            rp, n_rows = None, 0
+        elif rows is None:
+            rp, n_rows = None, self.d
+        else:
+            rows = list(rows)
+            rp, n_rows = (C.c_int32 * max(1, len(rows)))(*rows), len(rows)
+        _check(lib().fg_result_eval(self.h, d_draws, n, rp, n_rows, out))
+        return out
+
+    def result_values(self) -> np.ndarray:
+        """The model's return value at the engine's current values, [R][C] (a particle's `A`; HmcSession::result, hmc.rs:761)."""
+        out = self.result_eval(None, 1)
+        try:
+            return self.download(out, (self.cp.R, self.C))
+        finally:
+            self.device_free(out)
 
     def log_joint_stream(self, want_records: bool = False):
         """ScoreGivenTrace over the score stream: acc [3][C] (and every statement's log-density [n_records][C])."""

@@ -69,6 +69,13 @@ class ChainBatch:
     accept_rate: float = 0.0
     mean_step_size: float = float("nan")
     n_divergent: int = 0
+    result_names: List[str] = field(default_factory=list)    # the scalars of the model's return value `A` (CompiledProgram.result_names)
+    results: Optional[np.ndarray] = None                      # [n_samples][R][n_chains] float64, evaluated on the device; None when R = 0
+
+    def get_result(self, name: str) -> np.ndarray:            # the `A` half of every (A, Trace): [n_samples][n_chains]
+        if name not in self.result_names:
+            raise M.FugueError(f"result not found: {name}", M.ErrorCode.TraceAddressNotFound)
+        return self.results[:, self.result_names.index(name), :]
 
     def _row(self, address: str) -> int:
         if address not in self.sites:
@@ -97,9 +104,16 @@ class SMCResult:
     log_weights: np.ndarray
     log_evidence: float
     betas: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    result_names: List[str] = field(default_factory=list)    # the scalars of the model's return value `A`
+    results: Optional[np.ndarray] = None                      # [R][n_particles] float64: every particle's `A`; None when R = 0
 
     def get_f64(self, address: str) -> np.ndarray:
         return np.ascontiguousarray(self.cells[self.sites.index(address)]).view(np.float64)
+
+    def get_result(self, name: str) -> np.ndarray:
+        if name not in self.result_names:
+            raise M.FugueError(f"result not found: {name}", M.ErrorCode.TraceAddressNotFound)
+        return self.results[self.result_names.index(name)]
 
 
 def _compile(model_fn) -> E.CompiledProgram:
@@ -112,21 +126,28 @@ def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Option
     cfg = config or HMCConfig()
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     cells = np.zeros((n_samples, cp.S, n_chains), dtype=np.int64)
+    results = np.zeros((n_samples, cp.R, n_chains)) if cp.R > 0 else None
     if cp.d == 0:                                               # no continuous site: every step is a fresh prior draw (hmc.rs:826-845)
         eng.hmc_init(cfg.raw(), n_warmup)
         eng.hmc_step(n_warmup)
         for t in range(n_samples):
             eng.hmc_step(1)
             cells[t] = eng.get_values()
+            if cp.R > 0:
+                results[t] = eng.result_values()
         st = eng.hmc_stats()
     else:
         buf = eng.device_alloc(max(1, n_samples * cp.d * n_chains) * 8)
         st = eng.hmc_run(cfg.raw(), n_samples, n_warmup, buf)
         draws = eng.download(buf, (n_samples, cp.d, n_chains), dtype=np.int64)
+        if cp.R > 0 and n_samples > 0:                          # the `A` of every draw, from the draws where they lie (discrete sites: the engine's values)
+            rbuf = eng.result_eval(buf, n_samples)
+            results = eng.download(rbuf, (n_samples, cp.R, n_chains))
+            eng.device_free(rbuf)
         eng.device_free(buf)
         cells[:] = eng.get_values()[None]                       # HMC moves the f64 sites; discrete sites keep their prior draw (hmc.rs:238-260)
         cells[:, cp.f64_sites, :] = draws
-    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, st.mean_step_size, int(st.n_divergent))
+    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, st.mean_step_size, int(st.n_divergent), list(cp.result_names), results)
     eng.close()
     return out
 
@@ -151,8 +172,17 @@ def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_wa
     buf = eng.device_alloc(max(1, n_samples * cp.S * n_chains) * 8)
     st = eng.mh_run(n_samples, n_warmup, ov, rec, buf)
     cells = eng.download(buf, (n_samples, cp.S, n_chains), dtype=np.int64)
+    results = None
+    if cp.R > 0:
+        results = np.zeros((n_samples, cp.R, n_chains))
+        if n_samples > 0 and cp.S > 0:
+            rbuf = eng.result_eval(buf, n_samples, rows=rec)
+            results = eng.download(rbuf, (n_samples, cp.R, n_chains))
+            eng.device_free(rbuf)
+        elif n_samples > 0:
+            results[:] = eng.result_values()[None]
     eng.device_free(buf)
-    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate)
+    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, result_names=list(cp.result_names), results=results)
     eng.close()
     return out
 
@@ -183,6 +213,7 @@ class ChainSummary:
     quantiles: Optional[np.ndarray] = None
     quantile_probs: Tuple[float, ...] = QUANTILE_PROBS
     passes: int = 1
+    results: Optional["ChainSummary"] = None      # results=True: the same figures of the model's return value, `sites` = the result names
 
 
 def _summary_args(n_samples: int, chunk: int, max_lag: int):
@@ -195,63 +226,101 @@ def _summary_args(n_samples: int, chunk: int, max_lag: int):
 
 
 def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
-                    after_first_pass=None):
+                    after_first_pass=None, result_rows=False):
     """step(n, buf) records n draws [n][d][C] into buf; one chunk buffer is alive at a time.  quantiles: the state after warmup is
     exported, the first sampling pass feeds the diagnostics stream and a quantile stream, `after_first_pass()` reads the sampler's
     statistics, and while the quantile stream wants another pass the blob is imported into the same engine and the same chunks are
-    stepped again for the quantile stream alone."""
+    stepped again for the quantile stream alone.  result_rows (None: the HMC draw layout, or the sorted sites of buf's rows) asks for
+    the model's return value too: every chunk is turned into one reused [chunk][R][C] buffer of results (`Engine.result_eval`) that
+    feeds a second pair of streams of dimension R; a replay pass evaluates the results again."""
     chunk = min(chunk, n_samples)
+    with_results = result_rows is not False
+    R = eng.cp.R
     stream = eng.diag_stream(n_samples, d, max_lag)
-    qs, buf = None, None
+    qs, buf, rstream, rqs, rbuf = None, None, None, None, None
     try:
         blob = None
+        if with_results:
+            rstream = eng.diag_stream(n_samples, R, max_lag)
         if quantiles:
             qs = eng.diag_qstream(n_samples, d, QUANTILE_PROBS, capacity=quantile_capacity)
+            if with_results:
+                rqs = eng.diag_qstream(n_samples, R, QUANTILE_PROBS, capacity=quantile_capacity)
             blob = eng.state_export()
         buf = eng.device_alloc(chunk * d * eng.C * 8)
+        if with_results:
+            rbuf = eng.device_alloc(chunk * R * eng.C * 8)
 
-        def one_pass(consumers):
+        def one_pass(consumers, result_consumers=()):
             done = 0
             while done < n_samples:
                 n = min(chunk, n_samples - done)
                 step(n, buf)
                 for c in consumers:
                     c.update(buf, n)
+                if result_consumers:
+                    eng.result_eval(buf, n, rows=result_rows, out=rbuf)
+                    for c in result_consumers:
+                        c.update(rbuf, n)
                 done += n
 
-        one_pass([stream, qs] if quantiles else [stream])
+        one_pass([stream, qs] if quantiles else [stream], [c for c in (rstream, rqs) if c is not None])
         r = stream.rhat_ess()
         out = ChainSummary(list(sites), r["mean"], r["std"], r["r_hat"], r["ess"], n_samples, int(r["chains"]))
+        if with_results:
+            rr = rstream.rhat_ess()
+            out.results = ChainSummary(list(eng.cp.result_names), rr["mean"], rr["std"], rr["r_hat"], rr["ess"], n_samples, int(rr["chains"]))
         if after_first_pass:
             after_first_pass(out)
         if quantiles:
-            while not qs.end_pass():
+            live = [q for q in (qs, rqs) if q is not None and not q.end_pass()]
+            while live:                                    # each selector runs until its own quantiles are decided
                 eng.state_import(blob)
-                one_pass([qs])
+                one_pass([q for q in live if q is qs], [q for q in live if q is rqs])
+                live = [q for q in live if not q.end_pass()]
             out.quantiles, out.passes = qs.result()[0], qs.passes
+            if with_results:
+                out.results.quantiles, out.results.passes = rqs.result()[0], rqs.passes
     finally:
         eng.synchronize()
-        if buf is not None:
-            eng.device_free(buf)
-        stream.close()
-        if qs is not None:
-            qs.close()
+        for b in (buf, rbuf):
+            if b is not None:
+                eng.device_free(b)
+        for s in (stream, qs, rstream, rqs):
+            if s is not None:
+                s.close()
     return out
 
 
+def _want_results(cp, results: bool, recorded=None, who: str = ""):
+    if not results:
+        return
+    if cp.R == 0:
+        raise ValueError(f"{who}: results=True, but the model returns nothing the device can evaluate (CompiledProgram.result_skipped)")
+    if recorded is not None:
+        missing = [cp.site_names[j] for j in cp.result_sites if j not in recorded]
+        if missing:
+            raise ValueError(f"{who}: results=True needs every site a result reads among the recorded f64 sites; {missing} are not "
+                             "(a streamed MH run records its f64 sites only)")
+
+
 def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
-                      chunk: int = 64, max_lag: int = 64, device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536) -> ChainSummary:
+                      chunk: int = 64, max_lag: int = 64, device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536,
+                      results: bool = False) -> ChainSummary:
     """`hmc_chain` for runs longer than memory: the same transitions (`fg_hmc_step` is incremental), `chunk` at a time into one
     draw buffer that a diagnostics stream consumes, and the summary of every f64 site instead of the draws.  `max_lag` bounds how
     far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  `quantiles=True` adds the five quantiles
     of summarize_f64_parameter by exact radix select (`Engine.diag_qstream`): the draws are not kept, so every pass beyond the
     first REPEATS THE SAMPLING PHASE from the state exported after warmup -- about three passes for a long run at the default
     `quantile_capacity` (keys collected per quantile once that few candidates are left; device memory 8 x 5 x n_sites x capacity
-    bytes), `ChainSummary.passes` reports the count.  Every other figure is the one `quantiles=False` gives."""
+    bytes), `ChainSummary.passes` reports the count.  Every other figure is the one `quantiles=False` gives.  `results=True` adds
+    `ChainSummary.results`: the same figures of the model's return value (the `A` of hmc.rs:566-583), evaluated on the device chunk
+    by chunk; the site figures are the ones `results=False` gives."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     if cp.d == 0:
         raise ValueError("hmc_chain_summary: the model has no f64 site to summarise")
+    _want_results(cp, results, who="hmc_chain_summary")
     cfg = config or HMCConfig()
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     try:
@@ -261,7 +330,8 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
             st = eng.hmc_stats()
             out.accept_rate, out.mean_step_size, out.n_divergent = st.accept_rate, st.mean_step_size, int(st.n_divergent)
 
-        out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag, quantiles, quantile_capacity, stats)
+        out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag, quantiles, quantile_capacity, stats,
+                              result_rows=None if results else False)
     finally:
         eng.close()
     return out
@@ -269,16 +339,18 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
 
 def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1,
                                 overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
-                                device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536) -> ChainSummary:
+                                device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536, results: bool = False) -> ChainSummary:
     """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
     only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  `quantiles=True` adds the five
     quantiles as `hmc_chain_summary` does: every pass beyond the first REPEATS THE SAMPLING PHASE from the state exported after
-    warmup (`ChainSummary.passes`)."""
+    warmup (`ChainSummary.passes`).  `results=True` adds `ChainSummary.results` as `hmc_chain_summary` does; every site a result reads
+    must be an f64 site (the recorded ones: a discrete site moves under MH and is not in the chunk)."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     rec = list(cp.f64_sites)
     if not rec:
         raise ValueError("adaptive_mcmc_chain_summary: the model has no f64 site to summarise")
+    _want_results(cp, results, rec, "adaptive_mcmc_chain_summary")
     ov = _override_rows(cp, overrides)
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     try:
@@ -288,7 +360,7 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
             out.accept_rate = eng.mh_stats().accept_rate
 
         out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in rec], len(rec), n_samples, chunk, max_lag,
-                              quantiles, quantile_capacity, stats)
+                              quantiles, quantile_capacity, stats, result_rows=rec if results else False)
     finally:
         eng.close()
     return out
@@ -298,9 +370,11 @@ def adaptive_smc(seed: int, num_particles: int, model_fn, config: Optional[SMCCo
     cp = _compile(model_fn)
     cfg = config or SMCConfig()
     if num_particles == 0:                                         # smc.rs:462-467
-        return SMCResult(list(cp.site_names), list(cp.site_vtypes), np.zeros((cp.S, 0), dtype=np.int64), np.zeros(0), np.zeros(0), 0.0)   # empty population: log_evidence 0.0
+        return SMCResult(list(cp.site_names), list(cp.site_vtypes), np.zeros((cp.S, 0), dtype=np.int64), np.zeros(0), np.zeros(0), 0.0,   # empty population: log_evidence 0.0
+                         result_names=list(cp.result_names), results=np.zeros((cp.R, 0)) if cp.R > 0 else None)
     eng = E.Engine(cp, num_particles, seed=seed, device=device)
     r = eng.smc_run(cfg.resampling_method, cfg.ess_threshold, cfg.rejuvenation_steps)
-    out = SMCResult(list(cp.site_names), list(cp.site_vtypes), r["values"], r["weights"], r["log_w"], r["log_evidence"], r["betas"])
+    out = SMCResult(list(cp.site_names), list(cp.site_vtypes), r["values"], r["weights"], r["log_w"], r["log_evidence"], r["betas"],
+                    list(cp.result_names), eng.result_values() if cp.R > 0 else None)
     eng.close()
     return out

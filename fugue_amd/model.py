@@ -518,6 +518,32 @@ def trace_model(model_or_fn, program: Optional[Program] = None) -> Program:
         m = m.k(v) if m.k else pure(v)
 
 
+def flatten_result(result):
+    """The model's return value `A` (the payload of `pure(..)`, model.rs) as named scalars: a top-level expression or real number is
+    `result`; a tuple or list gives `result[0]`, `result[1][0]`, ...; a dict with string keys gives `result.key` in insertion order.
+    Returns (names, expressions, skipped): a leaf that is neither an `Expr` nor a real number (None, a `Cond`, a string, ...) means
+    nothing to the device and is listed in `skipped` by name -- never an error."""
+    import numbers
+    names, exprs, skipped = [], [], []
+
+    def walk(v, name):
+        if isinstance(v, Expr):
+            names.append(name); exprs.append(v)
+        elif isinstance(v, (numbers.Real, np.bool_)):
+            names.append(name); exprs.append(as_expr(v))
+        elif isinstance(v, (tuple, list)):
+            for i, x in enumerate(v):
+                walk(x, f"{name}[{i}]")
+        elif isinstance(v, dict) and all(isinstance(k, str) for k in v):
+            for k, x in v.items():
+                walk(x, f"{name}.{k}")
+        else:
+            skipped.append(name)
+
+    walk(result, "result")
+    return names, exprs, skipped
+
+
 def _wants_program(fn) -> bool:
     import inspect
     try:

@@ -93,6 +93,12 @@ class MhSession:
     def log_weights(self) -> np.ndarray:                         # mh.rs:180-185
         return self.eng.mh_log_weight()
 
+    def result_names(self) -> List[str]:
+        return list(self.cp.result_names)
+
+    def result(self) -> np.ndarray:                              # the model's return value at every chain's current state: [R][chains]
+        return self.eng.result_values()
+
     def _draws(self, site: str, window: int = 0) -> Optional[np.ndarray]:
         j = self._row(site)
         if j is None or self.hist.buf.shape[0] == 0:
@@ -182,6 +188,12 @@ class HmcSession:
 
     def step_size(self) -> np.ndarray:                           # hmc.rs:133-136 (one per chain)
         return self.eng.hmc_step_sizes()
+
+    def result_names(self) -> List[str]:
+        return list(self.cp.result_names)
+
+    def result(self) -> np.ndarray:                              # HmcSession::result (hmc.rs:761): the model's return value at the current state, [R][chains]
+        return self.eng.result_values()
 
     def values(self, site: str) -> np.ndarray:                   # hmc.rs:138-146: [retained states][chains], every transition since the session began
         if site not in self._names:

@@ -119,6 +119,19 @@ int fg_program_dep_count(const fg_program *p, int k);
  * 3: records of the register-resident trajectory kernel (> 0 only for independent-sites programs: every force term reads
  *    one coordinate and constants) */
 int fg_program_stream_records(const fg_program *p, int which);
+/* The model's return value: the `A` of `Model<A>` that `pure(a)` closes a model with (src/core/model.rs:20-131, `pure`) and that
+ * every driver hands back next to the trace, `Vec<(A, Trace)>` (src/inference/hmc.rs:566-583).  A result is one named postfix
+ * expression over the token set of a parameter expression (FG_T_CONST .. FG_T_SELECT); it is compiled like the expression of a
+ * `factor(..)` statement (same constant folding, same fused linear predictors) into an instruction list of its own and changes
+ * nothing of the program's statements.  Before fg_program_finalize; returns the result index r >= 0 (registration order).
+ * FG_E_STATE after finalize; FG_E_BAD_ARG for a malformed token stream, an unknown site handle, an empty or a duplicate name. */
+int fg_program_result(fg_program *p, const char *name_utf8, const fg_tok *toks, int n);
+int fg_program_n_results(const fg_program *p);    /* R: the scalar components of `A` (model.rs `pure`) */
+/* name of result r (model.rs `pure`), like fg_program_site_name: returns bytes needed incl. NUL */
+int fg_program_result_name(const fg_program *p, int r, char *buf, int buf_len);
+/* after finalize: the sorted site indices some result reads (model.rs `pure`: the sampled values `A` is computed from), ascending;
+ * writes the first min(count, cap) of them and returns the count */
+int fg_program_result_sites(const fg_program *p, int32_t *h_sites, int cap);
 
 const char *fg_last_error(void);
 int         fg_abi_version(void);
@@ -165,6 +178,15 @@ int fg_log_joint(fg_engine *e, double *h_acc, double *h_logp);
  * fg_program_stream_records(p, 1): the log-density of every statement.  FG_E_UNSUPPORTED when the program has no
  * score stream. */
 int fg_log_joint_stream(fg_engine *e, double *h_acc, double *h_rec_lp);
+/* The model's return value `A` for every draw and chain -- the first half of each `(A, Trace)` pair hmc_chain / adaptive_mcmc_chain
+ * return (src/inference/hmc.rs:566-583, mh.rs:921-944) and the value a Particle's trace gives (smc.rs) -- evaluated on the device:
+ * d_draws [n][n_rows][C] 8-byte cells -> d_out [n][R][C] doubles, R = fg_program_n_results.  Row j of a draw holds sorted site
+ * h_rows[j]; h_rows == NULL is the HMC draw layout (n_rows must be d: the f64 sites in coordinate order, as fg_hmc_step records them).
+ * A site that a result reads and that is not among the rows is read from the engine's current values [S][C] (HMC moves only the f64
+ * sites).  d_draws == NULL with n == 1 and n_rows == 0 evaluates at the current values alone (particles; HmcSession::result,
+ * hmc.rs:761).  Integer sites enter as f64 like FG_T_SITE.  Asynchronous on the engine's stream; n == 0 is FG_OK without a launch.
+ * FG_E_STATE: the program has no result; FG_E_BAD_ARG: a row index outside [0, S) or given twice, n_rows != d without h_rows. */
+int fg_result_eval(fg_engine *e, const void *d_draws, int n, const int32_t *h_rows, int n_rows, double *d_out);
 
 /* ------------------------------------------------------------------ HMC
  * Replaces hmc_chain / HmcSession (src/inference/hmc.rs:566-583, 643-920). */

@@ -84,6 +84,11 @@ extern "C" {
     pub fn fg_program_site_of_handle(p: *const fg_program, h: c_int) -> c_int;
     pub fn fg_program_f64_site(p: *const fg_program, k: c_int) -> c_int;
     pub fn fg_program_stream_records(p: *const fg_program, which: c_int) -> c_int;
+    // the model's return value, `A` of Model<A> (model.rs `pure`; hmc.rs:566-583 returns it with every trace)
+    pub fn fg_program_result(p: *mut fg_program, name_utf8: *const c_char, toks: *const fg_tok, n: c_int) -> c_int;
+    pub fn fg_program_n_results(p: *const fg_program) -> c_int;
+    pub fn fg_program_result_name(p: *const fg_program, r: c_int, buf: *mut c_char, buf_len: c_int) -> c_int;
+    pub fn fg_program_result_sites(p: *const fg_program, h_sites: *mut i32, cap: c_int) -> c_int;
     pub fn fg_dsl_compile(source_utf8: *const c_char, data_json_utf8: *const c_char) -> *mut fg_program;
     // ---- engine
     pub fn fg_engine_new(p: *const fg_program, n_chains: i64, seed: u64, chain_offset: u32, device: c_int) -> *mut fg_engine;
@@ -93,6 +98,7 @@ extern "C" {
     pub fn fg_engine_get_values(e: *mut fg_engine, h_cells: *mut c_void) -> c_int;
     pub fn fg_prior_init(e: *mut fg_engine, iteration: u32, h_acc: *mut f64) -> c_int;
     pub fn fg_log_joint(e: *mut fg_engine, h_acc: *mut f64, h_logp: *mut f64) -> c_int;
+    pub fn fg_result_eval(e: *mut fg_engine, d_draws: *const c_void, n: c_int, h_rows: *const i32, n_rows: c_int, d_out: *mut f64) -> c_int;
     // ---- HMC (hmc.rs:566-583, 643-920)
     pub fn fg_hmc_config_default(cfg: *mut fg_hmc_config);
     pub fn fg_hmc_init(e: *mut fg_engine, cfg: *const fg_hmc_config, n_warmup: c_int) -> c_int;
