@@ -95,6 +95,8 @@ ABI_SYMBOLS = [
     "fg_diag_stream_rhat_ess", "fg_diag_stream_free",
     "fg_diag_qstream_new", "fg_diag_qstream_update", "fg_diag_qstream_count", "fg_diag_qstream_end_pass", "fg_diag_qstream_passes",
     "fg_diag_qstream_result", "fg_diag_qstream_free",
+    "fg_diag_cstream_new", "fg_diag_cstream_update", "fg_diag_cstream_count", "fg_diag_cstream_result", "fg_diag_cstream_free",
+    "fg_diag_cells_f64",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
 ]
 
@@ -232,6 +234,13 @@ def lib():
     L.fg_diag_qstream_result.argtypes = [vp, dp, C.POINTER(C.c_int32)]
     L.fg_diag_qstream_free.restype = None
     L.fg_diag_qstream_free.argtypes = [vp]
+    L.fg_diag_cstream_new.argtypes = [vp, C.c_int, C.c_int, ip, ip, C.POINTER(C.c_int64), ip, C.c_int, C.POINTER(vp)]
+    L.fg_diag_cstream_update.argtypes = [vp, vp, C.c_int]
+    L.fg_diag_cstream_count.argtypes = [vp]
+    L.fg_diag_cstream_result.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.fg_diag_cstream_free.restype = None
+    L.fg_diag_cstream_free.argtypes = [vp]
+    L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
     L.fg_mh_last_kernel.restype = C.c_char_p
@@ -785,6 +794,25 @@ class Engine:
         presented once per pass (the sampling phase replayed from `state_export`'s blob), until `end_pass()` returns True."""
         return DiagQuantileStream(self, n_total, d, probs, digit_bits, capacity)
 
+    def diag_cstream(self, n_total: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], lo: Sequence[int], bins: Sequence[int]) -> "DiagCountStream":
+        """A `fg_diag_cstream`: exact frequency tables of the integer rows `rows` of chunks [n_chunk][n_rec][C] of cells (what
+        `mh_step` records) for a run of `n_total` draws that is never stored.  Row k has the ChoiceValue tag vtypes[k] and counts the
+        cells equal to lo[k] + j in bin j of bins[k]; whatever lies outside is counted in `below` / `above`."""
+        return DiagCountStream(self, n_total, n_rec, rows, vtypes, lo, bins)
+
+    def cells_f64(self, d_cells: int, n: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], out: Optional[int] = None) -> int:
+        """`fg_diag_cells_f64`: rows `rows` of the device cells [n][n_rec][C] as doubles [n][len(rows)][C] in the device buffer `out`
+        (allocated here when None: the caller frees it), asynchronously: an f64 row is copied, a u64 row converted as unsigned
+        (`x as f64`), bool / usize / i64 rows as signed.  The layout `diag_stream` and `diag_qstream` take."""
+        rows, vtypes = [int(r) for r in rows], [int(v) for v in vtypes]
+        if len(rows) != len(vtypes) or not rows:
+            raise ValueError("rows and vtypes must have one entry per selected row, at least one")
+        n = int(n)
+        if out is None:
+            out = self.device_alloc(max(1, n * len(rows) * self.C) * 8)
+        _check(lib().fg_diag_cells_f64(self.h, d_cells, n, int(n_rec), (C.c_int32 * len(rows))(*rows), (C.c_int32 * len(rows))(*vtypes), len(rows), out))
+        return out
+
     def hmc_last_kernel(self) -> str:
         """Kernel (and waves per tile) the engine's last HMC launch ran."""
         return (lib().fg_hmc_last_kernel(self.h) or b"").decode()
@@ -962,6 +990,73 @@ class DiagQuantileStream:
         if getattr(self, "h", None):
             if getattr(self.engine, "h", None):          # the state lives in the engine's device context
                 lib().fg_diag_qstream_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DiagCountStream:
+    """`fg_diag_cstream` (fg_diag_cstream.hip): exact posterior frequency tables of integer rows (the tabulation of the reference's
+    extract_bool_values / extract_u64_values / extract_usize_values / extract_i64_values, diagnostics.rs:76-98) of a run handed over
+    in chunks of cells [n_chunk][n_rec][C].  Integer sums: the result does not depend on the chunking.  Close it before its engine."""
+
+    def __init__(self, engine: Engine, n_total: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], lo: Sequence[int], bins: Sequence[int]):
+        for name, v in (("n_total", n_total), ("n_rec", n_rec)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        self.rows, self.vtypes = [int(r) for r in rows], [int(v) for v in vtypes]
+        self.lo, self.bins = [int(v) for v in lo], [int(b) for b in bins]
+        nw = len(self.rows)
+        if not (nw == len(self.vtypes) == len(self.lo) == len(self.bins)):
+            raise ValueError("rows, vtypes, lo and bins must have one entry per watched row")
+        if not 1 <= nw <= 65535:
+            raise ValueError("between 1 and 65535 watched rows")
+        if any(not -2 ** 63 <= v < 2 ** 63 for v in self.lo):
+            raise ValueError("lo must fit 64 signed bits")
+        self.engine, self.n, self.n_rec = engine, int(n_total), int(n_rec)
+        self.h = None
+        out = C.c_void_p()
+        i32 = lambda v: (C.c_int32 * nw)(*v)
+        _check(lib().fg_diag_cstream_new(engine.h, self.n, self.n_rec, i32(self.rows), i32(self.vtypes), (C.c_int64 * nw)(*self.lo), i32(self.bins), nw, C.byref(out)))
+        self.h = out.value
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the stream is closed")
+        return self.h
+
+    def update(self, d_cells: int, n_chunk: int):
+        """The next `n_chunk` draws, a device buffer of cells [n_chunk][n_rec][C]."""
+        _check(lib().fg_diag_cstream_update(self._handle(), d_cells, int(n_chunk)))
+
+    @property
+    def count(self) -> int:
+        return int(lib().fg_diag_cstream_count(self._handle()))
+
+    def result(self) -> dict:
+        """counts: a list of uint64 arrays [bins[k]]; below / above: uint64 [n_watch]; min / max: lists of Python ints [n_watch]
+        (a u64 row's are unsigned, so they may pass 2^63).  Raises EngineError (FG_E_STATE) before
+        `n_total` draws have arrived or when a row's total is not n_total x C."""
+        nw = len(self.rows)
+        flat = np.zeros(max(1, sum(self.bins)), dtype=np.uint64)
+        below, above = np.zeros(nw, dtype=np.uint64), np.zeros(nw, dtype=np.uint64)
+        mn, mx = np.zeros(nw, dtype=np.int64), np.zeros(nw, dtype=np.int64)
+        u64p, i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+        _check(lib().fg_diag_cstream_result(self._handle(), flat.ctypes.data_as(u64p), below.ctypes.data_as(u64p), above.ctypes.data_as(u64p),
+                                            mn.ctypes.data_as(i64p), mx.ctypes.data_as(i64p)))
+        at = np.concatenate([[0], np.cumsum(self.bins)])
+        counts = [flat[at[k]:at[k + 1]].copy() for k in range(nw)]
+        unsigned = lambda a: [int(v) & (2 ** 64 - 1) if self.vtypes[k] == M.U64 else int(v) for k, v in enumerate(a)]
+        return dict(counts=counts, below=below, above=above, min=unsigned(mn), max=unsigned(mx))
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
+                lib().fg_diag_cstream_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -12,7 +12,7 @@ counter-based, so a `seed` replaces it (results do not depend on how chains are 
 `ChainBatch` / `SMCResult`, the many-chain form of `Vec<(A, Trace)>` / `Vec<Particle>`: `get_f64(addr)` etc. return
 every chain's values of a site."""
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -214,6 +214,32 @@ class ChainSummary:
     quantile_probs: Tuple[float, ...] = QUANTILE_PROBS
     passes: int = 1
     results: Optional["ChainSummary"] = None      # results=True: the same figures of the model's return value, `sites` = the result names
+    discrete: Optional["DiscreteSummary"] = None  # adaptive_mcmc_chain_summary(discrete=True): the frequency tables of the discrete sites
+
+
+@dataclass
+class DiscreteSummary:
+    """The discrete sites of a run whose draws were never stored (`adaptive_mcmc_chain_summary(discrete=True)`): what a caller of
+    the reference tabulates from extract_bool_values / extract_u64_values / extract_usize_values / extract_i64_values
+    (diagnostics.rs:76-98).  Per site of `sites` (tags `vtypes`): `counts[k][j]` draws equal to `lo[k] + j`, `below[k]` / `above[k]`
+    draws outside the bins, the smallest and largest value seen (`min`, `max`: Python ints), all exact.  `numeric` holds what
+    Diagnostics<u64> (diagnostics.rs:153-191) gives the u64 sites through `x as f64`: mean / std / split R-hat / ESS (and the
+    quantiles when asked); bool, usize and i64 sites get tables only, as in the reference."""
+    sites: List[str]
+    vtypes: List[int]
+    lo: List[int]
+    counts: List[np.ndarray]
+    below: np.ndarray
+    above: np.ndarray
+    min: List[int]
+    max: List[int]
+    n_samples: int
+    n_chains: int
+    numeric: Optional[ChainSummary] = None
+
+    def probs(self) -> List[np.ndarray]:
+        """counts / (n_samples x n_chains): the posterior frequency of every bin (below / above are not in it)."""
+        return [c.astype(np.float64) / float(self.n_samples * self.n_chains) for c in self.counts]
 
 
 def _summary_args(n_samples: int, chunk: int, max_lag: int):
@@ -225,70 +251,131 @@ def _summary_args(n_samples: int, chunk: int, max_lag: int):
         raise ValueError("max_lag must lie in [1, 2048]")
 
 
-def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
-                    after_first_pass=None, result_rows=False):
-    """step(n, buf) records n draws [n][d][C] into buf; one chunk buffer is alive at a time.  quantiles: the state after warmup is
-    exported, the first sampling pass feeds the diagnostics stream and a quantile stream, `after_first_pass()` reads the sampler's
-    statistics, and while the quantile stream wants another pass the blob is imported into the same engine and the same chunks are
-    stepped again for the quantile stream alone.  result_rows (None: the HMC draw layout, or the sorted sites of buf's rows) asks for
-    the model's return value too: every chunk is turned into one reused [chunk][R][C] buffer of results (`Engine.result_eval`) that
-    feeds a second pair of streams of dimension R; a replay pass evaluates the results again."""
-    chunk = min(chunk, n_samples)
-    with_results = result_rows is not False
-    R = eng.cp.R
-    stream = eng.diag_stream(n_samples, d, max_lag)
-    qs, buf, rstream, rqs, rbuf = None, None, None, None, None
-    try:
-        blob = None
-        if with_results:
-            rstream = eng.diag_stream(n_samples, R, max_lag)
-        if quantiles:
-            qs = eng.diag_qstream(n_samples, d, QUANTILE_PROBS, capacity=quantile_capacity)
-            if with_results:
-                rqs = eng.diag_qstream(n_samples, R, QUANTILE_PROBS, capacity=quantile_capacity)
-            blob = eng.state_export()
-        buf = eng.device_alloc(chunk * d * eng.C * 8)
-        if with_results:
-            rbuf = eng.device_alloc(chunk * R * eng.C * 8)
+def _default_bins(cp, j: int) -> Tuple[int, int]:
+    """(lo, bins) of discrete site j where the program states its support with constant parameters, else (0, 64)."""
+    prog = cp.program
+    if prog is not None:
+        for st in prog.stmts:
+            if st.kind != M.SAMPLE or st.addr != cp.site_names[j]:
+                continue
+            name, par = st.dist.name, [M._cval(p) for p in st.dist.params]
+            if name == "Bernoulli":
+                return 0, 2
+            if name == "Categorical":
+                return 0, len(par)
+            if name == "DiscreteUniform":
+                b = st.dist.i64_bounds or (tuple(int(v) for v in par) if all(v is not None and float(v).is_integer() for v in par) else None)
+                if b is not None:
+                    return int(b[0]), int(min(b[1] - b[0] + 1, 4096))
+            if name == "Binomial" and par[0] is not None:
+                return 0, int(min(int(par[0]) + 1, 4096))
+    return 0, 64
 
-        def one_pass(consumers, result_consumers=()):
+
+def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
+                    after_first_pass=None, result_rows=False, discrete_bins=False):
+    """step(n, buf) records n draws into buf; one chunk buffer is alive at a time.  A chunk is seen through FEEDS: a view of it as
+    doubles [n][rows][C] and the diagnostics stream (with quantiles: and the quantile stream) that take the view.
+      - discrete_bins False: buf is [n][d][C] doubles (the f64 sites `sites`) and is its own view.
+      - discrete_bins a dict (discrete=True): buf holds EVERY site as cells [n][S][C].  `Engine.cells_f64` gathers the f64 rows into one
+        view and the u64 rows (`x as f64`) into a second, each with streams of its own -- the f64 streams are handed exactly the rows
+        and values of the other mode, so their figures are those bit for bit -- and a count stream watches every non-f64 row.
+      - result_rows (None: the HMC draw layout, or the sorted sites of buf's rows) adds the model's return value: every chunk is turned
+        into one reused [chunk][R][C] buffer (`Engine.result_eval`), a third view.
+    quantiles: the state after warmup is exported, the first sampling pass feeds every stream, `after_first_pass()` reads the
+    sampler's statistics, and while a quantile stream wants another pass the blob is imported into the same engine and the same
+    chunks are stepped again for the quantile streams that are still open; the count stream is complete after the first pass."""
+    chunk = min(chunk, n_samples)
+    cp, C_, R = eng.cp, eng.C, eng.cp.R
+    discrete = discrete_bins is not False
+    feeds, streams, buffers, cs = [], [], [], None
+
+    def alloc(words):
+        buffers.append(eng.device_alloc(words * 8))
+        return buffers[-1]
+
+    def feed(names, rows, view):
+        f = dict(names=list(names), view=view, stream=eng.diag_stream(n_samples, rows, max_lag), qs=None)
+        streams.append(f["stream"])
+        if quantiles:
+            f["qs"] = eng.diag_qstream(n_samples, rows, QUANTILE_PROBS, capacity=quantile_capacity)
+            streams.append(f["qs"])
+        feeds.append(f)
+        return f
+
+    def figures(f, names=()):
+        if f is None:                                      # discrete=True on a model without such sites
+            return ChainSummary(list(names), np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0), n_samples, int(C_),
+                                quantiles=np.zeros((0, len(QUANTILE_PROBS))) if quantiles else None)
+        r = f["stream"].rhat_ess()
+        return ChainSummary(f["names"], r["mean"], r["std"], r["r_hat"], r["ess"], n_samples, int(r["chains"]))
+
+    try:
+        main, numeric, w_rows, bins = None, None, [], []
+        if not discrete:
+            main, chunk_rows = feed(sites, d, lambda buf, n: buf), d
+        else:
+            chunk_rows = S = cp.S
+
+            def gathered(rows):
+                vts, dbuf = [cp.site_vtypes[j] for j in rows], alloc(chunk * len(rows) * C_)
+                return feed([cp.site_names[j] for j in rows], len(rows), lambda buf, n: eng.cells_f64(buf, n, S, rows, vts, out=dbuf))
+
+            u_rows = [j for j in range(S) if cp.site_vtypes[j] == M.U64]
+            w_rows = [j for j in range(S) if cp.site_vtypes[j] != M.F64]
+            main = gathered(list(cp.f64_sites)) if cp.f64_sites else None
+            numeric = gathered(u_rows) if u_rows else None
+            bins = [tuple(int(v) for v in (discrete_bins.get(cp.site_names[j]) or _default_bins(cp, j))) for j in w_rows]
+            if w_rows:
+                cs = eng.diag_cstream(n_samples, S, w_rows, [cp.site_vtypes[j] for j in w_rows], [b[0] for b in bins], [b[1] for b in bins])
+                streams.append(cs)
+        res = None
+        if result_rows is not False:
+            rbuf = alloc(chunk * R * C_)
+            res = feed(cp.result_names, R, lambda buf, n: eng.result_eval(buf, n, rows=result_rows, out=rbuf))
+        blob = eng.state_export() if quantiles else None
+        buf = alloc(chunk * chunk_rows * C_)
+
+        def one_pass(live, counters=()):
             done = 0
             while done < n_samples:
                 n = min(chunk, n_samples - done)
                 step(n, buf)
-                for c in consumers:
+                for f in feeds:
+                    mine = [c for c in (f["stream"], f["qs"]) if any(c is x for x in live)]
+                    if mine:
+                        view = f["view"](buf, n)
+                        for c in mine:
+                            c.update(view, n)
+                for c in counters:
                     c.update(buf, n)
-                if result_consumers:
-                    eng.result_eval(buf, n, rows=result_rows, out=rbuf)
-                    for c in result_consumers:
-                        c.update(rbuf, n)
                 done += n
 
-        one_pass([stream, qs] if quantiles else [stream], [c for c in (rstream, rqs) if c is not None])
-        r = stream.rhat_ess()
-        out = ChainSummary(list(sites), r["mean"], r["std"], r["r_hat"], r["ess"], n_samples, int(r["chains"]))
-        if with_results:
-            rr = rstream.rhat_ess()
-            out.results = ChainSummary(list(eng.cp.result_names), rr["mean"], rr["std"], rr["r_hat"], rr["ess"], n_samples, int(rr["chains"]))
+        one_pass([c for f in feeds for c in (f["stream"], f["qs"]) if c is not None], [cs] if cs is not None else [])
+        out = figures(main, sites)
+        if res is not None:
+            out.results = figures(res)
+        if discrete:
+            tab = cs.result() if cs is not None else dict(counts=[], below=np.zeros(0, dtype=np.uint64), above=np.zeros(0, dtype=np.uint64), min=[], max=[])
+            out.discrete = DiscreteSummary([cp.site_names[j] for j in w_rows], [cp.site_vtypes[j] for j in w_rows], [b[0] for b in bins], tab["counts"],
+                                           tab["below"], tab["above"], tab["min"], tab["max"], n_samples, int(C_), figures(numeric) if numeric else None)
         if after_first_pass:
             after_first_pass(out)
         if quantiles:
-            live = [q for q in (qs, rqs) if q is not None and not q.end_pass()]
+            live = [f["qs"] for f in feeds if not f["qs"].end_pass()]
             while live:                                    # each selector runs until its own quantiles are decided
                 eng.state_import(blob)
-                one_pass([q for q in live if q is qs], [q for q in live if q is rqs])
+                one_pass(live)
                 live = [q for q in live if not q.end_pass()]
-            out.quantiles, out.passes = qs.result()[0], qs.passes
-            if with_results:
-                out.results.quantiles, out.results.passes = rqs.result()[0], rqs.passes
+            for f, target in ((main, out), (numeric, out.discrete.numeric if discrete else None), (res, out.results)):
+                if f is not None:
+                    target.quantiles, target.passes = f["qs"].result()[0], f["qs"].passes
     finally:
         eng.synchronize()
-        for b in (buf, rbuf):
-            if b is not None:
-                eng.device_free(b)
-        for s in (stream, qs, rstream, rqs):
-            if s is not None:
-                s.close()
+        for b in buffers:
+            eng.device_free(b)
+        for st in streams:
+            st.close()
     return out
 
 
@@ -339,18 +426,39 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
 
 def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1,
                                 overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
-                                device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536, results: bool = False) -> ChainSummary:
+                                device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536, results: bool = False,
+                                discrete: bool = False, discrete_bins: Optional[Dict[str, Tuple[int, int]]] = None) -> ChainSummary:
     """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
     only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  `quantiles=True` adds the five
     quantiles as `hmc_chain_summary` does: every pass beyond the first REPEATS THE SAMPLING PHASE from the state exported after
     warmup (`ChainSummary.passes`).  `results=True` adds `ChainSummary.results` as `hmc_chain_summary` does; every site a result reads
-    must be an f64 site (the recorded ones: a discrete site moves under MH and is not in the chunk)."""
+    must be an f64 site (the recorded ones: a discrete site moves under MH and is not in the chunk).
+
+    `discrete=True` records every site and adds `ChainSummary.discrete`, a `DiscreteSummary`: exact frequency tables of every
+    discrete site (`Engine.diag_cstream`), and for the u64 sites the figures of Diagnostics<u64> (`DiscreteSummary.numeric`).  The
+    bins of a site are `discrete_bins[address] = (lo, bins)`, else its support where the program states it with constant
+    parameters (Bernoulli (0, 2), Categorical (0, K), DiscreteUniform (lo, hi - lo + 1), Binomial (0, n + 1), at most 4096 bins),
+    else (0, 64); draws outside are counted in `below` / `above`.  A result may then read any site, a model needs no f64 site, and
+    the f64 figures are those `discrete=False` gives."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
-    rec = list(cp.f64_sites)
-    if not rec:
-        raise ValueError("adaptive_mcmc_chain_summary: the model has no f64 site to summarise")
-    _want_results(cp, results, rec, "adaptive_mcmc_chain_summary")
+    who = "adaptive_mcmc_chain_summary"
+    if discrete_bins is not None and not discrete:
+        raise ValueError(f"{who}: discrete_bins is given, but discrete=True is not")
+    if discrete:
+        if cp.S == 0:
+            raise ValueError(f"{who}: the model has no site to summarise")
+        for a, b in (discrete_bins or {}).items():
+            if a not in cp.site_names or cp.site_vtypes[cp.site_names.index(a)] == M.F64:
+                raise ValueError(f"{who}: discrete_bins names {a!r}, which is no discrete site")
+            if len(b) != 2 or not 1 <= int(b[1]) <= 4096:
+                raise ValueError(f"{who}: discrete_bins[{a!r}] must be (lo, bins) with bins in [1, 4096]")
+        rec = list(range(cp.S))
+    else:
+        rec = list(cp.f64_sites)
+        if not rec:
+            raise ValueError(f"{who}: the model has no f64 site to summarise")
+    _want_results(cp, results, None if discrete else rec, who)
     ov = _override_rows(cp, overrides)
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     try:
@@ -359,8 +467,9 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
         def stats(out):
             out.accept_rate = eng.mh_stats().accept_rate
 
-        out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in rec], len(rec), n_samples, chunk, max_lag,
-                              quantiles, quantile_capacity, stats, result_rows=rec if results else False)
+        out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag,
+                              quantiles, quantile_capacity, stats, result_rows=rec if results else False,
+                              discrete_bins=dict(discrete_bins or {}) if discrete else False)
     finally:
         eng.close()
     return out

@@ -506,6 +506,40 @@ int  fg_diag_qstream_passes(const fg_diag_qstream *s);         /* diagnostics.rs
  * FG_E_STATE before the stream is done. */
 int  fg_diag_qstream_result(fg_diag_qstream *s, double *h_out, int32_t *h_slot_passes);
 void fg_diag_qstream_free(fg_diag_qstream *s);                 /* diagnostics.rs:355-371 */
+/* ------------------------------------------------------------------ discrete sites without stored draws
+ * The reference extracts the values of a discrete site (extract_bool_values / extract_u64_values / extract_usize_values /
+ * extract_i64_values, diagnostics.rs:76-98) and its callers tabulate them; fg_diag_cstream keeps those frequency tables for a run
+ * that is handed over one chunk at a time and never stored.  A chunk is what fg_mh_step records: [n_chunk][n_rec][C] 8-byte cells,
+ * f64 rows and integer rows mixed.  The stream watches n_watch of its rows.  Watched row k: its chunk row h_rows[k] (each at most
+ * once), its ChoiceValue tag h_vtypes[k] (FG_U64 cells compare as unsigned, FG_BOOL / FG_USIZE / FG_I64 cells as signed; FG_F64 is
+ * refused), a lower bound h_lo[k] and a bin count h_bins[k].  It keeps, as 64-bit integers, counts[bins] (bin j: the cells equal to
+ * lo + j), `below` and `above` (the cells outside [lo, lo + bins): nothing is dropped silently) and the smallest and largest cell
+ * seen.  Integer sums: the result does not depend on chunk boundaries or arrival order.  Rows of at most 8 bins are counted by
+ * wave ballots, wider ones in an LDS histogram; FG_DIAG_CSTREAM_FORM=wide|narrow (read at fg_diag_cstream_new) forces a form where
+ * it is legal.  This engine's chains only: counts of ranks add on the host. */
+typedef struct fg_diag_cstream fg_diag_cstream;
+/* diagnostics.rs:76-98.  FG_E_BAD_ARG: n_total < 1, n_rec < 1, n_watch outside [1, 65535], a row outside [0, n_rec) or given twice,
+ * a tag that is FG_F64 or unknown, bins outside [1, 4096], lo + bins overflowing the row's integer type (lo < 0 on an FG_U64 row).
+ * The stream must be freed before its engine. */
+int  fg_diag_cstream_new(fg_engine *e, int n_total, int n_rec, const int32_t *h_rows, const int32_t *h_vtypes,
+                         const int64_t *h_lo, const int32_t *h_bins, int n_watch, fg_diag_cstream **out);
+/* diagnostics.rs:76-98: the next n_chunk draws d_cells [n_chunk][n_rec][C]; asynchronous on the engine's stream.  FG_E_STATE when
+ * the chunk would pass n_total. */
+int  fg_diag_cstream_update(fg_diag_cstream *s, const void *d_cells, int n_chunk);
+int  fg_diag_cstream_count(const fg_diag_cstream *s);          /* diagnostics.rs:76-98: draws taken so far */
+/* diagnostics.rs:76-98: h_counts = the rows' bins back to back, h_below / h_above / h_min / h_max [n_watch] (min / max of an FG_U64
+ * row are the cell's 64 bits).  FG_E_STATE before n_total draws have arrived, or when a row's counts + below + above differ from
+ * n_total x C (the stream's integrity check). */
+int  fg_diag_cstream_result(fg_diag_cstream *s, uint64_t *h_counts, uint64_t *h_below, uint64_t *h_above,
+                            int64_t *h_min, int64_t *h_max);
+void fg_diag_cstream_free(fg_diag_cstream *s);                 /* diagnostics.rs:76-98 */
+/* diagnostics.rs:153-191 (Diagnostics<u64>: `x as f64`): d_cells [n][n_rec][C] -> d_out [n][n_sel][C], output row k = chunk row
+ * h_rows[k] (any order, repeats allowed) converted by its tag h_vtypes[k]: FG_F64 bits copied, FG_U64 (double)(uint64_t), FG_BOOL /
+ * FG_USIZE / FG_I64 (double)(int64_t).  What fg_diag_stream / fg_diag_qstream take.  One streaming kernel, asynchronous on the
+ * engine's stream; n = 0 is FG_OK without a launch.  FG_E_BAD_ARG: n < 0, n_rec < 1, n_sel < 1, a row outside [0, n_rec), an
+ * unknown tag. */
+int fg_diag_cells_f64(fg_engine *e, const void *d_cells, int n, int n_rec, const int32_t *h_rows,
+                      const int32_t *h_vtypes, int n_sel, double *d_out);
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_engine { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_qstream { _p: [u8; 0] }
+#[repr(C)] pub struct fg_diag_cstream { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -161,6 +162,16 @@ extern "C" {
     pub fn fg_diag_qstream_passes(s: *const fg_diag_qstream) -> c_int;
     pub fn fg_diag_qstream_result(s: *mut fg_diag_qstream, h_out: *mut f64, h_slot_passes: *mut i32) -> c_int;
     pub fn fg_diag_qstream_free(s: *mut fg_diag_qstream);
+    // ---- discrete sites without stored draws: exact frequency tables and the gather into f64 rows (fg_diag_cstream.hip)
+    pub fn fg_diag_cstream_new(e: *mut fg_engine, n_total: c_int, n_rec: c_int, h_rows: *const i32, h_vtypes: *const i32, h_lo: *const i64,
+                               h_bins: *const i32, n_watch: c_int, out: *mut *mut fg_diag_cstream) -> c_int;
+    pub fn fg_diag_cstream_update(s: *mut fg_diag_cstream, d_cells: *const c_void, n_chunk: c_int) -> c_int;
+    pub fn fg_diag_cstream_count(s: *const fg_diag_cstream) -> c_int;
+    pub fn fg_diag_cstream_result(s: *mut fg_diag_cstream, h_counts: *mut u64, h_below: *mut u64, h_above: *mut u64, h_min: *mut i64,
+                                  h_max: *mut i64) -> c_int;
+    pub fn fg_diag_cstream_free(s: *mut fg_diag_cstream);
+    pub fn fg_diag_cells_f64(e: *mut fg_engine, d_cells: *const c_void, n: c_int, n_rec: c_int, h_rows: *const i32, h_vtypes: *const i32,
+                             n_sel: c_int, d_out: *mut f64) -> c_int;
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
