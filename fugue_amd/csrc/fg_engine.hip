@@ -813,7 +813,7 @@ void fg_engine_free(fg_engine *e) {
     if (e->mhmw.unit.mod) (void)hipModuleUnload(e->mhmw.unit.mod);
     if (e->mhmw.unit_ns.mod) (void)hipModuleUnload(e->mhmw.unit_ns.mod);
     void *ptrs[] = { e->mhmw.d_catu_c, e->mhmw.d_catu, e->d_jit_tab, e->d_jit_mh_tab, e->mhmw.unit.d_tab, e->mhmw.unit_ns.d_tab, e->d_mhi_acc, e->d_mhi_site_ins, e->hsplit.d_mwi_order, e->hsplit.d_mwi_prof, e->d_gtile, e->d_lin_tab, e->d_lin_meta, e->mhmw.d_srt, e->d_sep, e->d_sep_coord, e->d_sep_free, e->d_site_rec, e->d_sobs, e->d_ins, e->d_ins_fast, e->d_coord, e->d_gstream, e->d_sstream, e->d_sub, e->d_sub_off, e->d_f64_slot, e->d_site_slot, e->d_vtype, e->d_site_cat, e->d_pool, e->d_values, e->d_acc, e->d_logp,
-                     e->d_tmp, e->d_itmp, e->d_res_ins, e->d_res_pool, e->d_res_site, e->d_res_row, e->d_res_gtile };
+                     e->d_tmp, e->d_itmp, e->d_res_ins, e->d_res_pool, e->d_res_site, e->d_res_row, e->d_res_gtile, e->d_pred_row, e->d_pred_sel, e->d_pred_gtile };
     for (void *q : ptrs) if (q) hipFree(q);
     if (e->stream && e->own_stream) hipStreamDestroy(e->stream);
     delete e;

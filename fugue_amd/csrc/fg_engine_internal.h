@@ -117,6 +117,10 @@ struct fg_engine {
     // each used site comes from as last uploaded; the global scratch of programs whose slice exceeds a CU's LDS, grown on demand
     FgIns *d_res_ins = nullptr; double *d_res_pool = nullptr; int *d_res_site = nullptr, *d_res_row = nullptr; std::vector<int> res_row_host;
     double *d_res_gtile = nullptr; size_t res_gtile_bytes = 0;
+    // predictive draws (fg_predict.hip): the row of the draw each site comes from and the table row of each observe statement, as last
+    // uploaded (made at the first fg_predict_eval); the global scratch of programs whose slice exceeds a CU's LDS, grown on demand
+    int *d_pred_row = nullptr, *d_pred_sel = nullptr; std::vector<int> pred_row_host, pred_sel_host;
+    double *d_pred_gtile = nullptr; size_t pred_gtile_bytes = 0;
 };
 
 // p0 ~ N(0, M): hmc.rs:436-441.  Box-Muller pairs from the chain's (iteration) stream.

@@ -937,6 +937,30 @@ int fg_program_site_name(const fg_program *p, int j, char *buf, int len) {
     if (buf && len > 0) { int n = std::min<int>(len - 1, (int)a.size()); std::memcpy(buf, a.data(), n); buf[n] = 0; }
     return (int)a.size() + 1;
 }
+// observe statement k in PROGRAM order (the order a run of the model meets them, and the row order of fg_predict_eval's tables)
+static const FgStmt *observe_stmt(const fg_program *p, int k) {
+    if (k < 0) return nullptr;
+    for (const FgStmt &s : p->stmts) if (s.kind == 1 && k-- == 0) return &s;
+    return nullptr;
+}
+int fg_program_observe_name(const fg_program *p, int k, char *buf, int len) {
+    NEED_FINAL(p);
+    const FgStmt *s = observe_stmt(p, k);
+    if (!s) return FG_ERR_ADDRESS_NOT_FOUND;
+    const std::string &a = s->addr;
+    if (buf && len > 0) { int n = std::min<int>(len - 1, (int)a.size()); std::memcpy(buf, a.data(), n); buf[n] = 0; }
+    return (int)a.size() + 1;
+}
+int fg_program_observe_vtype(const fg_program *p, int k) {
+    NEED_FINAL(p);
+    const FgStmt *s = observe_stmt(p, k);
+    return s ? s->vtype : FG_ERR_ADDRESS_NOT_FOUND;
+}
+int fg_program_observe_dist(const fg_program *p, int k) {
+    NEED_FINAL(p);
+    const FgStmt *s = observe_stmt(p, k);
+    return s ? s->dist : FG_ERR_ADDRESS_NOT_FOUND;
+}
 int fg_program_stream_records(const fg_program *p, int which) {
     if (!p || !p->finalized) return FG_E_STATE;
     if (which == 0) return p->n_gstream;

@@ -98,6 +98,7 @@ ABI_SYMBOLS = [
     "fg_diag_cstream_new", "fg_diag_cstream_update", "fg_diag_cstream_count", "fg_diag_cstream_result", "fg_diag_cstream_free",
     "fg_diag_cells_f64",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
+    "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
 ]
 
 _lib = None
@@ -150,6 +151,10 @@ def lib():
     L.fg_program_result_name.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
     L.fg_program_result_sites.argtypes = [vp, ip, C.c_int]
     L.fg_result_eval.argtypes = [vp, vp, C.c_int, ip, C.c_int, vp]
+    L.fg_program_observe_name.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+    L.fg_program_observe_vtype.argtypes = [vp, C.c_int]
+    L.fg_program_observe_dist.argtypes = [vp, C.c_int]
+    L.fg_predict_eval.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_uint32, ip, C.c_int, vp, vp]
     L.fg_engine_new.restype = vp
     L.fg_engine_new.argtypes = [vp, C.c_int64, C.c_uint64, C.c_uint32, C.c_int]
     L.fg_engine_free.argtypes = [vp]
@@ -410,6 +415,12 @@ class CompiledProgram:
         for r in range(self.R):
             L.fg_program_result_name(self.h, r, buf, 4096)
             self.result_names.append(buf.value.decode("utf-8"))
+        self.observe_names = []
+        for k in range(self.O):
+            L.fg_program_observe_name(self.h, k, buf, 4096)
+            self.observe_names.append(buf.value.decode("utf-8"))
+        self.observe_vtypes = [L.fg_program_observe_vtype(self.h, k) for k in range(self.O)]     # program order, as the names
+        self.observe_dists = [L.fg_program_observe_dist(self.h, k) for k in range(self.O)]
         rs = (C.c_int32 * max(1, self.S))()
         self.result_sites = list(rs[:L.fg_program_result_sites(self.h, rs, self.S)])   # sorted site indices some result reads
 
@@ -506,6 +517,38 @@ class Engine:
             rp, n_rows = (C.c_int32 * max(1, len(rows)))(*rows), len(rows)
         _check(lib().fg_result_eval(self.h, d_draws, n, rp, n_rows, out))
         return out
+
+    def predict_eval(self, d_draws: Optional[int], n: int, rows: Optional[Sequence[int]] = None, iter0: int = 0, sel: Optional[Sequence[int]] = None,
+                     out=None, loglik=None):
+        """`fg_predict_eval`: replicated data of the observe statements for every draw and chain of the device buffer d_draws
+        [n][n_rows][C] (rows as in `result_eval`; d_draws=None with n=1: the engine's current values), drawn from the stream
+        (seed, chain, iter0 + t, 9).  `sel`: program-order indices of the observe statements to keep (None: all O).  `out` / `loglik`:
+        device buffers [n][n_sel][C] of cells / doubles; None allocates one (the caller frees it), False leaves that table out.
+        Returns (out, loglik) with None for a table left out.  Asynchronous."""
+        n = int(n)
+        n_sel = self.cp.O if sel is None else len(list(sel))
+        words = max(1, n * n_sel * self.C) * 8
+        mine = []
+        try:
+            if out is None:
+                out = self.device_alloc(words); mine.append(out)
+            if loglik is None:
+                loglik = self.device_alloc(words); mine.append(loglik)
+            out, loglik = (None if out is False else out), (None if loglik is False else loglik)
+            if d_draws is None:
+                rp, n_rows = None, 0
+            elif rows is None:
+                rp, n_rows = None, self.d
+            else:
+                rows = list(rows)
+                rp, n_rows = (C.c_int32 * max(1, len(rows)))(*rows), len(rows)
+            sp = None if sel is None else (C.c_int32 * max(1, n_sel))(*[int(k) for k in sel])
+            _check(lib().fg_predict_eval(self.h, d_draws, n, rp, n_rows, int(iter0) & 0xFFFFFFFF, sp, n_sel, out, loglik))
+        except Exception:
+            for b in mine:
+                self.device_free(b)
+            raise
+        return out, loglik
 
     def result_values(self) -> np.ndarray:
         """The model's return value at the engine's current values, [R][C] (a particle's `A`; HmcSession::result, hmc.rs:761)."""

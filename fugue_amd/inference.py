@@ -5,6 +5,11 @@
     adaptive_mcmc_chain_with_overrides(..., overrides)                        mh.rs:946-1014
     adaptive_smc(seed, num_particles, model_fn, config)                       smc.rs:455-581
     hmc_chain_summary / adaptive_mcmc_chain_summary                           the same runs, summarised in chunks (ChainSummary)
+    prior_predictive(seed, model_fn, n_chains)                                PriorHandler, then replicated data of the observe sites
+
+Every driver takes `predictive=` / `pointwise=`: replicated data drawn on the device from the observe statements at every draw (the
+posterior predictive the reference's workflows sample by hand, tests/inference_integration.rs:717-740) and the per-observation
+log-likelihood (`Choice.logp` of the observe sites).
 
 `model_fn` is what the reference passes (`Fn() -> Model<A>`): here a zero-argument callable returning a
 `fugue_amd.model.Model`, or an already traced `Program`.  The reference threads `&mut R`; the engine's RNG is
@@ -71,6 +76,17 @@ class ChainBatch:
     n_divergent: int = 0
     result_names: List[str] = field(default_factory=list)    # the scalars of the model's return value `A` (CompiledProgram.result_names)
     results: Optional[np.ndarray] = None                      # [n_samples][R][n_chains] float64, evaluated on the device; None when R = 0
+    predictive_names: List[str] = field(default_factory=list)   # predictive= / pointwise=: the selected observe addresses, program order as selected
+    predictive_vtypes: List[int] = field(default_factory=list)
+    predictive: Optional[np.ndarray] = None                   # [n_samples][n_sel][n_chains] int64 cells like `cells`: replicated data, draw t from stream (seed, chain, t, 9)
+    log_likelihood: Optional[np.ndarray] = None               # pointwise=True: [n_samples][n_sel][n_chains] float64, log p(observed value | draw) per observe statement
+
+    def get_predictive(self, address: str) -> np.ndarray:     # [n_samples][n_chains]: float64 for an f64 observe site, int64 otherwise
+        if self.predictive is None or address not in self.predictive_names:
+            raise M.FugueError(f"address not found: {address}", M.ErrorCode.TraceAddressNotFound)
+        k = self.predictive_names.index(address)
+        col = np.ascontiguousarray(self.predictive[:, k, :])
+        return col.view(np.float64) if self.predictive_vtypes[k] == 0 else col
 
     def get_result(self, name: str) -> np.ndarray:            # the `A` half of every (A, Trace): [n_samples][n_chains]
         if name not in self.result_names:
@@ -106,9 +122,20 @@ class SMCResult:
     betas: np.ndarray = field(default_factory=lambda: np.zeros(0))
     result_names: List[str] = field(default_factory=list)    # the scalars of the model's return value `A`
     results: Optional[np.ndarray] = None                      # [R][n_particles] float64: every particle's `A`; None when R = 0
+    predictive_names: List[str] = field(default_factory=list)   # predictive= / pointwise=: the selected observe addresses
+    predictive_vtypes: List[int] = field(default_factory=list)
+    predictive: Optional[np.ndarray] = None                   # [n_sel][n_particles] int64 cells: one replicate per particle
+    log_likelihood: Optional[np.ndarray] = None               # pointwise=True: [n_sel][n_particles] float64
 
     def get_f64(self, address: str) -> np.ndarray:
         return np.ascontiguousarray(self.cells[self.sites.index(address)]).view(np.float64)
+
+    def get_predictive(self, address: str) -> np.ndarray:     # [n_particles]: float64 for an f64 observe site, int64 otherwise
+        if self.predictive is None or address not in self.predictive_names:
+            raise M.FugueError(f"address not found: {address}", M.ErrorCode.TraceAddressNotFound)
+        k = self.predictive_names.index(address)
+        col = np.ascontiguousarray(self.predictive[k])
+        return col.view(np.float64) if self.predictive_vtypes[k] == 0 else col
 
     def get_result(self, name: str) -> np.ndarray:
         if name not in self.result_names:
@@ -120,10 +147,62 @@ def _compile(model_fn) -> E.CompiledProgram:
     return model_fn if isinstance(model_fn, E.CompiledProgram) else E.compile_model(model_fn)
 
 
+def _predictive_sel(cp, predictive, pointwise: bool, who: str):
+    """The observe statements `predictive=` / `pointwise=` select, as program-order indices: None when neither is asked for, every
+    statement for True (or for pointwise=True alone), else the addresses given, in the order given."""
+    if predictive is False or predictive is None:
+        if not pointwise:
+            return None
+        predictive = True
+    if cp.O == 0:
+        raise ValueError(f"{who}: predictive / pointwise asked for, but the model has no observe statement")
+    if predictive is True:
+        return list(range(cp.O))
+    addrs = [predictive] if isinstance(predictive, str) else list(predictive)
+    sel = []
+    for a in addrs:
+        a = str(a)
+        if a not in cp.observe_names:
+            raise ValueError(f"{who}: predictive names {a!r}, which is no observe address of the model")
+        k = cp.observe_names.index(a)
+        if k in sel:
+            raise ValueError(f"{who}: predictive names {a!r} twice")
+        sel.append(k)
+    if not sel:
+        raise ValueError(f"{who}: predictive is an empty list")
+    return sel
+
+
+def _predict(eng, sel, want_y: bool, pointwise: bool, d_draws, n: int, rows=None, iter0: int = 0):
+    """One fg_predict_eval over n draws, downloaded: (cells [n][n_sel][C] or None, log-likelihood [n][n_sel][C] or None)."""
+    shape = (n, len(sel), eng.C)
+    if n == 0:
+        return (np.zeros(shape, dtype=np.int64) if want_y else None), (np.zeros(shape) if pointwise else None)
+    yb, lb = eng.predict_eval(d_draws, n, rows=rows, iter0=iter0, sel=sel, out=None if want_y else False, loglik=None if pointwise else False)
+    try:
+        y = eng.download(yb, shape, dtype=np.int64) if want_y else None
+        ll = eng.download(lb, shape) if pointwise else None
+    finally:
+        for b in (yb, lb):
+            if b:
+                eng.device_free(b)
+    return y, ll
+
+
+def _predictive_fields(cp, sel, y, ll):
+    return dict(predictive_names=[cp.observe_names[k] for k in sel], predictive_vtypes=[cp.observe_vtypes[k] for k in sel], predictive=y, log_likelihood=ll)
+
+
 def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
-              device: int = 0) -> ChainBatch:
+              device: int = 0, predictive=False, pointwise: bool = False) -> ChainBatch:
+    """`predictive=True | [addresses]`: `ChainBatch.predictive`, replicated data of the (selected) observe sites at every draw, sampled
+    on the device (draw t from the stream (seed, chain, t, 9)); `pointwise=True`: `ChainBatch.log_likelihood`, the log-likelihood of
+    the observed value per selected observe statement (all of them when `predictive` is False)."""
     cp = _compile(model_fn)
     cfg = config or HMCConfig()
+    sel = _predictive_sel(cp, predictive, pointwise, "hmc_chain")
+    want_y = sel is not None and predictive is not False and predictive is not None
+    pred_y = pred_ll = None
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     cells = np.zeros((n_samples, cp.S, n_chains), dtype=np.int64)
     results = np.zeros((n_samples, cp.R, n_chains)) if cp.R > 0 else None
@@ -135,6 +214,17 @@ def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Option
             cells[t] = eng.get_values()
             if cp.R > 0:
                 results[t] = eng.result_values()
+            if sel is not None:
+                y1, l1 = _predict(eng, sel, want_y, pointwise, None, 1, iter0=t)
+                if t == 0:
+                    pred_y = np.zeros((n_samples, len(sel), n_chains), dtype=np.int64) if want_y else None
+                    pred_ll = np.zeros((n_samples, len(sel), n_chains)) if pointwise else None
+                if want_y:
+                    pred_y[t] = y1[0]
+                if pointwise:
+                    pred_ll[t] = l1[0]
+        if sel is not None and n_samples == 0:
+            pred_y, pred_ll = _predict(eng, sel, want_y, pointwise, None, 0)
         st = eng.hmc_stats()
     else:
         buf = eng.device_alloc(max(1, n_samples * cp.d * n_chains) * 8)
@@ -144,10 +234,15 @@ def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Option
             rbuf = eng.result_eval(buf, n_samples)
             results = eng.download(rbuf, (n_samples, cp.R, n_chains))
             eng.device_free(rbuf)
+        if sel is not None:                                     # discrete sites: the engine's values, as for the results
+            pred_y, pred_ll = _predict(eng, sel, want_y, pointwise, buf, n_samples)
         eng.device_free(buf)
         cells[:] = eng.get_values()[None]                       # HMC moves the f64 sites; discrete sites keep their prior draw (hmc.rs:238-260)
         cells[:, cp.f64_sites, :] = draws
     out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, st.mean_step_size, int(st.n_divergent), list(cp.result_names), results)
+    if sel is not None:
+        for k, v in _predictive_fields(cp, sel, pred_y, pred_ll).items():
+            setattr(out, k, v)
     eng.close()
     return out
 
@@ -164,8 +259,11 @@ def _override_rows(cp, overrides):
 
 
 def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_warmup: int, overrides: Sequence[Tuple[str, SiteProposal]],
-                                       n_chains: int = 1, device: int = 0) -> ChainBatch:
+                                       n_chains: int = 1, device: int = 0, predictive=False, pointwise: bool = False) -> ChainBatch:
+    """`predictive=` / `pointwise=`: as `hmc_chain` (every site is recorded, so every parameter is the draw's own)."""
     cp = _compile(model_fn)
+    sel = _predictive_sel(cp, predictive, pointwise, "adaptive_mcmc_chain")
+    want_y = sel is not None and predictive is not False and predictive is not None
     ov = _override_rows(cp, overrides)
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     rec = list(range(cp.S))
@@ -181,14 +279,24 @@ def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_wa
             eng.device_free(rbuf)
         elif n_samples > 0:
             results[:] = eng.result_values()[None]
+    pred = {}
+    if sel is not None:
+        if cp.S > 0 or n_samples == 0:
+            y, ll = _predict(eng, sel, want_y, pointwise, buf, n_samples, rows=rec)
+        else:                                                   # a model without sites: every draw is the (empty) current state
+            parts = [_predict(eng, sel, want_y, pointwise, None, 1, iter0=t) for t in range(n_samples)]
+            y = np.concatenate([q[0] for q in parts]) if want_y else None
+            ll = np.concatenate([q[1] for q in parts]) if pointwise else None
+        pred = _predictive_fields(cp, sel, y, ll)
     eng.device_free(buf)
-    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, result_names=list(cp.result_names), results=results)
+    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, result_names=list(cp.result_names), results=results, **pred)
     eng.close()
     return out
 
 
-def adaptive_mcmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1, device: int = 0) -> ChainBatch:
-    return adaptive_mcmc_chain_with_overrides(seed, model_fn, n_samples, n_warmup, (), n_chains, device)
+def adaptive_mcmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1, device: int = 0, predictive=False,
+                        pointwise: bool = False) -> ChainBatch:
+    return adaptive_mcmc_chain_with_overrides(seed, model_fn, n_samples, n_warmup, (), n_chains, device, predictive, pointwise)
 
 
 QUANTILE_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)      # summarize_f64_parameter's "2.5%", "25%", "50%", "75%", "97.5%"
@@ -215,6 +323,7 @@ class ChainSummary:
     passes: int = 1
     results: Optional["ChainSummary"] = None      # results=True: the same figures of the model's return value, `sites` = the result names
     discrete: Optional["DiscreteSummary"] = None  # adaptive_mcmc_chain_summary(discrete=True): the frequency tables of the discrete sites
+    predictive: Optional["ChainSummary"] = None   # predictive=: the same figures of the replicated data, `sites` = the selected observe addresses
 
 
 @dataclass
@@ -273,7 +382,7 @@ def _default_bins(cp, j: int) -> Tuple[int, int]:
 
 
 def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
-                    after_first_pass=None, result_rows=False, discrete_bins=False):
+                    after_first_pass=None, result_rows=False, discrete_bins=False, predict=None):
     """step(n, buf) records n draws into buf; one chunk buffer is alive at a time.  A chunk is seen through FEEDS: a view of it as
     doubles [n][rows][C] and the diagnostics stream (with quantiles: and the quantile stream) that take the view.
       - discrete_bins False: buf is [n][d][C] doubles (the f64 sites `sites`) and is its own view.
@@ -282,6 +391,10 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
         and values of the other mode, so their figures are those bit for bit -- and a count stream watches every non-f64 row.
       - result_rows (None: the HMC draw layout, or the sorted sites of buf's rows) adds the model's return value: every chunk is turned
         into one reused [chunk][R][C] buffer (`Engine.result_eval`), a third view.
+      - predict (dict(sel=observe indices, rows=as result_rows)) adds the replicated data of the selected f64 observe sites: every
+        chunk is turned into one reused [chunk][n_sel][C] buffer (`Engine.predict_eval` with iter0 = the chunk's first draw: the stream
+        is keyed by the absolute draw index, so a replayed chunk holds the same bits), a further view.
+    A view is called with (chunk buffer, draws in it, index of its first draw in the sampling phase).
     quantiles: the state after warmup is exported, the first sampling pass feeds every stream, `after_first_pass()` reads the
     sampler's statistics, and while a quantile stream wants another pass the blob is imported into the same engine and the same
     chunks are stepped again for the quantile streams that are still open; the count stream is complete after the first pass."""
@@ -313,13 +426,13 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
     try:
         main, numeric, w_rows, bins = None, None, [], []
         if not discrete:
-            main, chunk_rows = feed(sites, d, lambda buf, n: buf), d
+            main, chunk_rows = feed(sites, d, lambda buf, n, t0: buf), d
         else:
             chunk_rows = S = cp.S
 
             def gathered(rows):
                 vts, dbuf = [cp.site_vtypes[j] for j in rows], alloc(chunk * len(rows) * C_)
-                return feed([cp.site_names[j] for j in rows], len(rows), lambda buf, n: eng.cells_f64(buf, n, S, rows, vts, out=dbuf))
+                return feed([cp.site_names[j] for j in rows], len(rows), lambda buf, n, t0: eng.cells_f64(buf, n, S, rows, vts, out=dbuf))
 
             u_rows = [j for j in range(S) if cp.site_vtypes[j] == M.U64]
             w_rows = [j for j in range(S) if cp.site_vtypes[j] != M.F64]
@@ -332,7 +445,13 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
         res = None
         if result_rows is not False:
             rbuf = alloc(chunk * R * C_)
-            res = feed(cp.result_names, R, lambda buf, n: eng.result_eval(buf, n, rows=result_rows, out=rbuf))
+            res = feed(cp.result_names, R, lambda buf, n, t0: eng.result_eval(buf, n, rows=result_rows, out=rbuf))
+        prd = None
+        if predict is not None:
+            psel, prows = list(predict["sel"]), predict["rows"]
+            pbuf = alloc(chunk * len(psel) * C_)
+            prd = feed([cp.observe_names[k] for k in psel], len(psel),
+                       lambda buf, n, t0: eng.predict_eval(buf, n, rows=prows, iter0=t0, sel=psel, out=pbuf, loglik=False)[0])
         blob = eng.state_export() if quantiles else None
         buf = alloc(chunk * chunk_rows * C_)
 
@@ -344,7 +463,7 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
                 for f in feeds:
                     mine = [c for c in (f["stream"], f["qs"]) if any(c is x for x in live)]
                     if mine:
-                        view = f["view"](buf, n)
+                        view = f["view"](buf, n, done)
                         for c in mine:
                             c.update(view, n)
                 for c in counters:
@@ -355,6 +474,8 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
         out = figures(main, sites)
         if res is not None:
             out.results = figures(res)
+        if prd is not None:
+            out.predictive = figures(prd)
         if discrete:
             tab = cs.result() if cs is not None else dict(counts=[], below=np.zeros(0, dtype=np.uint64), above=np.zeros(0, dtype=np.uint64), min=[], max=[])
             out.discrete = DiscreteSummary([cp.site_names[j] for j in w_rows], [cp.site_vtypes[j] for j in w_rows], [b[0] for b in bins], tab["counts"],
@@ -367,7 +488,7 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
                 eng.state_import(blob)
                 one_pass(live)
                 live = [q for q in live if not q.end_pass()]
-            for f, target in ((main, out), (numeric, out.discrete.numeric if discrete else None), (res, out.results)):
+            for f, target in ((main, out), (numeric, out.discrete.numeric if discrete else None), (res, out.results), (prd, out.predictive)):
                 if f is not None:
                     target.quantiles, target.passes = f["qs"].result()[0], f["qs"].passes
     finally:
@@ -391,9 +512,20 @@ def _want_results(cp, results: bool, recorded=None, who: str = ""):
                              "(a streamed MH run records its f64 sites only)")
 
 
+def _summary_predictive(cp, predictive, who: str):
+    """The selection of a summary driver: f64 observe sites only (a discrete one would need the count stream)."""
+    sel = _predictive_sel(cp, predictive, False, who)
+    if sel is not None:
+        bad = [cp.observe_names[k] for k in sel if cp.observe_vtypes[k] != M.F64]
+        if bad:
+            raise ValueError(f"{who}: predictive selects the discrete observe site(s) {bad}; the summaries take f64 observe sites only "
+                             "(name the f64 ones, or store the draws with the chain driver)")
+    return sel
+
+
 def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
                       chunk: int = 64, max_lag: int = 64, device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536,
-                      results: bool = False) -> ChainSummary:
+                      results: bool = False, predictive=False) -> ChainSummary:
     """`hmc_chain` for runs longer than memory: the same transitions (`fg_hmc_step` is incremental), `chunk` at a time into one
     draw buffer that a diagnostics stream consumes, and the summary of every f64 site instead of the draws.  `max_lag` bounds how
     far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  `quantiles=True` adds the five quantiles
@@ -402,12 +534,15 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
     `quantile_capacity` (keys collected per quantile once that few candidates are left; device memory 8 x 5 x n_sites x capacity
     bytes), `ChainSummary.passes` reports the count.  Every other figure is the one `quantiles=False` gives.  `results=True` adds
     `ChainSummary.results`: the same figures of the model's return value (the `A` of hmc.rs:566-583), evaluated on the device chunk
-    by chunk; the site figures are the ones `results=False` gives."""
+    by chunk; the site figures are the ones `results=False` gives.  `predictive=True | [addresses]` adds `ChainSummary.predictive`:
+    the same figures of the replicated data of the selected f64 observe sites, sampled on the device chunk by chunk (a replay pass
+    samples a chunk again to the same bits); a selected discrete observe site raises ValueError."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     if cp.d == 0:
         raise ValueError("hmc_chain_summary: the model has no f64 site to summarise")
     _want_results(cp, results, who="hmc_chain_summary")
+    psel = _summary_predictive(cp, predictive, "hmc_chain_summary")
     cfg = config or HMCConfig()
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     try:
@@ -418,7 +553,7 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
             out.accept_rate, out.mean_step_size, out.n_divergent = st.accept_rate, st.mean_step_size, int(st.n_divergent)
 
         out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag, quantiles, quantile_capacity, stats,
-                              result_rows=None if results else False)
+                              result_rows=None if results else False, predict=None if psel is None else dict(sel=psel, rows=None))
     finally:
         eng.close()
     return out
@@ -427,7 +562,7 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
 def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1,
                                 overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
                                 device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536, results: bool = False,
-                                discrete: bool = False, discrete_bins: Optional[Dict[str, Tuple[int, int]]] = None) -> ChainSummary:
+                                discrete: bool = False, discrete_bins: Optional[Dict[str, Tuple[int, int]]] = None, predictive=False) -> ChainSummary:
     """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
     only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  `quantiles=True` adds the five
     quantiles as `hmc_chain_summary` does: every pass beyond the first REPEATS THE SAMPLING PHASE from the state exported after
@@ -439,10 +574,17 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
     bins of a site are `discrete_bins[address] = (lo, bins)`, else its support where the program states it with constant
     parameters (Bernoulli (0, 2), Categorical (0, K), DiscreteUniform (lo, hi - lo + 1), Binomial (0, n + 1), at most 4096 bins),
     else (0, 64); draws outside are counted in `below` / `above`.  A result may then read any site, a model needs no f64 site, and
-    the f64 figures are those `discrete=False` gives."""
+    the f64 figures are those `discrete=False` gives.
+
+    `predictive=True | [addresses]` adds `ChainSummary.predictive` as `hmc_chain_summary` does.  The parameters of an observe statement
+    must come from recorded sites: a model with a discrete site needs `discrete=True` (which records every site)."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     who = "adaptive_mcmc_chain_summary"
+    psel = _summary_predictive(cp, predictive, who)
+    if psel is not None and not discrete and cp.d != cp.S:
+        raise ValueError(f"{who}: predictive on a model with discrete sites needs discrete=True (a streamed MH run records its f64 sites only, "
+                         "and the discrete ones move)")
     if discrete_bins is not None and not discrete:
         raise ValueError(f"{who}: discrete_bins is given, but discrete=True is not")
     if discrete:
@@ -469,21 +611,69 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
 
         out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag,
                               quantiles, quantile_capacity, stats, result_rows=rec if results else False,
-                              discrete_bins=dict(discrete_bins or {}) if discrete else False)
+                              discrete_bins=dict(discrete_bins or {}) if discrete else False, predict=None if psel is None else dict(sel=psel, rows=rec))
     finally:
         eng.close()
     return out
 
 
-def adaptive_smc(seed: int, num_particles: int, model_fn, config: Optional[SMCConfig] = None, device: int = 0) -> SMCResult:
+def adaptive_smc(seed: int, num_particles: int, model_fn, config: Optional[SMCConfig] = None, device: int = 0, predictive=False,
+                 pointwise: bool = False) -> SMCResult:
+    """`predictive=` / `pointwise=`: one replicate of the (selected) observe sites per final particle, `SMCResult.predictive`
+    [n_sel][N] (stream (seed, particle, 0, 9)), and the particles' pointwise log-likelihood."""
     cp = _compile(model_fn)
     cfg = config or SMCConfig()
+    sel = _predictive_sel(cp, predictive, pointwise, "adaptive_smc")
+    want_y = sel is not None and predictive is not False and predictive is not None
     if num_particles == 0:                                         # smc.rs:462-467
+        pred = {} if sel is None else _predictive_fields(cp, sel, np.zeros((len(sel), 0), dtype=np.int64) if want_y else None, np.zeros((len(sel), 0)) if pointwise else None)
         return SMCResult(list(cp.site_names), list(cp.site_vtypes), np.zeros((cp.S, 0), dtype=np.int64), np.zeros(0), np.zeros(0), 0.0,   # empty population: log_evidence 0.0
-                         result_names=list(cp.result_names), results=np.zeros((cp.R, 0)) if cp.R > 0 else None)
+                         result_names=list(cp.result_names), results=np.zeros((cp.R, 0)) if cp.R > 0 else None, **pred)
     eng = E.Engine(cp, num_particles, seed=seed, device=device)
     r = eng.smc_run(cfg.resampling_method, cfg.ess_threshold, cfg.rejuvenation_steps)
     out = SMCResult(list(cp.site_names), list(cp.site_vtypes), r["values"], r["weights"], r["log_w"], r["log_evidence"], r["betas"],
                     list(cp.result_names), eng.result_values() if cp.R > 0 else None)
+    if sel is not None:
+        y, ll = _predict(eng, sel, want_y, pointwise, None, 1)
+        for k, v in _predictive_fields(cp, sel, None if y is None else y[0], None if ll is None else ll[0]).items():
+            setattr(out, k, v)
     eng.close()
     return out
+
+
+@dataclass
+class PriorPredictive:
+    """`prior_predictive`: n_chains runs of PriorHandler (interpreters.rs:88-104) and, for each, one replicate of the observe sites
+    drawn at those values -- a simulator's output."""
+    sites: List[str]
+    vtypes: List[int]
+    cells: np.ndarray                 # [n_sites][n_chains]: the prior draws
+    predictive_names: List[str]
+    predictive_vtypes: List[int]
+    predictive: np.ndarray            # [n_sel][n_chains] int64 cells
+    log_likelihood: Optional[np.ndarray] = None   # pointwise=True: [n_sel][n_chains]
+
+    def get_f64(self, address: str) -> np.ndarray:
+        return np.ascontiguousarray(self.cells[self.sites.index(address)]).view(np.float64)
+
+    def get_predictive(self, address: str) -> np.ndarray:
+        if address not in self.predictive_names:
+            raise M.FugueError(f"address not found: {address}", M.ErrorCode.TraceAddressNotFound)
+        k = self.predictive_names.index(address)
+        col = np.ascontiguousarray(self.predictive[k])
+        return col.view(np.float64) if self.predictive_vtypes[k] == 0 else col
+
+
+def prior_predictive(seed: int, model_fn, n_chains: int, iteration: int = 0, predictive=True, pointwise: bool = False, device: int = 0) -> PriorPredictive:
+    """The prior predictive: `prior_init(iteration)` draws every site from its prior, then the observe sites are drawn at those values
+    from the stream (seed, chain, iteration, 9)."""
+    cp = _compile(model_fn)
+    sel = _predictive_sel(cp, True if predictive is False or predictive is None else predictive, pointwise, "prior_predictive")
+    eng = E.Engine(cp, n_chains, seed=seed, device=device)
+    try:
+        eng.prior_init(iteration)
+        y, ll = _predict(eng, sel, True, pointwise, None, 1, iter0=iteration)
+        f = _predictive_fields(cp, sel, y[0], None if ll is None else ll[0])
+        return PriorPredictive(list(cp.site_names), list(cp.site_vtypes), eng.get_values(), f["predictive_names"], f["predictive_vtypes"], f["predictive"], f["log_likelihood"])
+    finally:
+        eng.close()

@@ -110,6 +110,11 @@ int fg_program_n_slots(const fg_program *p);      /* S + expression temporaries 
 int fg_program_site_name(const fg_program *p, int sorted_idx, char *buf, int buf_len);
 int fg_program_site_vtype(const fg_program *p, int sorted_idx);
 int fg_program_site_of_handle(const fg_program *p, int handle);
+/* observe statement k in PROGRAM order, 0 <= k < O (the order `run` meets them, handler.rs:124-209; the row order of fg_predict_eval):
+ * its address like fg_program_site_name, the value type of its distribution (FG_F64 .. FG_I64), the distribution kind */
+int fg_program_observe_name(const fg_program *p, int k, char *buf, int buf_len);
+int fg_program_observe_vtype(const fg_program *p, int k);
+int fg_program_observe_dist(const fg_program *p, int k);
 int fg_program_f64_site(const fg_program *p, int k);
 /* number of instructions re-evaluated when f64 coordinate k is perturbed (sparse FD) */
 int fg_program_dep_count(const fg_program *p, int k);
@@ -187,6 +192,21 @@ int fg_log_joint_stream(fg_engine *e, double *h_acc, double *h_rec_lp);
  * hmc.rs:761).  Integer sites enter as f64 like FG_T_SITE.  Asynchronous on the engine's stream; n == 0 is FG_OK without a launch.
  * FG_E_STATE: the program has no result; FG_E_BAD_ARG: a row index outside [0, S) or given twice, n_rows != d without h_rows. */
 int fg_result_eval(fg_engine *e, const void *d_draws, int n, const int32_t *h_rows, int n_rows, double *d_out);
+/* Posterior (or prior) predictive draws: for every draw and chain, replicated data sampled from the distributions of the observe
+ * statements with the latent sites pinned to the draw -- what the reference's workflows do by hand after a run
+ * (tests/inference_integration.rs:717-740, tests/end_to_end_workflows.rs:650-700) -- and, if asked, the log-likelihood of the OBSERVED
+ * value per statement (`Choice.logp` of an observe site), the table WAIC / LOO start from.  d_draws, n, h_rows, n_rows as in
+ * fg_result_eval (h_rows == NULL: the HMC draw layout; d_draws == NULL with n == 1 and n_rows == 0: the engine's current values --
+ * after fg_prior_init the prior predictive, after fg_smc_run one replicate per particle).  Draw t of chain c draws from the stream
+ * (seed, chain_offset + c, iter0 + t, purpose 9), consumed by the observe statements in program order; every observe statement is
+ * drawn whether selected or not, so a selection holds the bits of the full table.  h_sel: the n_sel observe statements (program-order
+ * indices) to store, NULL: all O of them (n_sel is ignored).  d_yrep [n][n_sel][C] 8-byte cells (f64, or i64 for discrete
+ * distributions, as site cells are); d_loglik [n][n_sel][C] doubles: the term the scoring run adds to log_likelihood for that
+ * statement.  Either may be NULL, not both.  Asynchronous on the engine's stream; n == 0 is FG_OK without a launch.  Reads engine
+ * state and changes none (no sampler's stream moves).  FG_E_STATE: the program has no observe statement; FG_E_BAD_ARG: a bad row, a
+ * selection index outside [0, O) or given twice, both outputs NULL. */
+int fg_predict_eval(fg_engine *e, const void *d_draws, int n, const int32_t *h_rows, int n_rows, uint32_t iter0,
+                    const int32_t *h_sel, int n_sel, void *d_yrep, double *d_loglik);
 
 /* ------------------------------------------------------------------ HMC
  * Replaces hmc_chain / HmcSession (src/inference/hmc.rs:566-583, 643-920). */

@@ -85,6 +85,10 @@ extern "C" {
     pub fn fg_program_site_of_handle(p: *const fg_program, h: c_int) -> c_int;
     pub fn fg_program_f64_site(p: *const fg_program, k: c_int) -> c_int;
     pub fn fg_program_stream_records(p: *const fg_program, which: c_int) -> c_int;
+    // observe statements in program order (the rows of fg_predict_eval)
+    pub fn fg_program_observe_name(p: *const fg_program, k: c_int, buf: *mut c_char, buf_len: c_int) -> c_int;
+    pub fn fg_program_observe_vtype(p: *const fg_program, k: c_int) -> c_int;
+    pub fn fg_program_observe_dist(p: *const fg_program, k: c_int) -> c_int;
     // the model's return value, `A` of Model<A> (model.rs `pure`; hmc.rs:566-583 returns it with every trace)
     pub fn fg_program_result(p: *mut fg_program, name_utf8: *const c_char, toks: *const fg_tok, n: c_int) -> c_int;
     pub fn fg_program_n_results(p: *const fg_program) -> c_int;
@@ -100,6 +104,9 @@ extern "C" {
     pub fn fg_prior_init(e: *mut fg_engine, iteration: u32, h_acc: *mut f64) -> c_int;
     pub fn fg_log_joint(e: *mut fg_engine, h_acc: *mut f64, h_logp: *mut f64) -> c_int;
     pub fn fg_result_eval(e: *mut fg_engine, d_draws: *const c_void, n: c_int, h_rows: *const i32, n_rows: c_int, d_out: *mut f64) -> c_int;
+    // posterior / prior predictive draws of the observe statements and their pointwise log-likelihood (inference_integration.rs:717-740)
+    pub fn fg_predict_eval(e: *mut fg_engine, d_draws: *const c_void, n: c_int, h_rows: *const i32, n_rows: c_int, iter0: u32,
+                           h_sel: *const i32, n_sel: c_int, d_yrep: *mut c_void, d_loglik: *mut f64) -> c_int;
     // ---- HMC (hmc.rs:566-583, 643-920)
     pub fn fg_hmc_config_default(cfg: *mut fg_hmc_config);
     pub fn fg_hmc_init(e: *mut fg_engine, cfg: *const fg_hmc_config, n_warmup: c_int) -> c_int;
