@@ -14,5 +14,7 @@ from .inference import (ChainBatch, ChainSummary, HMCConfig, PriorPredictive, Re
 from .diagnostics import (ParameterSummary, StreamMoments, classic_r_hat_f64, effective_sample_size, effective_sample_size_multichain,  # noqa: F401
                           geweke_diagnostic, r_hat_f64, summarize_f64_parameter)
 from .validation import effective_sample_size_mcmc  # noqa: F401
+from .abc import (ABC_SMC_DEFAULT_ATTEMPT_FACTOR, ABCError, ABCSMCConfig, ABCSMCResult, EuclideanDistance, ManhattanDistance,  # noqa: F401
+                  SummaryStatsDistance, abc_rejection, abc_scalar_summary, abc_smc, abc_smc_weighted)
 from .vi import (GuideError, MeanFieldGuide, ParamCoord, Support, VIConfig, VIResult, VariationalParam, elbo_gradient_fd,  # noqa: F401
                  elbo_with_guide, estimate_elbo, optimize_meanfield_vi, optimize_meanfield_vi_with_config)

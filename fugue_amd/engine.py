@@ -99,6 +99,8 @@ ABI_SYMBOLS = [
     "fg_diag_cells_f64",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
+    "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
+    "fg_abc_stage_end", "fg_abc_last_round", "fg_abc_get_population", "fg_abc_set_population",
 ]
 
 _lib = None
@@ -155,6 +157,19 @@ def lib():
     L.fg_program_observe_vtype.argtypes = [vp, C.c_int]
     L.fg_program_observe_dist.argtypes = [vp, C.c_int]
     L.fg_predict_eval.argtypes = [vp, vp, C.c_int, ip, C.c_int, C.c_uint32, ip, C.c_int, vp, vp]
+    L.fg_abc_distance.argtypes = [vp, vp, C.c_int, C.c_int64, dp, C.c_int, C.c_int, dp, C.c_int, vp]
+    L.fg_abc_mixture.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int, dp, dp, vp]
+    i64p = C.POINTER(C.c_int64)
+    L.fg_abc_new.argtypes = [vp, C.c_int, ip, C.c_int, dp, C.c_int, C.c_int, dp, C.c_int, C.c_int64, C.POINTER(vp)]
+    L.fg_abc_free.argtypes = [vp]
+    L.fg_abc_free.restype = None
+    L.fg_abc_round_prior.argtypes = [vp, C.c_double, C.c_int64, i64p, i64p]
+    L.fg_abc_stage_begin.argtypes = [vp]
+    L.fg_abc_round_stage.argtypes = [vp, C.c_uint32, C.c_double, C.c_int64, i64p, i64p]
+    L.fg_abc_stage_end.argtypes = [vp]
+    L.fg_abc_last_round.argtypes = [vp, i64p, dp, dp, ip]
+    L.fg_abc_get_population.argtypes = [vp, C.c_int, i64p, vp, dp, dp, i64p, dp, dp]
+    L.fg_abc_set_population.argtypes = [vp, C.c_int64, vp, dp, dp, i64p, dp, dp]
     L.fg_engine_new.restype = vp
     L.fg_engine_new.argtypes = [vp, C.c_int64, C.c_uint64, C.c_uint32, C.c_int]
     L.fg_engine_free.argtypes = [vp]

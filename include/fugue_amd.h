@@ -208,6 +208,82 @@ int fg_result_eval(fg_engine *e, const void *d_draws, int n, const int32_t *h_ro
 int fg_predict_eval(fg_engine *e, const void *d_draws, int n, const int32_t *h_rows, int n_rows, uint32_t iter0,
                     const int32_t *h_sel, int n_sel, void *d_yrep, double *d_loglik);
 
+/* ------------------------------------------------------------------ approximate Bayesian computation
+ * The device pieces of src/inference/abc.rs.  A simulator's output for a batch of B attempts is an f64 table [K][B] (attempt-fastest):
+ * the selected observe statements drawn by fg_predict_eval at the current values (cells converted by fg_diag_cells_f64), or named
+ * results evaluated by fg_result_eval. */
+enum { FG_ABC_EUCLIDEAN = 0,      /* EuclideanDistance, abc.rs:132-145 */
+       FG_ABC_MANHATTAN = 1,      /* ManhattanDistance, abc.rs:168-180 */
+       FG_ABC_SUMMARY_STATS = 2   /* SummaryStatsDistance, abc.rs:183-226 */ };
+/* DistanceFunction::distance (abc.rs:132-145, 168-180, 183-226) of every attempt's column of d_sim [K][B] against h_observed
+ * [n_observed]: d_dist [B].  IEEE operations in the reference's order: bit-identical to a sequential evaluation.  Euclidean: the
+ * in-order sum of (o - s)(o - s), then sqrt; Manhattan: the in-order sum of |o - s|; both +inf for every attempt when K != n_observed.
+ * SummaryStats: sqrt(sum_i w_i (o_i - s_i)^2) over zip(stats, weights), stats = mean (in-order sum / K), population standard
+ * deviation (a second in-order pass), median (exact selection, the even-K average included); fewer than three weights give fewer
+ * terms, more than three are ignored; the observed vector's statistics are computed once on the host by the same arithmetic.  A
+ * NaN among an attempt's simulated values gives a NaN distance, which no tolerance accepts (the reference panics in
+ * `partial_cmp().unwrap()`, abc.rs:202); a NaN in the observed vector is FG_E_BAD_ARG for SummaryStats.  h_weights is read for
+ * FG_ABC_SUMMARY_STATS only.  Asynchronous on the engine's stream for SummaryStats, synchronous otherwise; B == 0 is FG_OK without a
+ * launch.  Reads no engine state and changes none. */
+int fg_abc_distance(fg_engine *e, const double *d_sim, int K, int64_t B, const double *h_observed, int n_observed, int kind,
+                    const double *h_weights, int n_weights, double *d_dist);
+/* kernel_mixture_log_density (abc.rs:776-799) for m proposals at once, the denominator of the importance weight of weighted ABC-SMC
+ * (abc.rs:612-616): d_out[i] = log sum_j h_weights[j] prod_c N(d_x[c][i]; d_centers[c][j], max(h_std[c], 1e-12)).  d_x [d][m],
+ * d_centers [d][n], h_weights [n], h_std [d], d_out [m].  The per-center constant ln w_j - sum_c ln s_c - d ln(2 pi)/2 is hoisted and
+ * the coordinates are pre-scaled by 1/s_c, so this is NOT the reference's rounding: it agrees to about 1e-12 relative.  w_j = 0
+ * contributes nothing; when every term is -inf the result is -inf; d = 0 gives log sum_j w_j; a NaN coordinate gives NaN.  Any d.
+ * Synchronous.  FG_E_BAD_ARG: m < 0, n < 1, d < 0.  Reads no engine state and changes none. */
+int fg_abc_mixture(fg_engine *e, const double *d_x, int64_t m, const double *d_centers, int64_t n, int d, const double *h_weights,
+                   const double *h_std, double *d_out);
+/* An ABC run over the model's own simulator.  The reference loops one attempt at a time (abc_rejection, abc.rs:283-325; the stages
+ * of abc_smc_weighted, abc.rs:520-650) and stops right after the n-th accept or at its attempt budget; the handle runs rounds of
+ * B = the engine's n_chains attempts and gives the result the sequential loop would give, whatever B is: attempt a (from 0 within a
+ * stage) uses the chain word chain_offset + a and the iteration word t = the stage (0: the prior stage), the accepted set is the
+ * first n accepted attempts in order of a, attempts beyond the budget are masked.  Streams of attempt a: stage 0 draws the trace
+ * as fg_prior_init does (purpose 1); stage t >= 1 draws its proposal from purpose 10 (one Uniform(0,1) for the base particle, then
+ * one Normal(0,1) per f64 site in address order); every stage simulates as fg_predict_eval does (purpose 9, iter0 = t).  The engine's
+ * values [S][B] are the rounds' workspace; with a live HMC / MH / SMC session on the engine they are saved and put back, and no
+ * sampler's stream moves.
+ * fg_abc_new binds an engine, the simulator (FG_ABC_SIM_OBSERVE: h_sel = n_sel observe statements, program-order indices, strictly
+ * increasing, NULL = all of them; FG_ABC_SIM_RESULT: h_sel = n_sel result indices, NULL = all of them), the observed vector, the
+ * distance (as fg_abc_distance) and the capacity n of a population.  FG_E_BAD_ARG: a bad selection or kind, capacity < 1, a NaN in
+ * the observed vector of SummaryStats; FG_E_STATE: the program has no observe statement / no result.  The handle must be freed before
+ * its engine. */
+enum { FG_ABC_SIM_OBSERVE = 0, FG_ABC_SIM_RESULT = 1 };
+typedef struct fg_abc fg_abc;
+int  fg_abc_new(fg_engine *e, int sim_kind, const int32_t *h_sel, int n_sel, const double *h_observed, int n_observed, int kind,
+                const double *h_weights, int n_weights, int64_t capacity, fg_abc **out);     /* abc.rs:283-291, 520-528 */
+void fg_abc_free(fg_abc *a);                                                                  /* abc.rs:283-325 */
+/* The prior stage (abc.rs:295-316, 534-547): rounds of prior draws until n are accepted (dist <= tol) or `budget` attempts are made;
+ * the accepted particles (site cells, distance, attempt index, log-prior) become the current population with weights 1 / accepted
+ * (abc.rs:555-558).  *accepted <= n; *attempts = index of the n-th accepted attempt + 1, or the budget.  At most ceil(budget / B)
+ * rounds.  FG_E_BAD_ARG: budget < 0 or budget > 2^32 - chain_offset. */
+int fg_abc_round_prior(fg_abc *a, double tol, int64_t budget, int64_t *accepted, int64_t *attempts);
+/* Opens a stage on the current population (abc.rs:570-580): downloads its f64 coordinates and weights once, computes
+ * kernel_bandwidths (abc.rs:751-773), the weight total and the in-order cumulative weights on the host in the reference's order and
+ * uploads them; empties the stage's accepted set.  FG_E_STATE: no population, or a weight total <= 0. */
+int fg_abc_stage_begin(fg_abc *a);
+/* The attempts of stage `stage` >= 1 (abc.rs:582-621): base particle by sample_index (abc.rs:816-830: u total <= cum[i], first such i,
+ * else the last), its cells copied, every f64 site moved by bandwidth x Normal(0,1), discrete sites unchanged; the scoring run at the
+ * proposal (log_prior = its first accumulator); simulate; distance; accepted when isfinite(log_prior) && dist <= tol.  Outputs as
+ * fg_abc_round_prior, for the stage's accepted set.  FG_E_STATE without fg_abc_stage_begin. */
+int fg_abc_round_stage(fg_abc *a, uint32_t stage, double tol, int64_t budget, int64_t *accepted, int64_t *attempts);
+/* Closes the stage (abc.rs:612-616, 632-643): log_denom of the accepted particles against the previous population (fg_abc_mixture),
+ * log_w = log_prior - log_denom normalised by log_sum_exp (1 / n each when the normaliser is not finite), and the accepted set
+ * becomes the current population.  FG_E_STATE: no open stage or nothing accepted. */
+int fg_abc_stage_end(fg_abc *a);
+/* What the last round of attempts decided, [B] each (any may be NULL): the base particle (-1 in the prior stage), the distance, the
+ * log-prior, the accept flag (0 for attempts beyond the budget); abc.rs:586-610. */
+int fg_abc_last_round(fg_abc *a, int64_t *h_index, double *h_dist, double *h_log_prior, int32_t *h_accept);
+/* A population (ABCParticle, abc.rs:457-463, with the engine's bookkeeping): which = 0 the current one, 1 the open stage's accepted
+ * set.  *out_n particles; h_cells [S][*out_n], the others [*out_n]; any output may be NULL (call once with all NULL for the size). */
+int fg_abc_get_population(fg_abc *a, int which, int64_t *out_n, void *h_cells, double *h_weights, double *h_dist,
+                          int64_t *h_attempt, double *h_log_prior, double *h_log_denom);
+/* Replaces the current population (abc.rs:457-463): 1 <= n <= capacity; h_cells [S][n] and h_weights [n] are required, the others
+ * may be NULL (zeros).  Closes an open stage without a result. */
+int fg_abc_set_population(fg_abc *a, int64_t n, const void *h_cells, const double *h_weights, const double *h_dist,
+                          const int64_t *h_attempt, const double *h_log_prior, const double *h_log_denom);
+
 /* ------------------------------------------------------------------ HMC
  * Replaces hmc_chain / HmcSession (src/inference/hmc.rs:566-583, 643-920). */
 enum { FG_GRAD_FD_DENSE = 0,   /* hmc.rs:304-329 verbatim: 2d full model runs per gradient */

@@ -9,6 +9,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_diag_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_qstream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_cstream { _p: [u8; 0] }
+#[repr(C)] pub struct fg_abc { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -107,6 +108,24 @@ extern "C" {
     // posterior / prior predictive draws of the observe statements and their pointwise log-likelihood (inference_integration.rs:717-740)
     pub fn fg_predict_eval(e: *mut fg_engine, d_draws: *const c_void, n: c_int, h_rows: *const i32, n_rows: c_int, iter0: u32,
                            h_sel: *const i32, n_sel: c_int, d_yrep: *mut c_void, d_loglik: *mut f64) -> c_int;
+    // ---- ABC (abc.rs:132-226 the distances, :776-799 the kernel mixture of weighted ABC-SMC)
+    pub fn fg_abc_distance(e: *mut fg_engine, d_sim: *const f64, k: c_int, b: i64, h_observed: *const f64, n_observed: c_int, kind: c_int,
+                           h_weights: *const f64, n_weights: c_int, d_dist: *mut f64) -> c_int;
+    pub fn fg_abc_mixture(e: *mut fg_engine, d_x: *const f64, m: i64, d_centers: *const f64, n: i64, d: c_int, h_weights: *const f64,
+                          h_std: *const f64, d_out: *mut f64) -> c_int;
+    // rounds of attempts and the stages of abc_smc_weighted (abc.rs:283-325, 520-650)
+    pub fn fg_abc_new(e: *mut fg_engine, sim_kind: c_int, h_sel: *const i32, n_sel: c_int, h_observed: *const f64, n_observed: c_int, kind: c_int,
+                      h_weights: *const f64, n_weights: c_int, capacity: i64, out: *mut *mut fg_abc) -> c_int;
+    pub fn fg_abc_free(a: *mut fg_abc);
+    pub fn fg_abc_round_prior(a: *mut fg_abc, tol: f64, budget: i64, accepted: *mut i64, attempts: *mut i64) -> c_int;
+    pub fn fg_abc_stage_begin(a: *mut fg_abc) -> c_int;
+    pub fn fg_abc_round_stage(a: *mut fg_abc, stage: u32, tol: f64, budget: i64, accepted: *mut i64, attempts: *mut i64) -> c_int;
+    pub fn fg_abc_stage_end(a: *mut fg_abc) -> c_int;
+    pub fn fg_abc_last_round(a: *mut fg_abc, h_index: *mut i64, h_dist: *mut f64, h_log_prior: *mut f64, h_accept: *mut i32) -> c_int;
+    pub fn fg_abc_get_population(a: *mut fg_abc, which: c_int, out_n: *mut i64, h_cells: *mut c_void, h_weights: *mut f64, h_dist: *mut f64,
+                                 h_attempt: *mut i64, h_log_prior: *mut f64, h_log_denom: *mut f64) -> c_int;
+    pub fn fg_abc_set_population(a: *mut fg_abc, n: i64, h_cells: *const c_void, h_weights: *const f64, h_dist: *const f64, h_attempt: *const i64,
+                                 h_log_prior: *const f64, h_log_denom: *const f64) -> c_int;
     // ---- HMC (hmc.rs:566-583, 643-920)
     pub fn fg_hmc_config_default(cfg: *mut fg_hmc_config);
     pub fn fg_hmc_init(e: *mut fg_engine, cfg: *const fg_hmc_config, n_warmup: c_int) -> c_int;
