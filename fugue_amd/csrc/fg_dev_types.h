@@ -21,6 +21,9 @@ struct FgHmcDev {
     double *alpha_sum; unsigned long long *n_div;
     double *p0_scratch;                             // [d][C] (eps search / injected momentum)
     int L; double h, target; int grad_mode; int use_mass;
+    // derived from h (fg_internal_hmc_set_cfg; never exported): n / (2h) == fma(n, div2_hi, n * div2_lo) when div2 is set (fg_div2.h);
+    // k_hmc_sep_steps's folded instantiations, which the plan picks only then, read hi and lo
+    double div2_hi, div2_lo; int div2;
 };
 
 

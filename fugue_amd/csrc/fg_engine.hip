@@ -12,6 +12,7 @@
 // temporaries + momentum) is a [(n_slots + d)][64] tile of doubles in LDS.
 #include "fg_engine_internal.h"
 #include "fg_hmc_sep_plan.h"
+#include "fg_div2.h"
 #include "fg_gradstream.h"
 #include "fg_cold.h"
 
@@ -949,6 +950,9 @@ void fg_internal_hmc_set_cfg(fg_engine *e, const fg_hmc_config *cfg) {
     e->H.L = cfg->n_leapfrog > 1 ? cfg->n_leapfrog : 1;        // hmc.rs:684
     e->H.h = cfg->finite_diff_eps; e->H.target = cfg->target_accept;
     e->H.grad_mode = cfg->grad_mode;
+    // k_hmc_sep_steps's folded loop divides by 2h in two instructions: only when the host can prove that exact for this h (else the plan
+    // gets no fold, fg_hmc_sep_launch); hi and lo are 0 when refused
+    e->H.div2 = fg_div2_prove(2.0 * e->H.h, &e->H.div2_hi, &e->H.div2_lo) ? 1 : 0;
 }
 
 // does fg_hmc_step run this program through the kernel compiled at run time ahead of the stream kernel (fg_hmc_jit_first, fg_hmc_split_plan.h)?
@@ -1219,6 +1223,7 @@ int fg_hmc_set_n_leapfrog(fg_engine *e, int n_leapfrog) {     // hmc.rs:751-753
 }
 const char *fg_hmc_last_kernel(const fg_engine *e) { return e ? e->last_hmc_kernel.c_str() : ""; }
 const char *fg_mh_last_kernel(const fg_engine *e) { return e ? e->last_mh_kernel.c_str() : ""; }
+int fg_hmc_short_quotient(const fg_engine *e) { return (e && e->hmc_ready && e->H.div2) ? 1 : 0; }
 int fg_hmc_is_warming_up(const fg_engine *e) { return (e && e->hmc_ready && e->iter < e->n_warmup) ? 1 : 0; }   // hmc.rs:780-782
 int64_t fg_hmc_iterations(const fg_engine *e) { return (e && e->hmc_ready) ? (int64_t)e->iter : 0; }             // hmc.rs:785-787
 

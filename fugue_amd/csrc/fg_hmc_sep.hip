@@ -96,6 +96,9 @@ __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const char *p) { return *(const f
       const double lp_ = FG_SEP_LP(k, zp_), lm_ = FG_SEP_LP(k, zm_);                                    \
       outp = (zp_ != zp_) ? FG_NEG_INF : lp_; outm = (zm_ != zm_) ? FG_NEG_INF : lm_; }
 
+template <typename RB> struct FgSepScalarRb { static constexpr bool value = false; };
+template <> struct FgSepScalarRb<const FG_AS4 char *> { static constexpr bool value = true; };
+
 // The whole trajectory of one coordinate: (q, p) -> (q', p') after L leapfrog steps (hmc.rs:353-407) with step size e, then
 // the endpoint-score terms of its statements.  NOBS observe records follow the coordinate's own sample record; P2: every
 // sigma is a power of two (no quotient branch at all).  The sums are fg_grec_math's: log_prior = the sample record,
@@ -109,12 +112,16 @@ __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const char *p) { return *(const f
 // AN = FG_GRAD_ANALYTIC: g_i = sum over the coordinate's records of d lp / d q_i = -(q - c) / sigma^2, one evaluation per record,
 // the additions of fg_grec_math's analytic branch in the same order ((x - mu) is +-(q - c) and its coefficient -+1: the same bits).
 // FOLD (CHECK = false, host switch FG_HMC_SEP_FOLD): P2 records take FG_SEP_DUALS, and the range test of the quotient leaves the step
-// too.  g is always fg_div_const's; a 32-bit running maximum over the high word of n records whether some |n| fell outside
+// too.  g is taken without a test; a 32-bit running maximum over the high word of n records whether some |n| fell outside
 // [2^-823, 2^953) (0, inf and NaN included), and such a trajectory ends with a NaN momentum: the caller's non-finite test re-runs it
 // with the CHECK instance, whose per-step test and true division give the exact bits.  In range the two quotients are the same.
+// FOLD also takes the quotient in two instructions, g = fma(n, c_hi, RN(n c_lo)) with c_hi = RN(1 / 2h), c_lo = RN(1 / 2h - c_hi):
+// the host proved for this run's 2h (fg_div2_prove, fg_div2.h) that this is RN(n / (2h)) for every n of the same window, and hands
+// the plan FOLD only then.  c_hi and c_lo are wave-uniform (SGPRs), one per instruction; the chain from n to the kick is 2 long
+// instead of fg_div_const's 5.  The deferred range test and the checked re-run (fg_div_const, true division) are unchanged.
 template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, bool FOLD = false, typename RB = const FG_AS4 char *>
 __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p_io, double emi, double hk, int L, double h, double two_h,
-                                                  double rcp_2h, double *terms, int tw, int nobs_rt) {
+                                                  double rcp_2h, double *terms, int tw, int nobs_rt, double c_hi = 0.0, double c_lo = 0.0) {
 #define FG_SEP_HAS(k) (NOBS >= 0 ? NOBS >= (k) : nobs_rt >= (k))
     FG_SEP_LOAD(0) FG_SEP_LOAD(1) FG_SEP_LOAD(2) FG_SEP_LOAD(3)
     double q = q_io, p = p_io;
@@ -124,6 +131,10 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
 #define FG_SEP_NHS2(k) if (FOLDED && (k > 0 || !U0) && FG_SEP_HAS(k)) { nhs2_##k = fg_dbl(b##k[2], b##k[3]); asm volatile("" : "+v"(nhs2_##k)); }
     FG_SEP_NHS2(0) FG_SEP_NHS2(1) FG_SEP_NHS2(2) FG_SEP_NHS2(3)
 #undef FG_SEP_NHS2
+    // FOLD: the loop's three uniform constants start a live range of their own here -- as values that live for the whole launch the
+    // register allocator may park them in VGPR lanes and read them back in EVERY step (8 v_readlane per step in the headline instantiation)
+    // (records by scalar loads only: in the half- and quarter-tile forms, whose records sit in VGPRs, the split costs 12 to 18 spilled VGPRs)
+    if (FOLD && !CHECK && !AN && FgSepScalarRb<RB>::value) asm volatile("" : "+s"(h), "+s"(c_hi), "+s"(c_lo));
     uint32_t nrange = 0u;                                        // FOLD: max over the steps of 2 |hi(n)| - 2 hi(2^-823), mod 2^32
     for (int gs = 0; gs <= L; ++gs) {
         double g;
@@ -172,7 +183,8 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         }
         }
         const double n = tp - tm;
-        g = fg_div_const(n, two_h, rcp_2h);                      // (lp - lm) / (2h), hmc.rs:322
+        if (!CHECK && FOLD) g = __builtin_fma(n, c_hi, n * c_lo);   // (lp - lm) / (2h), hmc.rs:322: proved exact for this h on the host
+        else g = fg_div_const(n, two_h, rcp_2h);
         if (!CHECK && FOLD) {                                    // in range iff 2 |hi(n)| - 0x19000000 < 0xde000000 (mod 2^32)
             uint32_t hi = (uint32_t)__double2hiint(n);
             asm("" : "+v"(hi));                                  // (else the shift is folded into the 64-bit word: v_alignbit + v_and)
@@ -394,7 +406,14 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     const int stagger = seg.c[FG_SEP_WMAX] <= -2 ? -seg.c[FG_SEP_WMAX] - 1 : 0;   // 1: the second half of the grid starts late, 2: the odd tiles
     const double *mi = MASS ? H.m_inv + c : nullptr;
     const double *ms = MASS ? H.mass_sqrt + c : nullptr;
-    const double h = fg_uniform(H.h), two_h = fg_uniform(2.0 * H.h), rcp_2h = fg_uniform(1.0 / (2.0 * H.h));
+    const double h = fg_uniform(H.h), two_h = FOLD ? 0.0 : fg_uniform(2.0 * H.h), rcp_2h = FOLD ? 0.0 : fg_uniform(1.0 / (2.0 * H.h));
+    const double c_hi = H.div2_hi, c_lo = H.div2_lo;   // (kernel arguments: SGPRs as they are)  FOLD: RN(1 / 2h) and RN(1 / 2h - c_hi), proved on the host
+    // (two_h / rcp_2h are 0 in FOLD kernels.  fg_dense_trajectory and the DENSE loop below also take them: they are MODE 1 / 3 code, and the
+    // static_assert(!FOLD || MODE == 0) above keeps FOLD out of those instantiations.)
+    // FOLD: only the checked re-run still divides by 2h itself. It forms 2h and RN(1 / 2h) where it runs (the same IEEE operations, the same
+    // bits; the empty asm keeps them from being hoisted), so the trajectories' registers hold c_hi / c_lo alone: with both pairs live
+    // for the launch the resident NC = 4 forms spill, and reload inside the leapfrog loop.
+#define FG_SEP_2H(th, rc) double th = two_h, rc = rcp_2h; if (FOLD) { double hh_ = h; asm volatile("" : "+v"(hh_)); th = 2.0 * hh_; rc = 1.0 / th; }
     const uint32_t sk0 = (uint32_t)X.seed, sk1 = (uint32_t)(X.seed >> 32), gchain = X.chain0 + (uint32_t)c;
     // RES: the wave's k1 - k0 <= NC coordinates for the whole launch -- committed values, proposals, mass, record offsets
     const int nown = k1 - k0;
@@ -487,12 +506,13 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                 const double emi = MASS ? e * mii : e;
                 const double q0 = q, p0 = p;
                 const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + roff[j]);
-                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R);
+                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo);
                 if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                     // (inline, not fg_sep_trajectory_checked: no call.  Its generic record mix computes the same bits for this shape:
                     // every record is POW2 -- (x - mu) * (1 / sigma) -- and a U0 record is exactly N(0, 1), see FG_SEP_LP_U)
                     q = q0; p = p0;
-                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R) || bad;
+                    FG_SEP_2H(th, rc)
+                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R>(rb, q, p, emi, hk, L, h, th, rc, termsR, tw, NOBS_R) || bad;
                 }
                 qpr[j] = q;                                              // the proposal
                 kin1R[i * tw] = MASS ? p * p * mii : p * p;
@@ -632,23 +652,25 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             const double q0 = q, p0 = p;
             if (HALF) {
                 const char *rb = (const char *)(P.sep + P.sep_coord[ci].off);
-#define FG_SEP_CALLH(NO, UU) fg_sep_trajectory<NO, true, false, false, UU, FOLD, const char *>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO)
+#define FG_SEP_CALLH(NO, UU) fg_sep_trajectory<NO, true, false, false, UU, FOLD, const char *>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO, c_hi, c_lo)
                 if ((cd.n & 512) && nobs == 1) FG_SEP_CALLH(1, true);
                 else if (nobs == 1) FG_SEP_CALLH(1, false); else if (nobs == 0) FG_SEP_CALLH(0, false); else if (nobs == 2) FG_SEP_CALLH(2, false); else FG_SEP_CALLH(3, false);
 #undef FG_SEP_CALLH
                 if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
-                    const FgD3 r = fg_sep_trajectory_checked<AN, const char *>(rb, q0, p0, emi, hk, L, h, two_h, rcp_2h, terms, tw, nobs);
+                    FG_SEP_2H(th, rc)
+                    const FgD3 r = fg_sep_trajectory_checked<AN, const char *>(rb, q0, p0, emi, hk, L, h, th, rc, terms, tw, nobs);
                     q = r.a; p = r.b; bad = bad || (on && r.c != 0.0);
                 }
             } else {
             const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + cd.off);
-#define FG_SEP_CALL(NO, PP) fg_sep_trajectory<NO, PP, false, AN, false, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO)
-            if (!AN && (cd.n & 512) && nobs == 1) fg_sep_trajectory<1, true, false, false, true, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, 1);
+#define FG_SEP_CALL(NO, PP) fg_sep_trajectory<NO, PP, false, AN, false, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO, c_hi, c_lo)
+            if (!AN && (cd.n & 512) && nobs == 1) fg_sep_trajectory<1, true, false, false, true, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, 1, c_hi, c_lo);
             else if (cd.n & 256) { if (nobs == 1) FG_SEP_CALL(1, true); else if (nobs == 0) FG_SEP_CALL(0, true); else if (nobs == 2) FG_SEP_CALL(2, true); else FG_SEP_CALL(3, true); }
             else { if (nobs == 1) FG_SEP_CALL(1, false); else if (nobs == 0) FG_SEP_CALL(0, false); else if (nobs == 2) FG_SEP_CALL(2, false); else FG_SEP_CALL(3, false); }
 #undef FG_SEP_CALL
             if (__builtin_expect(__any(!fg_finite(p)), 0)) {           // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
-                const FgD3 r = fg_sep_trajectory_checked<AN, const FG_AS4 char *>(rb, q0, p0, emi, hk, L, h, two_h, rcp_2h, terms, tw, nobs);
+                FG_SEP_2H(th, rc)
+                const FgD3 r = fg_sep_trajectory_checked<AN, const FG_AS4 char *>(rb, q0, p0, emi, hk, L, h, th, rc, terms, tw, nobs);
                 q = r.a; p = r.b; bad = bad || r.c != 0.0;
             }
             }
@@ -799,7 +821,7 @@ static FgSepVariant fg_sep_variants[] = { FG_SEP_VARIANTS(FG_SEP_ENTRY) };
 int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *draws, int first_sample_t, double *pos_all, double *info) {
     if (!fg_hmc_sep_gate(e->gt, e->P.sep != nullptr, e->sep_disabled, e->d)) return FG_E_UNSUPPORTED;   // (fg_hmc_sep_plan says so too: every HMC launch asks here first, most read no switch)
     const FgSepPlanIn in = { e->C, e->d, e->n_simd, e->n_slots, e->P.n_sep_free, e->P.n_sstream, e->cfg.grad_mode, e->H.use_mass != 0, e->mw_override,
-                             e->gt, e->sep_disabled, e->sep_res_disabled, e->sep_fold_disabled, e->prog->sep_fold, &e->prog->sep_coord, &e->prog->sep,
+                             e->gt, e->sep_disabled, e->sep_res_disabled, e->sep_fold_disabled, e->prog->sep_fold && e->H.div2 != 0 /* the folded loop divides by 2h in two instructions: proved for this h */, &e->prog->sep_coord, &e->prog->sep,
                              fg_env_switch("FG_HMC_SEP_HALF"), fg_env_switch("FG_HMC_DENSE_FAST"), fg_env_switch("FG_HMC_SUM4"), fg_env_switch("FG_HMC_PRIO"),
                              fg_env_switch("FG_HMC_STAGGER"), fg_env_switch("FG_HMC_PREDRAW") };
     FgSepPlan pl;

@@ -36,7 +36,7 @@ inline bool operator==(const FgSepKey &a, const FgSepKey &b) {
 struct FgSepPlanIn {
     long long C; int d, n_simd, n_slots, n_sep_free, n_sstream;
     int grad_mode; bool use_mass; int mw_override;         // (FG_HMC_WAVES)
-    bool gt, sep_disabled, res_disabled, fold_disabled, sep_fold;   // (fg_engine: FG_HMC_SEP, FG_HMC_SEP_RESIDENT, FG_HMC_SEP_FOLD; fg_program: sep_fold)
+    bool gt, sep_disabled, res_disabled, fold_disabled, sep_fold;   // (fg_engine: FG_HMC_SEP, FG_HMC_SEP_RESIDENT, FG_HMC_SEP_FOLD; sep_fold: fg_program's, and 2h passed fg_div2_prove)
     const std::vector<FgSepCoord> *coord; const std::vector<FgSepRec> *rec;   // fg_program's sep_coord / sep
     FgSwitch sep_half, dense_fast, sum4, prio, stagger, predraw;   // FG_HMC_SEP_HALF, FG_HMC_DENSE_FAST, FG_HMC_SUM4, FG_HMC_PRIO, FG_HMC_STAGGER, FG_HMC_PREDRAW
 };

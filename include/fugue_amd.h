@@ -335,6 +335,10 @@ int fg_hmc_set_step_size(fg_engine *e, double eps);
 int     fg_hmc_set_n_leapfrog(fg_engine *e, int n_leapfrog);
 int     fg_hmc_is_warming_up(const fg_engine *e);
 int64_t fg_hmc_iterations(const fg_engine *e);
+/* 1 when the host proved, for this session's finite_diff_eps, that the quotient by 2h of the sparse register-resident
+ * trajectories (k_hmc_sep_steps' folded loop) is exact in two instructions; 0 when the divisor was refused -- the kernels then
+ * run without the folded loop -- or no HMC session is initialised.  Results are the same bits either way. */
+int     fg_hmc_short_quotient(const fg_engine *e);
 /* Which kernel the engine's last fg_hmc_step / fg_hmc_run launch ran, with its waves per 64-chain tile, e.g.
  * "k_hmc_sep_steps W=8" (independent sites: whole trajectories in registers), "k_hmc_lin_steps W=8" (dense regressions:
  * observation-major gradient), "k_hmc_stream_steps W=4" (gradient / score streams), "k_hmc_steps W=1" (interpreter);
