@@ -165,13 +165,14 @@ int dev_upload(T **p, const std::vector<T> &v) {
 
 // One launch of a library kernel picked from a table of typed pointers (all instantiations of a kernel template have one
 // function type: the arguments are checked against it here, once).  A tile above 64 KB needs the function's dynamic-LDS limit
-// raised, once per (device, function): `raised` is the table entry's mask of the devices that have it.
+// raised, once per (device, function): `raised` is the table entry's mask of the devices that have it.  LDS_MAX: what it is raised
+// to -- a CU's 160 KB less the kernel's static LDS (the runtime refuses a limit that the two together exceed).
 template <typename T> struct fg_same { using type = T; };
-template <typename... P>
+template <int LDS_MAX = 160 * 1024, typename... P>
 int fg_launch(fg_engine *e, void (*fn)(P...), unsigned long long &raised, dim3 grid, dim3 block, size_t lds, const typename fg_same<P>::type &...args) {
     const unsigned long long dev_bit = 1ull << (e->device & 63);
     if (lds > 64 * 1024 && !(raised & dev_bit)) {
-        const hipError_t he = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        const hipError_t he = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
         if (he != hipSuccess) { fg_set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(he)); return FG_E_HIP; }
         raised |= dev_bit;
     }

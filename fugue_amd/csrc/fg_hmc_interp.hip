@@ -17,6 +17,7 @@
 #include "fg_engine_internal.h"
 #include "fg_cold.h"
 #include "fg_jit.h"
+#include "fg_smc_plan.h"
 
 #define FG_MWI_MAX 16         /* waves per tile */
 
@@ -361,23 +362,17 @@ bool fg_hmc_jit_has_ad(fg_engine *e) { return jit_hmc_module(e) == FG_OK && e->j
 // adaptive_smc's rejuvenation move of a program without a score stream through the compiled model (k_smc_jit_rejuv, fg_hmc_jit_body.h);
 // FG_E_UNSUPPORTED: the interpreter kernel k_smc_rejuv<-1> takes it.  n_blk_out: blocks launched (rows of M.blk that k_smc_adapt adds).
 int fg_smc_jit_rejuv_launch(fg_engine *e, const FgSmcDev &M, const FgSmcScalars *st, uint32_t move_id, unsigned *n_blk_out, const long long *vsrc, double *pmax) {
-    if (e->S > FG_SMC_HIST) return FG_E_UNSUPPORTED;
+    FgSmcJitShape sh;      // (asked ahead of the module: the callers come with 512 n_slots <= 150 KB and n_slots > S, so its tile test refuses nothing the site test let through)
+    if (int rc = fg_smc_jit_rejuv_shape(e->S, e->C, &sh)) return rc;
     if (int rc = jit_hmc_module(e)) return rc;
-    const size_t tile = (size_t)e->S * FG_WAVE * sizeof(double);
-    if (tile > 150 * 1024) return FG_E_UNSUPPORTED;
-    // tiles (waves) per block: four; sixteen for a program of a few sites (fewer blocks, fewer rows of counts and block maxima: 0.39 -> 0.375 ms
-    // per 1 048 576-particle run of the one-site model)
-    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(16 * tile <= 16 * 1024 ? 16 : 4, (150 * 1024) / tile));
-    const size_t lds = tile * wpb;
-    if (lds > 64 * 1024 && !e->jit_rejuv_attr) {
+    if (sh.lds > FG_SMC_LDS_PLAIN && !e->jit_rejuv_attr) {
         if (hipFuncSetAttribute((const void *)e->jit_fn_rejuv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { (void)hipGetLastError(); return FG_E_UNSUPPORTED; }
         e->jit_rejuv_attr = true;
     }
-    const unsigned nblk = (unsigned)((e->C + (long long)FG_WAVE * wpb - 1) / ((long long)FG_WAVE * wpb));
     FgSmcDev Mv = M;
     void *args[] = { &e->P, &e->X, &Mv, &st, &move_id, &vsrc, &pmax };
-    HIPCHK(hipModuleLaunchKernel(e->jit_fn_rejuv, nblk, 1, 1, FG_WAVE * wpb, 1, 1, (unsigned)lds, e->stream, args, nullptr));
-    if (n_blk_out) *n_blk_out = nblk;
+    HIPCHK(hipModuleLaunchKernel(e->jit_fn_rejuv, sh.nblk, 1, 1, FG_WAVE * sh.wpb, 1, 1, (unsigned)sh.lds, e->stream, args, nullptr));
+    if (n_blk_out) *n_blk_out = sh.nblk;
     return FG_OK;
 }
 

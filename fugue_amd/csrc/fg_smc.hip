@@ -19,23 +19,11 @@
 #include "fg_engine_internal.h"
 #include "fg_gradstream.h"
 #include "fg_cold.h"
+#include "fg_smc_plan.h"
 
-#define RED_BLOCKS 512
-#define RED_THREADS 256
-#define SCAN_THREADS 256
-#define SCAN_ITEMS 8
-#define SCAN_CHUNK (SCAN_THREADS * SCAN_ITEMS)
-
+// (RED_*, SCAN_*, ESS_*, ESS2_* and FG_SMC_WPB: fg_smc_plan.h, with the arena's layout and the rejuvenation plan)
 // (FgSmcScalars, FgSmcDev: fg_dev_types.h -- the rejuvenation kernel compiled at run time takes them too)
-// few, large blocks: a pass is dominated by what follows the sums -- one ticket atomic per block, the last block's sweep over the
-// blocks' partials -- not by the two exps per particle (512 x 256: 1.13 ms per run, 128 x 512: 1.00 ms, 2048 x 256: 2.3 ms)
-#ifndef ESS_BLOCKS
-#define ESS_BLOCKS 128
-#endif
-#ifndef ESS_THREADS
-#define ESS_THREADS 512
-#endif
-#define ESS_MAXC 8
+static_assert(FG_SMC_PLAN_WAVE == FG_WAVE && FG_SMC_PLAN_HIST == FG_SMC_HIST && sizeof(FgSmcScalars) <= FG_SMC_SCALARS_BYTES, "fg_smc_plan.h restates these");
 
 // ---------------------------------------------------------------------------------------
 // reductions:  v_i = lw_i + (b - beta) * ll_i     (smc.rs:590-594 / :512-516)
@@ -277,111 +265,16 @@ __global__ __launch_bounds__(ESS_THREADS) void k_smc_ess_pass(const double *lw, 
     if (threadIdx.x == 0) fg_ess_decide(st, ess_c, nc);
 }
 
-// The same pass when the incoming log-weights are UNIFORM (every next_beta call of adaptive_smc: log_w = -ln N after the
-// previous step's resample, smc.rs:476,538-540): ESS(b) = (sum t_i)^2 / sum t_i^2 with t_i = exp((b - beta)(ll_i - L)),
-// L = max ll (the common factor of the weights cancels).  The 7 midpoints of the depth-3 tree are equally spaced,
-// b_k = lo + k delta, so t_ik = E_i R_i^k with E_i = exp((lo - beta)(ll_i - L)), R_i = exp(delta (ll_i - L)): two exps
-// and seven multiplications per particle instead of seven exps.  The particle with ll_i = L contributes exactly 1 to every
-// sum (no underflow of the whole sum); like k_smc_ess_pass these values only decide comparisons.
-__global__ __launch_bounds__(ESS_THREADS) void k_smc_ess_pass_uniform(const double *ll, long long n, FgSmcScalars *st, const double *ll_max, double *part /*[gridDim.x][ESS_MAXC][3]*/) {
-    __shared__ double sh[ESS_THREADS / 64][ESS_MAXC][2];
-    __shared__ int is_last;
-    if (st->done) return;
-    const int nc = st->n_cand, first = st->first;
-    const double beta = st->beta, L = *ll_max;
-    const int nt = nc - first;                                       // tree candidates: 1, 3 or 7, heap order over [lo, hi]
-    const int lv = nt >= 7 ? 3 : (nt >= 3 ? 2 : 1);
-    const double lo = first ? beta : st->lo, hi = first ? 1.0 : st->hi;
-    // heap node j of the tree sits at grid position k(j) of lo + k (hi - lo) / 2^lv:  lv = 3: 4, 2, 6, 1, 3, 5, 7;  lv = 2: 2, 1, 3;
-    // lv = 1: 1.  (The candidates the decision walk RECORDS are the reference's 0.5 * (lo + hi) chains in st->cand; the grid
-    // points used here agree with them to the last bit or two.)
-    const double d0 = lo - beta, d1 = 1.0 - beta, dl = (hi - lo) / (double)(1 << lv);
-    double s1[ESS_MAXC], s2[ESS_MAXC];
-#pragma unroll
-    for (int q = 0; q < ESS_MAXC; ++q) { s1[q] = 0.0; s2[q] = 0.0; }
-    const bool allneg = isinf(L) && L < 0.0;
-#define ESS_ADD(q, tv) { const double tv_ = (tv); s1[q] += tv_; s2[q] += tv_ * tv_; }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n && !allneg; i += (long long)gridDim.x * blockDim.x) {
-        const double x = ll[i] - L;                                  // <= 0; -inf: the particle has no weight at any b > beta
-        if (isinf(x) && x < 0.0) continue;
-        const double E = exp(d0 * x), R = exp(dl * x);
-        const double p1 = E * R, p2 = p1 * R, p3 = p2 * R;
-        if (first) {                                                 // candidate 0 = b = 1, then the depth-3 tree over [beta, 1]
-            ESS_ADD(0, exp(d1 * x))
-            const double p4 = p3 * R, p5 = p4 * R, p6 = p5 * R, p7 = p6 * R;
-            ESS_ADD(1, p4) ESS_ADD(2, p2) ESS_ADD(3, p6) ESS_ADD(4, p1) ESS_ADD(5, p3) ESS_ADD(6, p5) ESS_ADD(7, p7)
-        } else if (lv == 3) {
-            const double p4 = p3 * R, p5 = p4 * R, p6 = p5 * R, p7 = p6 * R;
-            ESS_ADD(0, p4) ESS_ADD(1, p2) ESS_ADD(2, p6) ESS_ADD(3, p1) ESS_ADD(4, p3) ESS_ADD(5, p5) ESS_ADD(6, p7)
-        } else if (lv == 2) { ESS_ADD(0, p2) ESS_ADD(1, p1) ESS_ADD(2, p3) }
-        else ESS_ADD(0, p1)
-    }
-#undef ESS_ADD
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int q = 0; q < ESS_MAXC; ++q) {
-        if (q < nc) {
-            for (int o = 32; o > 0; o >>= 1) { s1[q] += __shfl_down(s1[q], o, 64); s2[q] += __shfl_down(s2[q], o, 64); }
-            if (lane == 0) { sh[wv][q][0] = s1[q]; sh[wv][q][1] = s2[q]; }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < (unsigned)nc) {
-        const int q = threadIdx.x;
-        double a = sh[0][q][0], b = sh[0][q][1];
-        for (int k = 1; k < ESS_THREADS / 64; ++k) { a += sh[k][q][0]; b += sh[k][q][1]; }
-        double *p = part + ((long long)blockIdx.x * ESS_MAXC + q) * 3;
-        p[0] = 0.0; p[1] = a; p[2] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int tk = atomicAdd(&st->ticket, 1u);
-        is_last = tk == gridDim.x - 1;
-        if (is_last) __threadfence();
-    }
-    __syncthreads();
-    if (!is_last) return;
-    // last block: every candidate's sums over the blocks in ONE sweep (thread t takes blocks t, t + 256, ...; lanes, then waves,
-    // in index order: a fixed tree)
-    __shared__ double ess_c[ESS_MAXC];
-    __shared__ double shl[ESS_THREADS / 64][ESS_MAXC][2];
-    double a[ESS_MAXC], b[ESS_MAXC];
-#pragma unroll
-    for (int q = 0; q < ESS_MAXC; ++q) { a[q] = 0.0; b[q] = 0.0; }
-    for (int bk = threadIdx.x; bk < (int)gridDim.x; bk += blockDim.x) {
-        const double *p = part + (long long)bk * ESS_MAXC * 3;
-#pragma unroll
-        for (int q = 0; q < ESS_MAXC; ++q) if (q < nc) { a[q] += __builtin_nontemporal_load(p + 3 * q + 1); b[q] += __builtin_nontemporal_load(p + 3 * q + 2); }
-    }
-#pragma unroll
-    for (int q = 0; q < ESS_MAXC; ++q) {
-        if (q < nc) {
-            for (int o = 32; o > 0; o >>= 1) { a[q] += __shfl_down(a[q], o, 64); b[q] += __shfl_down(b[q], o, 64); }
-            if (lane == 0) { shl[wv][q][0] = a[q]; shl[wv][q][1] = b[q]; }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < (unsigned)nc) {
-        const int q = threadIdx.x;
-        double ta = shl[0][q][0], tb = shl[0][q][1];
-        for (int k = 1; k < ESS_THREADS / 64; ++k) { ta += shl[k][q][0]; tb += shl[k][q][1]; }
-        const double e = ta * ta / tb;
-        ess_c[q] = (allneg || !(ta > 0.0) || !isfinite(e)) ? (double)n : e;                       // smc.rs:598-601
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) fg_ess_decide(st, ess_c, nc);
-}
-
-// ---- next_beta for UNIFORM incoming weights WITHOUT a cross-block epilogue --------------------------------------------------
-// k_smc_ess_pass_uniform ends every pass with a ticket atomic per block, two fences and the last block's sweep + single-thread
-// decision: a chain of device-scope round trips.  Here the kernel boundary IS the grid barrier: pass p + 1 starts with EVERY block
-// combining the block partials of pass p (a fixed tree: the same numbers in every block) and walking the decision tree itself -- a
-// few hundred redundant additions per block instead of the epilogue -- then forms its candidates' sums and leaves its own
-// partials.  Bracket state and partials are double-buffered by pass parity; block 0 records the new bracket.  The decisions are
-// fg_ess_decide's: the same comparisons `ESS(mid) < target` on the reference's midpoints 0.5 (lo + hi) (smc.rs:612-619), three
-// levels per pass; pass 0 also evaluates b = 1 (smc.rs:604-607) and reduces the block maxima of ll itself.
+// ---- next_beta for UNIFORM incoming weights (the ess2 passes) ----------------------------------------------------------------
+// Every next_beta call of adaptive_smc meets uniform log-weights (log_w = -ln N after the previous step's resample, smc.rs:476,
+// 538-540), so ESS(b) = (sum t_i)^2 / sum t_i^2 with t_i = exp((b - beta)(ll_i - L)), L = max ll: the common factor of the weights
+// cancels, and the particle with ll_i = L contributes exactly 1 to every sum (the whole sum cannot underflow).
+// A pass has no cross-block epilogue: the kernel boundary IS the grid barrier.  Pass p + 1 starts with EVERY block combining the block
+// partials of pass p (a fixed tree: the same numbers in every block) and walking the decision tree itself -- a few hundred redundant
+// additions per block, no ticket atomic, no fence, no last block -- then forms its candidates' sums and leaves its own partials.
+// Bracket state and partials are double-buffered by pass parity; block 0 records the new bracket.  The decisions are the reference's:
+// the comparisons `ESS(mid) < target` on its midpoints 0.5 (lo + hi) (smc.rs:612-619), three levels per pass; pass 0 also evaluates
+// b = 1 (smc.rs:604-607) and reduces the block maxima of ll itself.  Like k_smc_ess_pass's, these values only decide comparisons.
 struct FgEssBracket { double lo, hi, bnew; int iters, done, first, extra;     // extra: candidate 0 of the next pass is b = xb (first: b = 1)
                       double s1_hi, s1_one;      // sum_i exp((b - beta)(ll_i - max ll)) at b = hi and at b = 1: the reweight's log-sum-exp needs no pass of its own (k_smc_ess2_apply)
                       // the zoom passes (see fg_ess_step): ESS(za) >= target > ESS(zb) with the two values, the window of the next pass
@@ -402,12 +295,6 @@ __device__ __forceinline__ double fg_wave_sum63(double v) {
     v = fg_dpp_add<0x142, 0xa>(v); v = fg_dpp_add<0x143, 0xc>(v);
     return v;
 }
-#ifndef ESS2_BLOCKS
-#define ESS2_BLOCKS 256
-#endif
-#ifndef ESS2_THREADS
-#define ESS2_THREADS 512
-#endif
 #ifndef ESS2_UNROLL
 #define ESS2_UNROLL 4
 #endif
@@ -445,7 +332,7 @@ __device__ __forceinline__ void fg_ess_window(FgEssBracket &B, double target) {
     if (wl < B.za || B.zk == 8) wl = B.za;
     B.wl = wl;
 }
-// The bracket after a pass whose candidates had effective sample sizes ess_c (fg_ess_decide as a pure function).
+// The bracket after a pass whose candidates had effective sample sizes ess_c (k_smc_ess_pass's fg_ess_decide as a pure function).
 //
 // next_beta's answer (smc.rs:588-622) is hi after 64 halvings of [beta, 1], each decided by `ESS(mid) < target`.  ESS(b) does not
 // increase with b (d ln ESS / d b = 2 (E_b[ll] - E_2b[ll]) <= 0 under uniform incoming weights), so every one of those decisions
@@ -599,7 +486,9 @@ __global__ __launch_bounds__(ESS2_THREADS) void k_smc_ess2_pass(const double *ll
         if (host_flag) { *host_flag = flag_base | (1 + (B.done ? 1 : 0)); __threadfence_system(); }   // pinned host memory: the host launches pass p + 1 when it sees pass p's flag
     }
     if (B.done) return;
-    // the candidates' sums over this block's particles (the two-exp form of k_smc_ess_pass_uniform)
+    // the candidates' sums over this block's particles, in the two-exp form: the candidates of a pass are equally spaced, b_k = lo + k dl,
+    // so t_ik = E_i R_i^k with E_i = exp((lo - beta) x_i), R_i = exp(dl x_i), x_i = ll_i - L -- two exps and seven multiplications per
+    // particle instead of seven exps
     const int first = B.first, x0 = (first || B.extra) ? 1 : 0;     // candidate 0: b = 1 (first pass) or b = xb
     const int left = 64 - B.iters, lv = B.zmode ? 3 : (first ? 3 : (left < 3 ? left : 3));
     const int nc = x0 + (1 << lv) - 1;
@@ -806,13 +695,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_smc_final_norm(double *lw, dou
         if (isfinite(lse)) { const double nz = lw[i] - lse; lw[i] = nz; w[i] = exp(nz); }
         else { lw[i] = -log((double)n); w[i] = 1.0 / (double)n; }
     }
-}
-__global__ __launch_bounds__(RED_THREADS) void k_smc_max_finish(const double *part_max, int nb, double *out) {   // max of the block maxima
-    __shared__ double sh[RED_THREADS / 64];
-    double m = -INFINITY;
-    for (int k = threadIdx.x; k < nb; k += blockDim.x) m = fmax(m, part_max[k]);
-    m = block_reduce_max(m, sh);
-    if (threadIdx.x == 0) *out = m;
 }
 // arms the lookahead search for the current beta: first pass = {b = 1} + the midpoint tree of [beta, 1]
 __global__ void k_smc_ess_begin(FgSmcScalars *st) {
@@ -1031,7 +913,6 @@ __global__ void k_smc_gather(const long long *src, long long *dst, const double 
 // ---------------------------------------------------------------------------------------
 // rejuvenation: tempered_single_site_mh (smc.rs:631-688), one move per particle
 // ---------------------------------------------------------------------------------------
-#define FG_SMC_WPB(SCORE) ((SCORE) < 0 ? 1 : ((SCORE) == 2 ? 4 : 16))   /* tiles (waves) per block of k_smc_rejuv<SCORE> */
 // SCORE: 0 = score stream of fast Normals, 3 = + linear predictors / option selects / Categorical tables, 2 = + general
 // distribution records, -1 = the interpreter (programs without a score stream).  The stream variants carry no interpreter
 // code and run 4 tiles per 256-thread block.
@@ -1254,16 +1135,35 @@ static hipError_t smc_wait(hipStream_t s) {
         if (q != hipErrorNotReady) return q;
     }
 }
-struct Reducer {     // scratch for the two-pass reductions
-    double *part_max = nullptr, *part_sum = nullptr, *ess_part = nullptr;
+// What a standalone device primitive holds for the length of one call -- device buffers, pinned host memory, a stream: released when the
+// call returns, whichever way.  (The engine's calls own nothing here: their buffers are regions of the engine's arena.)
+struct SmcScope {
+    std::vector<void *> dev; void *pinned = nullptr; hipStream_t stream = nullptr;
+    SmcScope() = default;
+    SmcScope(const SmcScope &) = delete;
+    SmcScope &operator=(const SmcScope &) = delete;
+    SmcScope(SmcScope &&o) noexcept : dev(std::move(o.dev)), pinned(o.pinned), stream(o.stream) { o.dev.clear(); o.pinned = nullptr; o.stream = nullptr; }
+    ~SmcScope() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void *p : dev) (void)hipFree(p);
+        if (pinned) (void)hipHostFree(pinned);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    template <typename T> int alloc(T **p, size_t n) {              // dev_alloc: n zeroed elements
+        *p = nullptr;
+        const int rc = dev_alloc(p, n);
+        if (*p) dev.push_back(*p);
+        return rc;
+    }
+};
+struct Reducer {     // scratch for the two-pass reductions: regions of the engine's arena, or a standalone call's own
+    double *part_max = nullptr, *part_sum = nullptr, *ess_part = nullptr;   // [max(RED_BLOCKS, tiles)], [2 RED_BLOCKS], k_smc_ess_pass: [ESS_BLOCKS][ESS_MAXC][3]
     double *ess2 = nullptr;      // k_smc_ess2_pass: part[2][ESS2_BLOCKS][ESS_MAXC][2] | lmax[2] | FgEssBracket brk[2]
     static size_t ess2_doubles() { return (size_t)2 * ESS2_BLOCKS * ESS_MAXC * 2 + 2 + 2 * sizeof(FgEssBracket) / 8 + 2; }
-    int init() {
-        if (dev_alloc(&part_max, RED_BLOCKS) || dev_alloc(&part_sum, 2 * RED_BLOCKS) || dev_alloc(&ess_part, (size_t)ESS_BLOCKS * ESS_MAXC * 3 + 8) || dev_alloc(&ess2, ess2_doubles())) return FG_E_HIP;
+    int own(SmcScope &sc) {
+        if (sc.alloc(&part_max, RED_BLOCKS) || sc.alloc(&part_sum, 2 * RED_BLOCKS) || sc.alloc(&ess_part, (size_t)ESS_BLOCKS * ESS_MAXC * 3) || sc.alloc(&ess2, ess2_doubles())) return FG_E_HIP;
         return FG_OK;
     }
-    void free_all() { if (part_max) (void)hipFree(part_max); if (part_sum) (void)hipFree(part_sum); if (ess_part) (void)hipFree(ess_part); if (ess2) (void)hipFree(ess2);
-                      part_max = part_sum = ess_part = ess2 = nullptr; }
     // the passes alone: part_max[0 .. n_pmax) holds block maxima of ll (their producer's: k_smc_split_acc_max or the step's last
     // rejuvenation sweep); what follows them is k_smc_ess2_apply.  The host looks at pass 1's bracket through pinned memory.
     int ess2_passes(hipStream_t s, const double *ll, long long n, const double *beta_ptr, double target, int n_pmax, FgSmcHostScalars *hs_host,
@@ -1311,18 +1211,12 @@ struct Reducer {     // scratch for the two-pass reductions
         return FG_OK;
     }
     // next_beta (smc.rs:588-622) -> st->bnew: ESS at b = 1, then 64 bisections, three levels per pass (k_smc_ess_pass)
-    // uniform_lw: the caller guarantees that every lw_i is the same number (adaptive_smc: always) -> the two-exp pass
-    int next_beta(hipStream_t s, const double *lw, const double *ll, long long n, FgSmcScalars *st, bool uniform_lw = false) {
+    // for any incoming log-weights (fg_device_next_beta); adaptive_smc's are uniform and take ess2_passes
+    int next_beta(hipStream_t s, const double *lw, const double *ll, long long n, FgSmcScalars *st) {
         hipLaunchKernelGGL(k_smc_ess_begin, dim3(1), dim3(1), 0, s, st);
         const int nb = (int)std::min<long long>(ESS_BLOCKS, (n + ESS_THREADS - 1) / ESS_THREADS);
-        if (uniform_lw) {
-            hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, ll, (const double *)nullptr, n, (const double *)&st->one, (const double *)&st->beta, part_max);
-            hipLaunchKernelGGL(k_smc_max_finish, dim3(1), dim3(RED_THREADS), 0, s, (const double *)part_max, RED_BLOCKS, ess_part + (size_t)ESS_BLOCKS * ESS_MAXC * 3);
-        }
-        for (int pass = 0; pass < 23; ++pass) {      // pass 0: b = 1 and levels 1-3; passes 1..20: three levels each; pass 21: the 64th; one spare (a no-op once done)
-            if (uniform_lw) hipLaunchKernelGGL(k_smc_ess_pass_uniform, dim3(nb), dim3(ESS_THREADS), 0, s, ll, n, st, (const double *)(ess_part + (size_t)ESS_BLOCKS * ESS_MAXC * 3), ess_part);
-            else hipLaunchKernelGGL(k_smc_ess_pass, dim3(nb), dim3(ESS_THREADS), 0, s, lw, ll, n, st, ess_part);
-        }
+        // pass 0: b = 1 and levels 1-3; passes 1..20: three levels each; pass 21: the 64th; one spare (a no-op once done)
+        for (int pass = 0; pass < 23; ++pass) hipLaunchKernelGGL(k_smc_ess_pass, dim3(nb), dim3(ESS_THREADS), 0, s, lw, ll, n, st, ess_part);
         hipLaunchKernelGGL(k_smc_ess_end, dim3(1), dim3(1), 0, s, st);
         HIPCHK(hipGetLastError());
         return FG_OK;
@@ -1330,27 +1224,17 @@ struct Reducer {     // scratch for the two-pass reductions
     // lse / ESS of v = lw + (b - beta) ll, then k_smc_finish(phase)
     int run(hipStream_t s, const double *lw, const double *ll, long long n, FgSmcScalars *st, const double *b_ptr, int phase) {
         hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, lw, ll, n, b_ptr, (const double *)&st->beta, part_max);
-        hipLaunchKernelGGL(k_smc_red_sum, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, lw, ll, n, b_ptr, (const double *)&st->beta,
-                           (const double *)part_max, part_sum);
-        hipLaunchKernelGGL(k_smc_finish, dim3(1), dim3(RED_THREADS), 0, s, st, (const double *)part_max, (const double *)part_sum, RED_BLOCKS, n, phase);
-        HIPCHK(hipGetLastError());
-        return FG_OK;
+        return run_sum_only(s, lw, ll, n, st, b_ptr, phase);
     }
 };
 
-struct Scanner {     // scratch for the prefix sum
-    double *chunk = nullptr, *cum = nullptr; long long cap = 0;
-    bool external = false;      // buffers belong to the caller's arena
-    int ensure(long long n) {
-        if (n <= cap) return FG_OK;
-        if (external) { fg_set_error("scan scratch too small"); return FG_E_BAD_ARG; }
-        free_all();
-        const long long nc = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        if (dev_alloc(&chunk, (size_t)nc) || dev_alloc(&cum, (size_t)n)) return FG_E_HIP;
+struct Scanner {     // scratch for the prefix sum: regions of the engine's arena, or a standalone call's own
+    double *chunk = nullptr, *cum = nullptr; long long cap = 0;   // chunk totals [ceil(cap / SCAN_CHUNK)], cumulative weights [cap]
+    int own(SmcScope &sc, long long n) {
+        if (sc.alloc(&chunk, (size_t)((n + SCAN_CHUNK - 1) / SCAN_CHUNK)) || sc.alloc(&cum, (size_t)n)) return FG_E_HIP;
         cap = n;
         return FG_OK;
     }
-    void free_all() { if (!external) { if (chunk) (void)hipFree(chunk); if (cum) (void)hipFree(cum); } chunk = cum = nullptr; cap = 0; }
     void search(hipStream_t s, long long n, int method, double U, const double *d_u, unsigned long long seed, uint32_t step, long long *d_idx) {
         const long long nc = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
         if (nc <= 4096)        // (the chunk ends fit a block's LDS)
@@ -1359,8 +1243,7 @@ struct Scanner {     // scratch for the prefix sum
     }
     int indices(hipStream_t s, const double *w, long long n, int method, double U, const double *d_u, unsigned long long seed,
                 uint32_t step, long long *d_idx) {
-        int rc = ensure(n);
-        if (rc) return rc;
+        if (n > cap) { fg_set_error("scan scratch too small"); return FG_E_BAD_ARG; }
         const int nc = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
         hipLaunchKernelGGL(k_scan_chunk_sums, dim3(nc), dim3(SCAN_THREADS), 0, s, w, n, chunk);
         hipLaunchKernelGGL(k_scan_chunk_offsets, dim3(1), dim3(SCAN_THREADS), 0, s, chunk, nc);
@@ -1378,40 +1261,32 @@ struct SmcWs {
     FgSmcDev M{}; FgSmcScalars *st = nullptr; Reducer R; Scanner SC;
     double *d_lw = nullptr, *d_w = nullptr, *d_ll2 = nullptr, *d_lp2 = nullptr, *d_red = nullptr, *d_chunk2 = nullptr;
     long long *d_vals2 = nullptr, *d_idx = nullptr;
-    size_t o_ls = 0, o_st = 0;
-    char *base = nullptr;
+    char *adapt_reset = nullptr; size_t adapt_reset_bytes = 0;   // log_scale, acc, tot (FgSmcArena)
 };
+// lay the arena out (fg_smc_arena_layout), grow it if need be, bind the pointers
 int smc_workspace(fg_engine *e, SmcWs &W) {
     const long long N = e->C;
-    const int S = e->S;
-    const size_t Sn = (size_t)std::max(1, S);
-    const long long n_chunks = (N + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    const size_t max_blk = (size_t)((N + FG_WAVE - 1) / FG_WAVE);          // k_smc_rejuv blocks at one tile per block
-    size_t arena_off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = arena_off; arena_off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_ll = carve(N * 8), o_lp = carve(N * 8), o_scale = carve(Sn * 8), o_ls = carve(Sn * 8), o_acc = carve(Sn * 8), o_tot = carve(Sn * 8),
-                 o_st = carve(sizeof(FgSmcScalars)), o_lw = carve(N * 8), o_w = carve(N * 8), o_ll2 = carve(N * 8), o_lp2 = carve(N * 8), o_vals2 = carve(Sn * N * 8),
-                 o_idx = carve(N * 8), o_pmax = carve(std::max<size_t>(RED_BLOCKS, max_blk) * 8), o_psum = carve(2 * RED_BLOCKS * 8), o_ess = carve(((size_t)ESS_BLOCKS * ESS_MAXC * 3 + 8) * 8),
-                 o_ess2 = carve(Reducer::ess2_doubles() * 8),
-                 o_chunk = carve((size_t)n_chunks * 8), o_chunk2 = carve((size_t)n_chunks * 8), o_cum = carve(N * 8), o_blk = carve(max_blk * 2 * Sn * 4), o_red = carve(64);
-    if (e->smc_arena_bytes < arena_off) {
+    const FgSmcArena A = fg_smc_arena_layout(N, e->S, Reducer::ess2_doubles());
+    if (e->smc_arena_bytes < A.bytes) {
         if (e->smc_arena) { HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipFree(e->smc_arena)); e->smc_arena = nullptr; e->smc_arena_bytes = 0; }
-        HIPCHK(hipMalloc(&e->smc_arena, arena_off));
-        e->smc_arena_bytes = arena_off;
+        HIPCHK(hipMalloc(&e->smc_arena, A.bytes));
+        e->smc_arena_bytes = A.bytes;
         e->smc_pop_ready = false;
     }
     char *ar = (char *)e->smc_arena;
-    W.base = ar; W.o_ls = o_ls; W.o_st = o_st;
+#define AT(T, name) ((T *)(ar + A.off[FG_SMC_R_##name]))
     FgSmcDev &M = W.M;
-    M.ll = (double *)(ar + o_ll); M.lprior = (double *)(ar + o_lp); M.scale = (double *)(ar + o_scale); M.log_scale = (double *)(ar + o_ls);
-    M.acc = (long long *)(ar + o_acc); M.tot = (long long *)(ar + o_tot); M.sw_n = nullptr; M.sw_a = nullptr;
-    M.blk = (unsigned int *)(ar + o_blk); M.S = S;
-    W.st = (FgSmcScalars *)(ar + o_st);
-    W.d_lw = (double *)(ar + o_lw); W.d_w = (double *)(ar + o_w); W.d_ll2 = (double *)(ar + o_ll2); W.d_lp2 = (double *)(ar + o_lp2);
-    W.d_vals2 = (long long *)(ar + o_vals2); W.d_idx = (long long *)(ar + o_idx); W.d_red = (double *)(ar + o_red);
-    W.R.part_max = (double *)(ar + o_pmax); W.R.part_sum = (double *)(ar + o_psum); W.R.ess_part = (double *)(ar + o_ess); W.R.ess2 = (double *)(ar + o_ess2);
-    W.d_chunk2 = (double *)(ar + o_chunk2);
-    W.SC.chunk = (double *)(ar + o_chunk); W.SC.cum = (double *)(ar + o_cum); W.SC.cap = N; W.SC.external = true;
+    M.ll = AT(double, ll); M.lprior = AT(double, lprior); M.scale = AT(double, scale); M.log_scale = AT(double, log_scale);
+    M.acc = AT(long long, acc); M.tot = AT(long long, tot); M.sw_n = nullptr; M.sw_a = nullptr;
+    M.blk = AT(unsigned int, blk); M.S = e->S;
+    W.st = AT(FgSmcScalars, st);
+    W.d_lw = AT(double, lw); W.d_w = AT(double, w); W.d_ll2 = AT(double, ll2); W.d_lp2 = AT(double, lp2);
+    W.d_vals2 = AT(long long, vals2); W.d_idx = AT(long long, idx); W.d_red = AT(double, red);
+    W.R.part_max = AT(double, part_max); W.R.part_sum = AT(double, part_sum); W.R.ess_part = AT(double, ess_part); W.R.ess2 = AT(double, ess2);
+    W.d_chunk2 = AT(double, chunk2);
+    W.SC.chunk = AT(double, chunk); W.SC.cum = AT(double, cum); W.SC.cap = N;
+#undef AT
+    W.adapt_reset = ar + A.adapt_reset_off; W.adapt_reset_bytes = A.adapt_reset_bytes;
     return FG_OK;
 }
 
@@ -1481,6 +1356,209 @@ static int smc_global_tile(fg_engine *e) {
     return FG_OK;
 }
 
+// ---- the rejuvenation sweep: plan (fg_smc_plan.h), look up, launch ----
+using FgSmcRejuvKernel = void (*)(FgProgramDev, FgChainCtx, FgSmcDev, const FgSmcScalars *, uint32_t, const long long *, double *);
+using FgSmcSeqKernel = void (*)(FgProgramDev, FgChainCtx, FgSmcDev, const FgSmcScalars *, uint32_t, int);
+template <typename K> struct FgSmcRejuvVariant { int score; bool gt; K fn; unsigned long long raised; };       // raised: fg_launch
+#define FG_SMC_REJUV_ENTRY(SCORE, GT) { SCORE, GT, k_smc_rejuv<SCORE, GT>, 0 },
+static FgSmcRejuvVariant<FgSmcRejuvKernel> fg_smc_rejuv_variants[] = { FG_SMC_REJUV_VARIANTS(FG_SMC_REJUV_ENTRY) };
+#undef FG_SMC_REJUV_ENTRY
+#define FG_SMC_REJUV_ENTRY(SCORE, GT) { SCORE, GT, k_smc_rejuv_seq<SCORE, GT>, 0 },
+static FgSmcRejuvVariant<FgSmcSeqKernel> fg_smc_rejuv_seq_variants[] = { FG_SMC_REJUV_VARIANTS(FG_SMC_REJUV_ENTRY) };
+#undef FG_SMC_REJUV_ENTRY
+template <typename V, size_t n> static V *smc_rejuv_variant(V (&table)[n], const FgSmcRejuvKey &key) {
+    V *v = std::find_if(table, table + n, [&](const V &q) { return q.score == key.score && q.gt == key.gt; });
+    if (v == table + n) { fg_set_error("no rejuvenation kernel for this program"); return nullptr; }
+    return v;
+}
+// the plan of this engine's sweeps; FG_E_UNSUPPORTED: no coordinate to move (callers ask d first)
+static int smc_rejuv_plan_for(const fg_engine *e, bool sequential, bool from_run, FgSmcRejuvPlan *pl) {
+    FgSmcRejuvIn in{};
+    in.N = e->C; in.S = e->S; in.d = e->d; in.lds_score = e->lds_score; in.tw = e->tw;
+    in.has_sstream = e->P.sstream ? true : false; in.sstream_kinds = e->P.sstream_kinds; in.sstream_gen = e->P.sstream_gen ? true : false;
+    in.jit_state = e->jit_state; in.sequential = sequential; in.from_run = from_run;
+    return fg_smc_rejuv_plan(in, pl);
+}
+// One batched sweep (a move per particle) and the fold of its counts into the adaptation.  vsrc / pmax: k_smc_rejuv's two extras.
+// n_blk: blocks launched = rows of M.blk that k_smc_adapt added = block maxima behind pmax.
+static int smc_rejuv_sweep(fg_engine *e, const FgSmcDev &M, const FgSmcScalars *st, const FgSmcRejuvPlan &pl, uint32_t move_id, const long long *vsrc, double *pmax, unsigned *n_blk) {
+    *n_blk = pl.nblk;
+    if (!(pl.try_compiled && fg_smc_jit_rejuv_launch(e, M, st, move_id, n_blk, vsrc, pmax) == FG_OK)) {
+        if (pl.try_compiled && std::getenv("FG_JIT_VERBOSE")) fprintf(stderr, "fugue_amd: no compiled rejuvenation sweep: %s\n", pl.name.c_str());
+        auto *v = smc_rejuv_variant(fg_smc_rejuv_variants, pl.key);
+        if (!v) return FG_E_UNSUPPORTED;
+        // (raised to the 150 KB the plan keeps to: the kernel has its counts and block maxima in static LDS beside the tiles)
+        if (int rc = fg_launch<FG_SMC_LDS_MAX>(e, v->fn, v->raised, dim3(pl.nblk), dim3(pl.threads), pl.lds, e->P, e->X, M, st, move_id, vsrc, pmax)) return rc;
+    }
+    hipLaunchKernelGGL(k_smc_adapt, dim3((unsigned)e->S), dim3(256), 0, e->stream, M, e->S, (int)*n_blk);
+    return FG_OK;
+}
+// n_moves moves per particle in the reference's order (k_smc_rejuv_seq adapts after every move itself)
+static int smc_rejuv_sequential(fg_engine *e, const FgSmcDev &M, const FgSmcScalars *st, const FgSmcRejuvPlan &pl, uint32_t move0, int n_moves) {
+    auto *v = smc_rejuv_variant(fg_smc_rejuv_seq_variants, pl.key);
+    if (!v) return FG_E_UNSUPPORTED;
+    return fg_launch<FG_SMC_LDS_MAX>(e, v->fn, v->raised, dim3(pl.nblk), dim3(pl.threads), pl.lds, e->P, e->X, M, st, move0, n_moves);
+}
+// U of systematic resampling (smc.rs:255-270): one draw per tempering step
+static double smc_systematic_u(const fg_engine *e, uint32_t step) { FgStream rs = fg_stream(e->seed, 0, step, FG_RNG_SMC_RESAMPLE); return fg_rng_u01(rs); }
+// the resampled population replaces the current one: particles, log-likelihoods and log-priors by ancestor, then back in place
+static int smc_commit_resampled(fg_engine *e, SmcWs &W) {
+    const long long N = e->C;
+    const int S = e->S, TB = 256, NB = (int)((N + TB - 1) / TB);
+    hipStream_t s = e->stream;
+    hipLaunchKernelGGL(k_smc_gather, dim3(NB), dim3(TB), 0, s, (const long long *)e->d_values, W.d_vals2, (const double *)W.M.ll, W.d_ll2,
+                       (const double *)W.M.lprior, W.d_lp2, (const long long *)W.d_idx, S, N);
+    HIPCHK(hipMemcpyAsync(e->d_values, W.d_vals2, (size_t)S * N * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(W.M.ll, W.d_ll2, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(W.M.lprior, W.d_lp2, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+    return FG_OK;
+}
+
+// ---- adaptive_smc (smc.rs:455-581) in the reference's own steps: set up; the importance-sampling branch, or per tempering step temper,
+// resample, rejuvenate and the block maxima for the next step; then the final normalisation and the download ----
+constexpr int SMC_TB = 256;     // threads per block of the elementwise kernels
+enum SmcEvidence { SMC_EV_DEVICE, SMC_EV_STEP, SMC_EV_PINNED };   // the log-evidence at the end: in the device scalars, in SmcRun::log_evidence, in the pinned copy (read behind the final synchronisation)
+struct SmcRun {
+    fg_engine *e; const fg_smc_config *cfg; long long N; int NB; hipStream_t s;   // (NB: blocks of SMC_TB threads over the particles)
+    SmcWs W; FgSmcHostScalars *hs, *hs_dev;                  // the arena; the pinned scalars and their device address
+    FgSmcScalars h;                                          // host copy of the device scalars
+    double lw0;                                              // log_w = -ln N at every step's start (smc.rs:476,538-540)
+    bool moves, sweep_io; FgSmcRejuvPlan rejuv;              // the program has coordinates to move; batched sweeps take the resampled population and leave the block maxima; how they launch
+    // what a step leaves for the later ones
+    int n_pmax;                  // rows of R.part_max with block maxima of ll -- set: smc_run_block_maxima, smc_run_rejuvenate; read: smc_run_temper
+    bool fin_ready;              // the last reweight left the sums of the final normalisation -- set: smc_run_temper; read: smc_run_finish
+    SmcEvidence evidence;        // set: smc_run_temper; read: smc_run_finish
+    double log_evidence;         // ... of SMC_EV_STEP -- set: smc_run_temper; read: smc_run_finish
+    long long n_runs;            // model runs -- set: smc_run_setup (the prior draw), smc_run_rejuvenate; read: smc_run_finish
+    std::vector<double> betas;   // the ladder, one entry per step -- set: smc_run_importance, smc_run_temper; read: smc_run_steps, smc_run_finish
+};
+static int smc_run_setup(SmcRun &r) {
+    fg_engine *e = r.e;
+    const size_t Sn = (size_t)std::max(1, e->S);
+    if (int rc = smc_workspace(e, r.W)) return rc;
+    if (!e->smc_host) HIPCHK(hipHostMalloc(&e->smc_host, sizeof(FgSmcHostScalars), hipHostMallocMapped));
+    r.hs = (FgSmcHostScalars *)e->smc_host;
+    HIPCHK(hipHostGetDevicePointer((void **)&r.hs_dev, r.hs, 0));
+    std::memset(r.hs, 0, sizeof(*r.hs));
+    std::memset(&r.h, 0, sizeof(r.h));
+    r.h.one = 1.0; r.h.beta = 0.0;
+    r.h.target_ess = std::min(std::max(r.cfg->ess_threshold * (double)r.N, 1.0), (double)r.N);     // smc.rs:481
+    // the run's scalars, and scale = 1, log_scale = 0, acc = tot = 0 (DiminishingAdaptation::new): one launch
+    hipLaunchKernelGGL(k_smc_init, dim3((unsigned)((Sn + SMC_TB - 1) / SMC_TB)), dim3(SMC_TB), 0, r.s, r.W.st, r.h, r.W.M, (long long)Sn);
+    // smc_prior_particles (smc.rs:764-790): through the compiled model for a large population (the draw is a tenth of a 1 048 576-particle
+    // run on the interpreter kernel; the unit is compiled once per program and cached)
+    if (e->gt || r.N < (1LL << 18) || fg_jit_prior_launch(e, 0, FG_RNG_SMC_PRIOR, e->d_acc, nullptr, true) != FG_OK)
+        if (int rc = fg_launch_prior(e, 0, FG_RNG_SMC_PRIOR, e->d_acc, nullptr)) return rc;
+    r.lw0 = -std::log((double)r.N);
+    r.n_runs = r.N; r.n_pmax = RED_BLOCKS; r.fin_ready = false; r.evidence = SMC_EV_DEVICE; r.log_evidence = 0.0;
+    // (planned behind the prior draw: a large population has just had the compiled unit built, which the plan of a fast-Normal stream asks about)
+    r.moves = e->d > 0;
+    r.sweep_io = r.moves && !r.cfg->sequential_adaptation;   // (every batched sweep kernel takes vsrc / pmax: k_smc_rejuv<...>, k_smc_jit_rejuv)
+    return r.moves ? smc_rejuv_plan_for(e, r.cfg->sequential_adaptation != 0, true, &r.rejuv) : FG_OK;
+}
+// rejuvenation_steps == 0: a single importance-sampling reweight (smc.rs:484-493)
+static int smc_run_importance(SmcRun &r) {
+    hipLaunchKernelGGL(k_smc_split_acc, dim3(r.NB), dim3(SMC_TB), 0, r.s, (const double *)r.e->d_acc, r.W.M.lprior, r.W.M.ll, r.N);
+    hipLaunchKernelGGL(k_smc_is_weights, dim3(r.NB), dim3(SMC_TB), 0, r.s, r.W.d_lw, (const double *)r.W.M.ll, r.N);
+    r.betas.push_back(1.0);
+    return r.W.R.run(r.s, r.W.d_lw, nullptr, r.N, r.W.st, (const double *)&r.W.st->one, 3);      // log_evidence = lse(combined)
+}
+// next_beta on the device (smc.rs:588-622), reweight and evidence (:512-529): smc_temper_step.  fused: the step left the chunk totals of
+// the resampling prefix sum.
+static int smc_run_temper(SmcRun &r, int step, bool *fused) {
+    fg_engine *e = r.e;
+    if (step >= 10000) { int one = 1; HIPCHK(hipMemcpyAsync(&r.W.st->force_one, &one, sizeof(int), hipMemcpyHostToDevice, r.s)); }   // smc.rs:504-506
+    e->smc_epoch = (e->smc_epoch + 1) & 0x0fffffff;
+    if (e->smc_epoch == 0) e->smc_epoch = 1;                // (0 is what an unwritten flag reads as)
+    SmcStep o;
+    if (int rc = smc_temper_step(r.s, r.W.R, r.W.M.ll, r.N, r.n_pmax, r.W.st, step, r.lw0, r.W.d_lw, r.W.d_w, r.W.SC.chunk, r.W.d_chunk2, r.hs, r.hs_dev, e->smc_epoch,
+                                 smc_zoom_default(), smc_force_sum_env(), step < 10000, r.h, o)) return rc;
+    *fused = o.fused;
+    r.evidence = o.ends ? SMC_EV_PINNED : (o.fused ? SMC_EV_STEP : SMC_EV_DEVICE);
+    r.log_evidence = o.log_evidence;
+    r.fin_ready = o.ends || (o.fused && o.beta >= 1.0);
+    r.betas.push_back(o.beta);
+    return FG_OK;
+}
+// ancestors from the new weights (smc.rs:534-540).  A batched sweep of a program with coordinates reads the resampled population where
+// k_smc_gather left it and writes every site back (no copy), scores every particle again (ll / log-prior need no gather) and leaves the
+// block maxima of ll (sweep_io); otherwise the population is committed here.
+static int smc_run_resample(SmcRun &r, int step, bool fused) {
+    fg_engine *e = r.e;
+    const int n_chunks = (int)((r.N + SCAN_CHUNK - 1) / SCAN_CHUNK), method = r.cfg->resampling_method;
+    Scanner &SC = r.W.SC;
+    const double U = method == FG_RESAMPLE_SYSTEMATIC ? smc_systematic_u(e, (uint32_t)step) : 0.0;
+    if (fused) {                                 // the chunk totals are there: offsets + prefix sum in one launch, then the search
+        hipLaunchKernelGGL(k_scan_cumsum_off, dim3((unsigned)n_chunks), dim3(SCAN_THREADS), 0, r.s, (const double *)r.W.d_w, r.N, (const double *)SC.chunk, n_chunks, SC.cum);
+        SC.search(r.s, r.N, method, U, nullptr, (unsigned long long)e->seed, (uint32_t)step, r.W.d_idx);
+    } else if (int rc = SC.indices(r.s, r.W.d_w, r.N, method, U, nullptr, e->seed, (uint32_t)step, r.W.d_idx)) return rc;
+    if (!r.sweep_io) return smc_commit_resampled(e, r.W);
+    hipLaunchKernelGGL(k_smc_gather, dim3(r.NB), dim3(SMC_TB), 0, r.s, (const long long *)e->d_values, r.W.d_vals2, (const double *)nullptr, (double *)nullptr,
+                       (const double *)nullptr, (double *)nullptr, (const long long *)r.W.d_idx, e->S, r.N);
+    return FG_OK;
+}
+// rejuvenation_steps moves per particle (smc.rs:541-559).  have_pmax: the last sweep left the block maxima of ll.
+static int smc_run_rejuvenate(SmcRun &r, int step, bool *have_pmax) {
+    const int K = r.cfg->rejuvenation_steps;
+    if (r.rejuv.global_tile) { if (int rc = smc_global_tile(r.e)) return rc; }
+    if (r.cfg->sequential_adaptation) {
+        r.n_runs += 2 * r.N * K;
+        return smc_rejuv_sequential(r.e, r.W.M, r.W.st, r.rejuv, (uint32_t)((step - 1) * K), K);
+    }
+    for (int k = 0; k < K; ++k) {
+        const long long *vsrc = (r.sweep_io && k == 0) ? (const long long *)r.W.d_vals2 : (const long long *)nullptr;
+        double *pmax = (r.sweep_io && k == K - 1) ? r.W.R.part_max : (double *)nullptr;
+        unsigned n_blk = 0;
+        if (int rc = smc_rejuv_sweep(r.e, r.W.M, r.W.st, r.rejuv, (uint32_t)((step - 1) * K + k), vsrc, pmax, &n_blk)) return rc;
+        if (pmax) { *have_pmax = true; r.n_pmax = (int)n_blk; }
+        r.n_runs += 2 * r.N;
+    }
+    return FG_OK;
+}
+// the block maxima of ll for the next step's first pass, where no sweep left them
+static void smc_run_block_maxima(SmcRun &r) {
+    FgSmcScalars *st = r.W.st;
+    hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, r.s, (const double *)r.W.M.ll, (const double *)nullptr, r.N, (const double *)&st->one, (const double *)&st->one, r.W.R.part_max);
+    r.n_pmax = RED_BLOCKS;
+}
+// attach the final normalised weights (smc.rs:565-575), download, and the run's one synchronisation
+static int smc_run_finish(SmcRun &r, double *h_log_w, double *h_weights, fg_smc_result *res, double *h_betas, int max_betas) {
+    SmcWs &W = r.W;
+    if (r.fin_ready) hipLaunchKernelGGL(k_smc_final_norm, dim3((unsigned)std::min<long long>(1024, (r.N + 4 * SCAN_THREADS - 1) / (4 * SCAN_THREADS))), dim3(SCAN_THREADS), 0, r.s, W.d_lw, W.d_w, r.N, (const double *)W.d_chunk2, W.st);
+    else {
+        if (int rc = W.R.run(r.s, W.d_lw, nullptr, r.N, W.st, (const double *)&W.st->one, 4)) return rc;
+        hipLaunchKernelGGL(k_smc_normalize, dim3(r.NB), dim3(SMC_TB), 0, r.s, W.d_lw, W.d_w, r.N, (const FgSmcScalars *)W.st);
+    }
+    if (r.evidence == SMC_EV_DEVICE) HIPCHK(hipMemcpyAsync(&r.h, W.st, sizeof(r.h), hipMemcpyDeviceToHost, r.s));
+    if (h_log_w) HIPCHK(hipMemcpyAsync(h_log_w, W.d_lw, (size_t)r.N * 8, hipMemcpyDeviceToHost, r.s));
+    if (h_weights) HIPCHK(hipMemcpyAsync(h_weights, W.d_w, (size_t)r.N * 8, hipMemcpyDeviceToHost, r.s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(r.s));
+    r.e->smc_pop_ready = true;
+    res->log_evidence = r.evidence == SMC_EV_DEVICE ? r.h.log_evidence : (r.evidence == SMC_EV_PINNED ? r.hs->log_evidence : r.log_evidence);
+    res->n_steps = (int)r.betas.size(); res->n_model_runs = r.n_runs;
+    if (h_betas) for (int i = 0; i < (int)r.betas.size() && i < max_betas; ++i) h_betas[i] = r.betas[i];
+    return FG_OK;
+}
+static int smc_run_steps(SmcRun &r, double *h_log_w, double *h_weights, fg_smc_result *res, double *h_betas, int max_betas) {
+    if (int rc = smc_run_setup(r)) return rc;
+    if (r.cfg->rejuvenation_steps == 0) { if (int rc = smc_run_importance(r)) return rc; }
+    else {
+        // particle_log_likelihood (smc.rs:381-383) and the block maxima of ll for the first pass of the first next_beta
+        hipLaunchKernelGGL(k_smc_split_acc_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, r.s, (const double *)r.e->d_acc, r.W.M.lprior, r.W.M.ll, r.N, r.W.R.part_max);
+        for (int step = 1; ; ++step) {                       // smc.rs:501-560
+            bool fused = false, have_pmax = false;
+            if (int rc = smc_run_temper(r, step, &fused)) return rc;
+            if (r.betas.back() >= 1.0) break;                // the ladder ends: nothing to resample for
+            if (int rc = smc_run_resample(r, step, fused)) return rc;
+            if (r.moves) { if (int rc = smc_run_rejuvenate(r, step, &have_pmax)) return rc; }
+            if (!have_pmax) smc_run_block_maxima(r);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return smc_run_finish(r, h_log_w, h_weights, res, h_betas, max_betas);
+}
+
 extern "C" {
 
 void fg_smc_config_default(fg_smc_config *c) {      // SMCConfig::default, smc.rs:181-189
@@ -1488,20 +1566,20 @@ void fg_smc_config_default(fg_smc_config *c) {      // SMCConfig::default, smc.r
     c->resampling_method = FG_RESAMPLE_SYSTEMATIC; c->ess_threshold = 0.5; c->rejuvenation_steps = 0; c->sequential_adaptation = 0;
 }
 
-// ---- standalone device primitives (no program needed) ----
+// ---- standalone device primitives (no program needed; an SmcScope holds what a call allocates) ----
 int fg_device_log_sum_exp(int device, const double *h_x, int64_t n, double *out) {
     int rc = set_device_or_fail(device);
     if (rc) return rc;
     if (!out || n < 0) return FG_E_BAD_ARG;
     if (n == 0) { *out = -INFINITY; return FG_OK; }       // numerical.rs:16-18
-    double *d_x = nullptr; FgSmcScalars *st = nullptr; Reducer R;
-    if (dev_alloc(&d_x, (size_t)n) || dev_alloc(&st, 1) || R.init()) return FG_E_HIP;
+    SmcScope sc; double *d_x = nullptr; FgSmcScalars *st = nullptr; Reducer R;
+    if (sc.alloc(&d_x, (size_t)n) || sc.alloc(&st, 1) || R.own(sc)) return FG_E_HIP;
     HIPCHK(hipMemcpy(d_x, h_x, (size_t)n * 8, hipMemcpyHostToDevice));
-    rc = R.run(nullptr, d_x, nullptr, n, st, (const double *)&st->one, 4);
+    if ((rc = R.run(nullptr, d_x, nullptr, n, st, (const double *)&st->one, 4))) return rc;
     FgSmcScalars h;
-    if (!rc) { hipError_t e_ = hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost); if (e_ != hipSuccess) rc = FG_E_HIP; else *out = h.lse1; }
-    (void)hipFree(d_x); (void)hipFree(st); R.free_all();
-    return rc;
+    if (hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return FG_E_HIP;
+    *out = h.lse1;
+    return FG_OK;
 }
 
 int fg_device_next_beta(int device, double beta, const double *h_log_w, const double *h_ll, int64_t n, double target_ess,
@@ -1509,17 +1587,17 @@ int fg_device_next_beta(int device, double beta, const double *h_log_w, const do
     int rc = set_device_or_fail(device);
     if (rc) return rc;
     if (!out_beta || n <= 0) return FG_E_BAD_ARG;
-    double *d_lw = nullptr, *d_ll = nullptr; FgSmcScalars *st = nullptr; Reducer R;
-    if (dev_alloc(&d_lw, (size_t)n) || dev_alloc(&d_ll, (size_t)n) || dev_alloc(&st, 1) || R.init()) return FG_E_HIP;
+    SmcScope sc; double *d_lw = nullptr, *d_ll = nullptr; FgSmcScalars *st = nullptr; Reducer R;
+    if (sc.alloc(&d_lw, (size_t)n) || sc.alloc(&d_ll, (size_t)n) || sc.alloc(&st, 1) || R.own(sc)) return FG_E_HIP;
     FgSmcScalars h; std::memset(&h, 0, sizeof(h));
     h.beta = beta; h.one = 1.0; h.target_ess = target_ess;
     HIPCHK(hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_lw, h_log_w, (size_t)n * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_ll, h_ll, (size_t)n * 8, hipMemcpyHostToDevice));
-    rc = R.next_beta(nullptr, d_lw, d_ll, n, st);
-    if (!rc) { hipError_t e_ = hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost); if (e_ != hipSuccess) rc = FG_E_HIP; else *out_beta = h.bnew; }
-    (void)hipFree(d_lw); (void)hipFree(d_ll); (void)hipFree(st); R.free_all();
-    return rc;
+    if ((rc = R.next_beta(nullptr, d_lw, d_ll, n, st))) return rc;
+    if (hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return FG_E_HIP;
+    *out_beta = h.bnew;
+    return FG_OK;
 }
 
 // one tempering step of fg_smc_run (smc_temper_step) on the caller's log-likelihoods, from uniform log-weights -ln n.  flags: 1 = plain passes
@@ -1531,215 +1609,59 @@ int fg_device_smc_temper(int device, double beta, const double *h_ll, int64_t n,
     if (rc) return rc;
     if (!h_ll || !out_beta || !out_log_norm || n <= 0 || (flags & ~3)) return FG_E_BAD_ARG;
     const long long N = n, n_chunks = (N + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    double *d_ll = nullptr, *d_lw = nullptr, *d_w = nullptr, *d_chunk = nullptr, *d_chunk2 = nullptr; FgSmcScalars *st = nullptr; Reducer R;
-    FgSmcHostScalars *hs = nullptr, *hs_dev = nullptr; hipStream_t s = nullptr;
-    auto release = [&]() {
-        if (s) (void)hipStreamSynchronize(s);
-        (void)hipFree(d_ll); (void)hipFree(d_lw); (void)hipFree(d_w); (void)hipFree(d_chunk); (void)hipFree(d_chunk2); (void)hipFree(st); R.free_all();
-        if (hs) (void)hipHostFree(hs);
-        if (s) (void)hipStreamDestroy(s);
-    };
-    rc = FG_E_HIP;
-    bool stepped = false;
-    if (!dev_alloc(&d_ll, (size_t)N) && !dev_alloc(&d_lw, (size_t)N) && !dev_alloc(&d_w, (size_t)N) && !dev_alloc(&d_chunk, (size_t)n_chunks) &&
-        !dev_alloc(&d_chunk2, (size_t)n_chunks) && !dev_alloc(&st, 1) && !R.init() &&
-        hipHostMalloc((void **)&hs, sizeof(FgSmcHostScalars), hipHostMallocMapped) == hipSuccess &&
-        hipHostGetDevicePointer((void **)&hs_dev, hs, 0) == hipSuccess && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess) {
-        std::memset(hs, 0, sizeof(*hs));
-        FgSmcScalars h; std::memset(&h, 0, sizeof(h));
-        h.beta = beta; h.one = 1.0; h.target_ess = target_ess; h.beta2[0] = beta; h.beta2[1] = beta;
-        // (blocking uploads from the caller's pageable memory: complete before anything on the stream reads them)
-        if (hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_ll, h_ll, (size_t)N * 8, hipMemcpyHostToDevice) == hipSuccess) {
-            // the block maxima of ll for the first pass: fg_smc_run's source when no rejuvenation sweep left them
-            hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, (const double *)d_ll, (const double *)nullptr, N, (const double *)&st->one, (const double *)&st->one, R.part_max);
-            SmcStep o;
-            stepped = true;
-            rc = smc_temper_step(s, R, d_ll, N, RED_BLOCKS, st, 1, -std::log((double)N), d_lw, d_w, d_chunk, d_chunk2, hs, hs_dev, 1,
-                                 (flags & 1) ? 0 : 1, (flags & 2) ? 1 : 0, false, h, o);
-            if (!rc) {
-                if (hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    (h_log_w && hipMemcpyAsync(h_log_w, d_lw, (size_t)N * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-                    (h_weights && hipMemcpyAsync(h_weights, d_w, (size_t)N * 8, hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess) rc = FG_E_HIP;
-                else { *out_beta = h.beta; *out_log_norm = h.log_norm; if (out_need_sum) *out_need_sum = o.fused ? 0 : 1; }
-            }
-        }
+    SmcScope sc; double *d_ll = nullptr, *d_lw = nullptr, *d_w = nullptr, *d_chunk = nullptr, *d_chunk2 = nullptr; FgSmcScalars *st = nullptr; Reducer R;
+    FgSmcHostScalars *hs = nullptr, *hs_dev = nullptr;
+    FgSmcScalars h; std::memset(&h, 0, sizeof(h));
+    h.beta = beta; h.one = 1.0; h.target_ess = target_ess; h.beta2[0] = beta; h.beta2[1] = beta;
+    // (blocking uploads from the caller's pageable memory: complete before anything on the stream reads them)
+    if (sc.alloc(&d_ll, (size_t)N) || sc.alloc(&d_lw, (size_t)N) || sc.alloc(&d_w, (size_t)N) || sc.alloc(&d_chunk, (size_t)n_chunks) ||
+        sc.alloc(&d_chunk2, (size_t)n_chunks) || sc.alloc(&st, 1) || R.own(sc) ||
+        hipHostMalloc(&sc.pinned, sizeof(FgSmcHostScalars), hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&hs_dev, sc.pinned, 0) != hipSuccess || hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking) != hipSuccess ||
+        hipMemcpy(st, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_ll, h_ll, (size_t)N * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        fg_set_error("fg_device_smc_temper: allocation or upload failed");
+        return FG_E_HIP;
     }
-    if (rc == FG_E_HIP && !stepped) fg_set_error("fg_device_smc_temper: allocation or upload failed");
-    release();
-    return rc;
+    hs = (FgSmcHostScalars *)sc.pinned;
+    std::memset(hs, 0, sizeof(*hs));
+    hipStream_t s = sc.stream;
+    // the block maxima of ll for the first pass: fg_smc_run's source when no rejuvenation sweep left them
+    hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, (const double *)d_ll, (const double *)nullptr, N, (const double *)&st->one, (const double *)&st->one, R.part_max);
+    SmcStep o;
+    if ((rc = smc_temper_step(s, R, d_ll, N, RED_BLOCKS, st, 1, -std::log((double)N), d_lw, d_w, d_chunk, d_chunk2, hs, hs_dev, 1,
+                              (flags & 1) ? 0 : 1, (flags & 2) ? 1 : 0, false, h, o))) return rc;
+    if (hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (h_log_w && hipMemcpyAsync(h_log_w, d_lw, (size_t)N * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        (h_weights && hipMemcpyAsync(h_weights, d_w, (size_t)N * 8, hipMemcpyDeviceToHost, s) != hipSuccess) || hipStreamSynchronize(s) != hipSuccess) return FG_E_HIP;
+    *out_beta = h.beta; *out_log_norm = h.log_norm; if (out_need_sum) *out_need_sum = o.fused ? 0 : 1;
+    return FG_OK;
 }
 
 int fg_device_resample_indices(int device, int method, const double *h_weights, int64_t n, const double *h_u, int64_t *h_idx) {
     int rc = set_device_or_fail(device);
     if (rc) return rc;
     if (!h_weights || !h_u || !h_idx || n <= 0 || method < 0 || method > 2) return FG_E_BAD_ARG;
-    double *d_w = nullptr, *d_u = nullptr; long long *d_idx = nullptr; Scanner S;
+    SmcScope sc; double *d_w = nullptr, *d_u = nullptr; long long *d_idx = nullptr; Scanner S;
     const size_t nu = (method == FG_RESAMPLE_SYSTEMATIC) ? 1 : (size_t)n;
-    if (dev_alloc(&d_w, (size_t)n) || dev_alloc(&d_u, nu) || dev_alloc(&d_idx, (size_t)n)) return FG_E_HIP;
+    if (sc.alloc(&d_w, (size_t)n) || sc.alloc(&d_u, nu) || sc.alloc(&d_idx, (size_t)n) || S.own(sc, n)) return FG_E_HIP;
     HIPCHK(hipMemcpy(d_w, h_weights, (size_t)n * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_u, h_u, nu * 8, hipMemcpyHostToDevice));
-    rc = S.indices(nullptr, d_w, n, method, h_u[0], method == FG_RESAMPLE_SYSTEMATIC ? nullptr : d_u, 0, 0, d_idx);
-    if (!rc) { hipError_t e_ = hipMemcpy(h_idx, d_idx, (size_t)n * 8, hipMemcpyDeviceToHost); if (e_ != hipSuccess) rc = FG_E_HIP; }
-    (void)hipFree(d_w); (void)hipFree(d_u); (void)hipFree(d_idx); S.free_all();
-    return rc;
+    if ((rc = S.indices(nullptr, d_w, n, method, h_u[0], method == FG_RESAMPLE_SYSTEMATIC ? nullptr : d_u, 0, 0, d_idx))) return rc;
+    if (hipMemcpy(h_idx, d_idx, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return FG_E_HIP;
+    return FG_OK;
 }
 
-// ---- adaptive_smc (smc.rs:455-581) ----
+// ---- adaptive_smc (smc.rs:455-581): smc_run_steps; a failing step returns its code, and the stream is drained before the caller sees it ----
 int fg_smc_run(fg_engine *e, const fg_smc_config *cfg, double *h_log_w, double *h_weights, fg_smc_result *res, double *h_betas,
                int max_betas) {
     NEED_ENGINE(e);
     if (!cfg || !res) return FG_E_BAD_ARG;
     if (cfg->resampling_method < 0 || cfg->resampling_method > 2 || cfg->rejuvenation_steps < 0) { fg_set_error("bad SMC config"); return FG_E_BAD_ARG; }
-    const long long N = e->C;
-    const int S = e->S, TB = 256, NB = (int)((N + TB - 1) / TB);
-    hipStream_t s = e->stream;
-    SmcWs WS;
-    if (int rc0 = smc_workspace(e, WS)) return rc0;
-    const size_t Sn = (size_t)std::max(1, S);
-    auto cleanup = [&]() { (void)hipStreamSynchronize(s); };
-    FgSmcDev &M = WS.M; Reducer &R = WS.R; Scanner &SC = WS.SC;
-    FgSmcScalars *st = WS.st;
-    double *d_lw = WS.d_lw, *d_w = WS.d_w, *d_ll2 = WS.d_ll2, *d_lp2 = WS.d_lp2;
-    long long *d_vals2 = WS.d_vals2, *d_idx = WS.d_idx;
-    int rc = FG_OK;
-#define SMC_TRY(x) do { rc = (x); if (rc) { cleanup(); SC.free_all(); return rc; } } while (0)
-#define SMC_HIP(x) do { if ((x) != hipSuccess) { fg_set_error(#x); cleanup(); SC.free_all(); return FG_E_HIP; } } while (0)
-    if (!e->smc_host) SMC_HIP(hipHostMalloc(&e->smc_host, sizeof(FgSmcHostScalars), hipHostMallocMapped));
-    FgSmcHostScalars *hs = (FgSmcHostScalars *)e->smc_host, *hs_dev = nullptr;
-    SMC_HIP(hipHostGetDevicePointer((void **)&hs_dev, hs, 0));
-    std::memset(hs, 0, sizeof(*hs));
-    FgSmcScalars h; std::memset(&h, 0, sizeof(h));
-    h.one = 1.0; h.beta = 0.0;
-    h.target_ess = std::min(std::max(cfg->ess_threshold * (double)N, 1.0), (double)N);     // smc.rs:481
-    // the run's scalars, and scale = 1, log_scale = 0, acc = tot = 0 (DiminishingAdaptation::new): one launch
-    hipLaunchKernelGGL(k_smc_init, dim3((unsigned)((Sn + TB - 1) / TB)), dim3(TB), 0, s, st, h, M, (long long)Sn);
-    // smc_prior_particles (smc.rs:764-790): through the compiled model for a large population (the draw is a tenth of a 1 048 576-particle
-    // run on the interpreter kernel; the unit is compiled once per program and cached)
-    if (e->gt || N < (1LL << 18) || fg_jit_prior_launch(e, 0, FG_RNG_SMC_PRIOR, e->d_acc, nullptr, true) != FG_OK)
-        SMC_TRY(fg_launch_prior(e, 0, FG_RNG_SMC_PRIOR, e->d_acc, nullptr));
-    const double lw0 = -std::log((double)N);                                // log_w = -ln N at every step's start (smc.rs:476,538-540)
-    long long n_runs = N;
-    int n_steps = 0;
-    bool fin_ready = false;                                  // the last reweight left the sums of the final normalisation (k_smc_ess2_apply)
-    double log_evidence = 0.0; bool have_evidence = false, evidence_late = false;   // (late: the pinned copy is read behind the final synchronisation)
-    std::vector<double> betas;
-    if (cfg->rejuvenation_steps == 0) {                      // single importance-sampling reweight: smc.rs:484-493
-        hipLaunchKernelGGL(k_smc_split_acc, dim3(NB), dim3(TB), 0, s, (const double *)e->d_acc, M.lprior, M.ll, N);
-        hipLaunchKernelGGL(k_smc_is_weights, dim3(NB), dim3(TB), 0, s, d_lw, (const double *)M.ll, N);
-        SMC_TRY(R.run(s, d_lw, nullptr, N, st, (const double *)&st->one, 3));      // log_evidence = lse(combined)
-        betas.push_back(1.0); n_steps = 1;
-    } else {
-        // particle_log_likelihood (smc.rs:381-383) and the block maxima of ll for the first pass of next_beta
-        hipLaunchKernelGGL(k_smc_split_acc_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, (const double *)e->d_acc, M.lprior, M.ll, N, R.part_max);
-        int n_pmax = RED_BLOCKS;
-        const int n_chunks = (int)((N + SCAN_CHUNK - 1) / SCAN_CHUNK);
-        const int zoom = smc_zoom_default();
-        double beta = 0.0;
-        int steps = 0;
-        while (beta < 1.0) {                                 // smc.rs:501-560
-            steps += 1;
-            // next_beta: ESS at b = 1, then 64 bisections on the device (smc.rs:588-622)
-            if (steps >= 10000) { int one = 1; SMC_HIP(hipMemcpyAsync(&st->force_one, &one, sizeof(int), hipMemcpyHostToDevice, s)); }
-            e->smc_epoch = (e->smc_epoch + 1) & 0x0fffffff;
-            if (e->smc_epoch == 0) e->smc_epoch = 1;                // (0 is what an unwritten flag reads as)
-            SmcStep o;
-            SMC_TRY(smc_temper_step(s, R, M.ll, N, n_pmax, st, steps, lw0, d_lw, d_w, SC.chunk, WS.d_chunk2, hs, hs_dev, e->smc_epoch,
-                                    zoom, smc_force_sum_env(), steps < 10000, h, o));
-            const bool fused = o.fused;
-            beta = o.beta;
-            if (o.ends) { have_evidence = true; evidence_late = true; fin_ready = true; }
-            else if (fused) { log_evidence = o.log_evidence; have_evidence = true; fin_ready = beta >= 1.0; }
-            else { have_evidence = false; fin_ready = false; }
-            betas.push_back(beta); n_steps++;
-            if (beta < 1.0) {                                // resample + rejuvenate (smc.rs:534-559)
-                double U = 0.0;
-                if (cfg->resampling_method == FG_RESAMPLE_SYSTEMATIC) { FgStream rs = fg_stream(e->seed, 0, (uint32_t)steps, FG_RNG_SMC_RESAMPLE); U = fg_rng_u01(rs); }
-                if (fused) {                                 // the chunk totals are there: offsets + prefix sum in one launch, then the search
-                    hipLaunchKernelGGL(k_scan_cumsum_off, dim3((unsigned)n_chunks), dim3(SCAN_THREADS), 0, s, (const double *)d_w, N, (const double *)SC.chunk, n_chunks, SC.cum);
-                    SC.search(s, N, cfg->resampling_method, U, nullptr, (unsigned long long)e->seed, (uint32_t)steps, d_idx);
-                } else SMC_TRY(SC.indices(s, d_w, N, cfg->resampling_method, U, nullptr, e->seed, (uint32_t)steps, d_idx));
-                const int score = !e->P.sstream ? -1 : (e->P.sstream_kinds == 0 ? 0 : (e->P.sstream_gen ? 2 : 3));
-                // a batched sweep of a score-stream program reads the resampled population where k_smc_gather left it and writes every site
-                // back (no copy), scores every particle again (ll / log-prior need no gather) and leaves the block maxima of ll
-                const bool sweep_io = e->d > 0 && !cfg->sequential_adaptation;      // (every batched sweep kernel takes vsrc / pmax: k_smc_rejuv<...>, k_smc_jit_rejuv)
-                if (sweep_io)
-                    hipLaunchKernelGGL(k_smc_gather, dim3(NB), dim3(TB), 0, s, (const long long *)e->d_values, d_vals2, (const double *)nullptr, (double *)nullptr,
-                                       (const double *)nullptr, (double *)nullptr, (const long long *)d_idx, S, N);
-                else {
-                    hipLaunchKernelGGL(k_smc_gather, dim3(NB), dim3(TB), 0, s, (const long long *)e->d_values, d_vals2, (const double *)M.ll, d_ll2,
-                                       (const double *)M.lprior, d_lp2, (const long long *)d_idx, S, N);
-                    SMC_HIP(hipMemcpyAsync(e->d_values, d_vals2, (size_t)S * N * 8, hipMemcpyDeviceToDevice, s));
-                    SMC_HIP(hipMemcpyAsync(M.ll, d_ll2, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-                    SMC_HIP(hipMemcpyAsync(M.lprior, d_lp2, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-                }
-                bool have_pmax = false;
-                if (e->d > 0) {
-                    // tiles (waves) per block: as many as the kernel is built for and 150 KB of LDS hold; a tile beyond one CU's LDS (or more
-                    // sites than the block histogram has) lives in the engine's global scratch, one wave per block
-                    const bool big = e->lds_score > 150 * 1024 || S > FG_SMC_HIST;
-                    if (big) SMC_TRY(smc_global_tile(e));
-                    const int wpb = big ? 1 : (int)std::max<size_t>(1, std::min<size_t>((size_t)FG_SMC_WPB(score), (150 * 1024) / std::max<size_t>(1, e->lds_score)));
-                    const size_t lds_r = big ? 0 : e->lds_score * wpb;
-                    const unsigned nblk = (unsigned)((N + (long long)e->tw * wpb - 1) / ((long long)e->tw * wpb));
-                    if (cfg->sequential_adaptation) {               // the reference's order: one wave, particle by particle (k_smc_rejuv_seq)
-                        const uint32_t mv0 = (uint32_t)((steps - 1) * cfg->rejuvenation_steps);
-#define SMC_SEQ(SC_) do { if (big) hipLaunchKernelGGL((k_smc_rejuv_seq<SC_, true>), dim3(1), dim3(FG_WAVE), 0, s, e->P, e->X, M, (const FgSmcScalars *)st, mv0, cfg->rejuvenation_steps); \
-                          else { SMC_TRY(set_lds(k_smc_rejuv_seq<SC_>, std::max<size_t>(e->lds_score, 64 * 1024 + 1))); \
-                                 hipLaunchKernelGGL(k_smc_rejuv_seq<SC_>, dim3(1), dim3(FG_WAVE), e->lds_score, s, e->P, e->X, M, (const FgSmcScalars *)st, mv0, cfg->rejuvenation_steps); } } while (0)
-                        if (score == 0) SMC_SEQ(0); else if (score == 3) SMC_SEQ(3); else if (score == 2) SMC_SEQ(2); else SMC_SEQ(-1);
-#undef SMC_SEQ
-                        n_runs += 2 * N * cfg->rejuvenation_steps;
-                    } else
-                    for (int r = 0; r < cfg->rejuvenation_steps; ++r) {
-                        const uint32_t mv = (uint32_t)((steps - 1) * cfg->rejuvenation_steps + r);
-                        const long long *vsrc = (sweep_io && r == 0) ? (const long long *)d_vals2 : (const long long *)nullptr;
-                        double *pmax = (sweep_io && r == cfg->rejuvenation_steps - 1) ? R.part_max : (double *)nullptr;
-#define SMC_REJUV(SC_) do { if (big) hipLaunchKernelGGL((k_smc_rejuv<SC_, true>), dim3(nblk), dim3(FG_WAVE), 0, s, e->P, e->X, M, (const FgSmcScalars *)st, mv, vsrc, pmax); \
-                            else { SMC_TRY(set_lds(k_smc_rejuv<SC_>, std::max<size_t>(lds_r, 64 * 1024 + 1))); \
-                                   hipLaunchKernelGGL(k_smc_rejuv<SC_>, dim3(nblk), dim3(e->tw * wpb), lds_r, s, e->P, e->X, M, (const FgSmcScalars *)st, mv, vsrc, pmax); } } while (0)
-                        unsigned nb_adapt = nblk;
-                        // the compiled model where there is one: programs without a score stream, and stream programs with general / option-select /
-                        // Categorical records (hier_scale 3.2 -> 2.3 ms per 262 144-particle run, mixture 3.4 -> 2.4); fast-Normal streams keep k_smc_rejuv<0>
-                        // (... and k_smc_rejuv<0> too once the unit exists -- a large population had it built for its prior draw --: 28.6 -> 24.7 us per sweep
-                        // of 1 048 576 particles)
-                        if ((score != 0 || (e->jit_state == 1 && N >= (1LL << 18))) && !big &&
-                            fg_smc_jit_rejuv_launch(e, M, (const FgSmcScalars *)st, mv, &nb_adapt, vsrc, pmax) == FG_OK) { }
-                        else if (score == 0) SMC_REJUV(0); else if (score == 3) SMC_REJUV(3); else if (score == 2) SMC_REJUV(2);
-                        else SMC_REJUV(-1);
-#undef SMC_REJUV
-                        if (pmax) { have_pmax = true; n_pmax = (int)nb_adapt; }
-                        hipLaunchKernelGGL(k_smc_adapt, dim3((unsigned)S), dim3(256), 0, s, M, S, (int)nb_adapt);
-                        n_runs += 2 * N;
-                    }
-                }
-                if (!have_pmax) {                            // the block maxima of ll for the next step's first pass
-                    hipLaunchKernelGGL(k_smc_red_max, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, (const double *)M.ll, (const double *)nullptr, N, (const double *)&st->one, (const double *)&st->one, R.part_max);
-                    n_pmax = RED_BLOCKS;
-                }
-                SMC_HIP(hipGetLastError());
-            }
-        }
-    }
-    // attach the final normalised weights (smc.rs:565-575)
-    if (fin_ready) hipLaunchKernelGGL(k_smc_final_norm, dim3((unsigned)std::min<long long>(1024, (N + 4 * SCAN_THREADS - 1) / (4 * SCAN_THREADS))), dim3(SCAN_THREADS), 0, s, d_lw, d_w, N, (const double *)WS.d_chunk2, st);
-    else {
-        SMC_TRY(R.run(s, d_lw, nullptr, N, st, (const double *)&st->one, 4));
-        hipLaunchKernelGGL(k_smc_normalize, dim3(NB), dim3(TB), 0, s, d_lw, d_w, N, (const FgSmcScalars *)st);
-    }
-    if (!have_evidence) SMC_HIP(hipMemcpyAsync(&h, st, sizeof(h), hipMemcpyDeviceToHost, s));
-    if (h_log_w) SMC_HIP(hipMemcpyAsync(h_log_w, d_lw, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    if (h_weights) SMC_HIP(hipMemcpyAsync(h_weights, d_w, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    SMC_HIP(hipGetLastError());
-    SMC_HIP(hipStreamSynchronize(s));
-    if (have_evidence) h.log_evidence = evidence_late ? hs->log_evidence : log_evidence;
-    e->smc_pop_ready = true;
-    res->log_evidence = h.log_evidence; res->n_steps = n_steps; res->n_model_runs = n_runs;
-    if (h_betas) for (int i = 0; i < (int)betas.size() && i < max_betas; ++i) h_betas[i] = betas[i];
-    cleanup();
-    SC.free_all();
-    return FG_OK;
-#undef SMC_TRY
-#undef SMC_HIP
+    SmcRun r{};
+    r.e = e; r.cfg = cfg; r.N = e->C; r.NB = (int)((e->C + SMC_TB - 1) / SMC_TB); r.s = e->stream;
+    const int rc = smc_run_steps(r, h_log_w, h_weights, res, h_betas, max_betas);
+    if (rc) (void)hipStreamSynchronize(e->stream);
+    return rc;
 }
 
 
@@ -1826,16 +1748,11 @@ int fg_smc_resample(fg_engine *e, int method, uint32_t step, int64_t *h_indices)
     SmcWs W;
     if (int rc = smc_pop(e, W, true)) return rc;
     const long long N = e->C;
-    const int S = e->S, TB = 256, NB = (int)((N + TB - 1) / TB);
+    const int TB = 256, NB = (int)((N + TB - 1) / TB);
     hipStream_t s = e->stream;
-    double U = 0.0;
-    if (method == FG_RESAMPLE_SYSTEMATIC) { FgStream rs = fg_stream(e->seed, 0, step, FG_RNG_SMC_RESAMPLE); U = fg_rng_u01(rs); }
+    const double U = method == FG_RESAMPLE_SYSTEMATIC ? smc_systematic_u(e, step) : 0.0;
     if (int rc = W.SC.indices(s, W.d_w, N, method, U, nullptr, e->seed, step, W.d_idx)) return rc;
-    hipLaunchKernelGGL(k_smc_gather, dim3(NB), dim3(TB), 0, s, (const long long *)e->d_values, W.d_vals2, (const double *)W.M.ll, W.d_ll2,
-                       (const double *)W.M.lprior, W.d_lp2, (const long long *)W.d_idx, S, N);
-    HIPCHK(hipMemcpyAsync(e->d_values, W.d_vals2, (size_t)S * N * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(W.M.ll, W.d_ll2, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(W.M.lprior, W.d_lp2, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+    if (int rc = smc_commit_resampled(e, W)) return rc;
     const double uw = 1.0 / (double)N;
     hipLaunchKernelGGL(k_fill, dim3(NB), dim3(TB), 0, s, W.d_w, N, uw);
     hipLaunchKernelGGL(k_fill, dim3(NB), dim3(TB), 0, s, W.d_lw, N, std::log(uw));
@@ -1845,38 +1762,26 @@ int fg_smc_resample(fg_engine *e, int method, uint32_t step, int64_t *h_indices)
     return FG_OK;
 }
 // rejuvenate_particles (smc.rs:698-713): `steps` pi_beta-invariant single-site MH moves per particle with a fresh
-// DiminishingAdaptation (batched per sweep, as in fg_smc_run); weights are NOT touched (FG-13).
+// DiminishingAdaptation (fg_smc_run's batched sweeps: smc_rejuv_sweep); weights are NOT touched (FG-13).
 int fg_smc_rejuvenate(fg_engine *e, double beta, int steps, uint32_t first_move_id, double *h_accept_rate) {
     NEED_ENGINE(e);
     if (steps < 0) return FG_E_BAD_ARG;
     SmcWs W;
     if (int rc = smc_pop(e, W, true)) return rc;
-    const long long N = e->C;
-    const int S = e->S, TB = 256;
-    const size_t Sn = (size_t)std::max(1, S);
+    const int TB = 256;
+    const size_t Sn = (size_t)std::max(1, e->S);
     hipStream_t s = e->stream;
     if (e->d == 0 || steps == 0) { if (h_accept_rate) *h_accept_rate = 0.0; return FG_OK; }
+    FgSmcRejuvPlan pl;
+    if (int rc = smc_rejuv_plan_for(e, false, false, &pl)) return rc;
     FgSmcScalars h; std::memset(&h, 0, sizeof(h)); h.one = 1.0; h.beta = beta;
     HIPCHK(hipMemcpyAsync(W.st, &h, sizeof(h), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(W.base + W.o_ls, 0, W.o_st - W.o_ls, s));            // log_scale, acc, tot = 0; scale = 1
+    HIPCHK(hipMemsetAsync(W.adapt_reset, 0, W.adapt_reset_bytes, s));          // log_scale, acc, tot = 0; scale = 1
     hipLaunchKernelGGL(k_fill, dim3((unsigned)((Sn + TB - 1) / TB)), dim3(TB), 0, s, W.M.scale, (long long)Sn, 1.0);
-    const int score = !e->P.sstream ? -1 : (e->P.sstream_kinds == 0 ? 0 : (e->P.sstream_gen ? 2 : 3));
-    const bool big = e->lds_score > 150 * 1024 || S > FG_SMC_HIST;            // (as in fg_smc_run)
-    if (big) { if (int rc_ = smc_global_tile(e)) return rc_; }
-    const int wpb = big ? 1 : (int)std::max<size_t>(1, std::min<size_t>((size_t)FG_SMC_WPB(score), (150 * 1024) / std::max<size_t>(1, e->lds_score)));
-    const size_t lds_r = big ? 0 : e->lds_score * wpb;
-    const unsigned nblk = (unsigned)((N + (long long)e->tw * wpb - 1) / ((long long)e->tw * wpb));
+    if (pl.global_tile) { if (int rc = smc_global_tile(e)) return rc; }
     for (int r = 0; r < steps; ++r) {
-        const uint32_t mv = first_move_id + (uint32_t)r;
-#define SMC_REJUV(SC_) do { if (big) hipLaunchKernelGGL((k_smc_rejuv<SC_, true>), dim3(nblk), dim3(FG_WAVE), 0, s, e->P, e->X, W.M, (const FgSmcScalars *)W.st, mv, (const long long *)nullptr, (double *)nullptr); \
-                            else { if (int rc_ = set_lds(k_smc_rejuv<SC_>, std::max<size_t>(lds_r, 64 * 1024 + 1))) return rc_; \
-                                   hipLaunchKernelGGL(k_smc_rejuv<SC_>, dim3(nblk), dim3(e->tw * wpb), lds_r, s, e->P, e->X, W.M, (const FgSmcScalars *)W.st, mv, (const long long *)nullptr, (double *)nullptr); } } while (0)
-        unsigned nb_adapt = nblk;
-        if (score != 0 && !big && fg_smc_jit_rejuv_launch(e, W.M, (const FgSmcScalars *)W.st, mv, &nb_adapt) == FG_OK) { }      // (as in fg_smc_run)
-        else if (score == 0) SMC_REJUV(0); else if (score == 3) SMC_REJUV(3); else if (score == 2) SMC_REJUV(2);
-        else SMC_REJUV(-1);
-#undef SMC_REJUV
-        hipLaunchKernelGGL(k_smc_adapt, dim3((unsigned)S), dim3(256), 0, s, W.M, S, (int)nb_adapt);
+        unsigned n_blk = 0;
+        if (int rc = smc_rejuv_sweep(e, W.M, W.st, pl, first_move_id + (uint32_t)r, nullptr, nullptr, &n_blk)) return rc;
     }
     HIPCHK(hipGetLastError());
     if (h_accept_rate) {

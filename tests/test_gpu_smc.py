@@ -201,6 +201,31 @@ def test_standalone_smc_building_blocks(oracle):
     assert abs(mu2.mean() - 1.2) < 0.05 and abs(mu2.var() - 0.2) < 0.05
 
 
+@pytest.mark.parametrize("model,n", [("normal_sites400", 128), ("mixture", 3000)])
+def test_standalone_rejuvenate_takes_the_runs_sweep(model, n, monkeypatch):
+    """smc_prior_particles -> smc_resample -> smc_rejuvenate(beta, 2) launches its sweeps through fg_smc_run's launcher (smc_rejuv_sweep):
+    on a program beyond the block histogram (400 sites: the tile in global memory, one wave per block, whatever FG_JIT says) and on a
+    stream program with Categorical records (the compiled sweep under FG_JIT=1, k_smc_rejuv<3> under FG_JIT=0).  Which kernel runs does
+    not change a result: particles, weights and accept rate are the same under both settings, bit for bit."""
+    from tests.models import ZOO
+    cp = E.compile_model(W.normal_sites(400) if model == "normal_sites400" else ZOO[model]())
+    out = []
+    for jit in ("0", "1"):
+        monkeypatch.setenv("FG_JIT", jit)
+        eng = E.Engine(cp, n, seed=23)
+        eng.smc_prior_particles()
+        idx = eng.smc_resample(E.RESAMPLE_SYSTEMATIC, step=1)
+        before = eng.get_values().copy()
+        acc = eng.smc_rejuvenate(0.37, 2)
+        lw, w = eng.smc_weights()
+        out.append((idx, eng.get_values(), lw, w, np.float64(acc)))
+        eng.close()
+        assert 0.0 < acc < 1.0 and (out[-1][1] != before).any()                   # the sweeps ran and moved particles
+        assert np.array_equal(w, np.full(n, 1.0 / n))                             # ... and left the weights alone (FG-13)
+    for a, b in zip(out[0], out[1]):
+        assert np.array_equal(a, b, equal_nan=True)
+
+
 def test_next_beta_zoom_passes_agree_with_the_plain_passes():
     """next_beta brackets the ESS crossing by zoom passes and replays the reference's 64 halvings from the bracket (DESIGN 3.4, round 4);
     FG_SMC_ZOOM=0 evaluates every halving (three levels per pass).  Both follow the same comparisons `ESS(mid) < target` wherever the
