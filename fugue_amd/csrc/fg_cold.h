@@ -11,6 +11,30 @@
 struct FgD2 { double a, b; };
 
 // p0 pair j of a chain's (iteration) stream: fg_rng_normal_pair at block j (hmc.rs:436-441)
+#ifdef FG_COLD_UKEY
+// A unit that defines FG_COLD_UKEY before this header (fg_hmc_sep.hip, fg_hmc_lin.hip: the kernels these two functions are a fifth of)
+// promises that (k0, k1) are the two halves of the engine's seed in every call -- wave-uniform, see fg_philox4x32_10_ukey -- and gets the
+// scalar key schedule, the polynomial coefficients of log and sincos from SGPRs (fg_sk) and fg_sqrt_pos.  The same words and the same
+// roundings as fg_rng_normal_pair on the stream (k0, k1, chain, block, iter, purpose).  Every other unit, the run-time compiled ones
+// included, compiles the generic forms below: the MH and SMC legs of the benchmark measured no gain from the short forms and one of
+// them a loss (profiles/round9_momentum_draw_ab.txt).
+static __device__ __noinline__ FgD2 fg_cold_normal_pair(uint32_t k0, uint32_t k1, uint32_t chain, uint32_t block, uint32_t iter, uint32_t purpose) {
+    uint32_t o[4];
+    fg_philox4x32_10_ukey(chain, block, iter, purpose, k0, k1, o);
+    FgD2 r;
+    fg_normal_pair_of<true>((unsigned long long)o[0] | ((unsigned long long)o[1] << 32), (unsigned long long)o[2] | ((unsigned long long)o[3] << 32), r.a, r.b);
+    return r;
+}
+// two uniforms of one Philox block (a: the accept uniform of hmc.rs:461 / mh.rs:733)
+static __device__ __noinline__ FgD2 fg_cold_u01_pair(uint32_t k0, uint32_t k1, uint32_t chain, uint32_t block, uint32_t iter, uint32_t purpose) {
+    uint32_t o[4];
+    fg_philox4x32_10_ukey(chain, block, iter, purpose, k0, k1, o);
+    FgD2 r;
+    r.a = fg_u01_of((unsigned long long)o[0] | ((unsigned long long)o[1] << 32));
+    r.b = fg_u01_of((unsigned long long)o[2] | ((unsigned long long)o[3] << 32));
+    return r;
+}
+#else
 static __device__ __noinline__ FgD2 fg_cold_normal_pair(uint32_t k0, uint32_t k1, uint32_t chain, uint32_t block, uint32_t iter, uint32_t purpose) {
     FgStream s; s.k0 = k0; s.k1 = k1; s.c0 = chain; s.c1 = block; s.c2 = iter; s.c3 = purpose;
     FgD2 r;
@@ -25,6 +49,7 @@ static __device__ __noinline__ FgD2 fg_cold_u01_pair(uint32_t k0, uint32_t k1, u
     FgD2 r; r.a = fg_u01_of(a); r.b = fg_u01_of(b);
     return r;
 }
+#endif
 // min(1, exp(h0 - h1)): hmc.rs:460
 static __device__ __noinline__ double fg_cold_accept_prob(double h0, double h_new) { return fmin(exp(h0 - h_new), 1.0); }
 static __device__ __noinline__ double fg_cold_exp(double x) { return exp(x); }

@@ -26,6 +26,7 @@
 // averaging; commit / roll back by the owning wave.
 #include "fg_engine_internal.h"
 #include "fg_gradstream.h"
+#define FG_COLD_UKEY 1        /* every fg_cold_normal_pair / fg_cold_u01_pair call of this unit passes the halves of X.seed: scalar Philox keys */
 #include "fg_cold.h"
 
 #define FG_LIN_WMAX 16

@@ -17,6 +17,7 @@
 // the arithmetic -- then accept and dual averaging (cold code, out of line) | barrier | commit / roll back the own coordinates.
 #include "fg_engine_internal.h"
 #include "fg_gradstream.h"
+#define FG_COLD_UKEY 1        /* every fg_cold_normal_pair / fg_cold_u01_pair call of this unit passes the halves of X.seed: scalar Philox keys */
 #include "fg_cold.h"
 #include "fg_hmc_sep_plan.h"
 
@@ -57,10 +58,12 @@ __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const char *p) { return *(const f
     double outp, outm;                                                                                 \
     { const double c = fg_dbl(a##k[2], a##k[3]); const double zp = FG_SEP_Z(k, qp - c), zm = FG_SEP_Z(k, qm - c); \
       outp = FG_SEP_LP(k, zp); outm = FG_SEP_LP(k, zm); }
-// record k at q (endpoint score term; NaN z -> -inf like FG_OP_NORMAL_FAST)
+// record k at q (endpoint score term; NaN z -> -inf like FG_OP_NORMAL_FAST).  The replacement sits behind a wave-uniform test, as in
+// FG_DENSE_LP: a wave with no NaN z (every wave of a run that does not diverge) issues a compare and a scalar branch, not two selects
+#define FG_SEP_NAN_NEG_INF(z, lp) { if (__builtin_expect(__any((z) != (z)), 0)) lp = ((z) != (z)) ? FG_NEG_INF : lp; }
 #define FG_SEP_TERM_TO(k, dst)                                                                         \
-    { const double z = FG_SEP_Z(k, q - fg_dbl(a##k[2], a##k[3])); const double lp = FG_SEP_LP(k, z); \
-      (dst)[a##k[1] * tw] = (z != z) ? FG_NEG_INF : lp; }
+    { const double z = FG_SEP_Z(k, q - fg_dbl(a##k[2], a##k[3])); double lp = FG_SEP_LP(k, z);       \
+      FG_SEP_NAN_NEG_INF(z, lp) (dst)[a##k[1] * tw] = lp; }
 #define FG_SEP_TERM(k) FG_SEP_TERM_TO(k, terms)
 // record 0 when the coordinate's own sample statement is Normal(0, 1) (U0): q - 0, * 1 and - ln 1 change no bit of any double
 // (x - 0.0 = x, x * 1.0 = x for every x incl. -0.0, inf, NaN), so they are not issued: 6 of the 42 instructions of a coordinate-step
@@ -202,7 +205,7 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         if (gs < L) { asm volatile(""); q = q + emi * p; }       // hmc.rs:391-393
     }
     if (!CHECK && FOLD && nrange >= 0xde000000u) p = __builtin_nan("");   // some quotient out of fg_div_const's range: the checked re-run
-    if (U0) { const double lp = FG_SEP_LP_U(q); terms[a0[1] * tw] = (q != q) ? FG_NEG_INF : lp; }
+    if (U0) { double lp = FG_SEP_LP_U(q); FG_SEP_NAN_NEG_INF(q, lp) terms[a0[1] * tw] = lp; }
     else FG_SEP_TERM(0)
     if (FG_SEP_HAS(1)) FG_SEP_TERM(1)
     if (FG_SEP_HAS(2)) FG_SEP_TERM(2)
@@ -755,14 +758,19 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         FG_PROF_T(3)
         const bool acc = xch[tw] != 0.0;
         unsigned long long wn = 0;
-        if (warming && welford_on) wn = H.w_n[c] + 1ull;          // every wave reads the old count before wave 0 bumps it below
+        double wnd = 0.0;                                         // (double)wn, Welford::push's divisor
+        if (warming && welford_on) {                              // every wave reads the old count before wave 0 bumps it below
+            wn = H.w_n[c] + 1ull;
+            wnd = (double)wn;
+            asm volatile("" : "+v"(wnd));                         // load and conversion stay behind the uniform branch: the sampling phase issues neither
+        }
         // the committed value x of coordinate i: draws, positions, Welford (cc: the lane's chain)
         auto commit = [&](int i, double x, bool on, long long cc) {
             if (live && on && pos_all) pos_all[((long long)t * d + i) * X.C + cc] = x;
             if (warming) {
                 if (welford_on) {                                 // Welford::push: hmc.rs:202-211
                     const long long gi = (long long)i * X.C + cc;
-                    const double n = (double)wn;
+                    const double n = wnd;
                     double mean = H.w_mean[gi];
                     const double delta = x - mean;
                     mean += delta / n;

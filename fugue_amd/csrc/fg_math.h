@@ -308,6 +308,40 @@ FG_HD void fg_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, 
     }
     o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
 }
+// The same ten rounds for a WAVE-UNIFORM key (device form; the host build is the generic arithmetic).  Both key words go through
+// v_readfirstlane, so the key schedule is 18 scalar additions instead of 18 v_add_u32, and each round's h ^ c ^ k is ONE three-input
+// bit operation (v_bitop3_b32, truth table 0x96 = a ^ b ^ c) with the round key as its scalar operand instead of two v_xor_b32.
+// Only the key is made scalar: the four counter words stay per-lane operands (chain differs per lane, block between the lane halves of
+// half and quarter tiles).  The form is taken by fg_cold_normal_pair / fg_cold_u01_pair in the units that ask for it (FG_COLD_UKEY:
+// fg_hmc_sep.hip, fg_hmc_lin.hip).  Every call of the two wrappers there -- and in every other unit of the library: the HMC kernels of
+// fg_engine / fg_hmc_interp / fg_hmc_jit_body, the MH kernels of fg_engine / fg_mh_interp_body / fg_mh_mw_body / fg_mh_mw2_body, the
+// rejuvenation kernels of fg_smc / fg_hmc_jit_body -- passes the two halves of X.seed, the engine's seed in the kernel-argument struct
+// FgChainCtx: the same value in every lane, so the first active lane's copy is every lane's.
+FG_HD uint32_t fg_xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96u);
+#else
+    return a ^ b ^ c;
+#endif
+#else
+    return a ^ b ^ c;
+#endif
+}
+FG_HD void fg_philox4x32_10_ukey(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t *o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k0); k1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k1);
+#endif
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
+        const uint32_t n0 = fg_xor3(h1, c1, k0), n2 = fg_xor3(h0, c3, k1);
+        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
 FG_HD FgStream fg_stream(unsigned long long seed, uint32_t chain, uint32_t iter, uint32_t purpose) {
     FgStream s; s.k0 = (uint32_t)seed; s.k1 = (uint32_t)(seed >> 32); s.c0 = chain; s.c1 = 0; s.c2 = iter; s.c3 = purpose;
     return s;
@@ -330,7 +364,18 @@ FG_HD double fg_rng_u01(FgStream &s) { unsigned long long a, b; fg_rng_block(s, 
 // values are pinned by no reference test (rand_distr's ziggurat is not reproduced); the oracle computes the same
 // expressions with glibc and the parity tests compare with tolerances far above an ulp.  tests/cpp/test_fast_math.cpp checks
 // both against libm on the host build.
-FG_HD double fg_fast_log(double x) {            // x > 0, normal
+// SK (device build; nothing on the host): every polynomial coefficient is pinned to an SGPR pair, with the empty-asm idiom of
+// fg_sep_trajectory.  A Horner step's addend is then the scalar operand of a v_fma_f64 (one per VALU instruction, no VALU slot for the
+// s_mov) instead of a v_mov_b32 pair into the destination of a v_fmac_f64.  The expressions, hence the roundings, are the same.  The
+// pinned form is taken by fg_cold_normal_pair under FG_COLD_UKEY only, which is out of line and has its own register allocation:
+// inlined callers (the MH kernels) keep the compiler's choice and their SGPR budgets.
+template <bool SK> FG_HD double fg_sk(double c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (SK) asm("" : "+s"(c));
+#endif
+    return c;
+}
+template <bool SK> FG_HD double fg_fast_log_t(double x) {            // x > 0, normal
     const long long bx = fg_as_i64(x);
     int hx = (int)(bx >> 32);
     int k = (hx >> 20) - 1023;
@@ -349,43 +394,72 @@ FG_HD double fg_fast_log(double x) {            // x > 0, normal
     double sq = f * y;
     sq = __builtin_fma(__builtin_fma(-sq, d, f), y, sq);             // f / (2 + f)
     const double z = sq * sq, w = z * z;
-    const double t1 = w * __builtin_fma(w, __builtin_fma(w, 1.531383769920937332e-01, 2.222219843214978396e-01), 3.999999999940941908e-01);
-    const double t2 = z * __builtin_fma(w, __builtin_fma(w, __builtin_fma(w, 1.479819860511658591e-01, 1.818357216161805012e-01), 2.857142874366239149e-01),
-                                        6.666666666666735130e-01);
+#define FG_K(c) fg_sk<SK>(c)
+    const double t1 = w * __builtin_fma(w, __builtin_fma(w, FG_K(1.531383769920937332e-01), FG_K(2.222219843214978396e-01)), FG_K(3.999999999940941908e-01));
+    const double t2 = z * __builtin_fma(w, __builtin_fma(w, __builtin_fma(w, FG_K(1.479819860511658591e-01), FG_K(1.818357216161805012e-01)), FG_K(2.857142874366239149e-01)),
+                                        FG_K(6.666666666666735130e-01));
     const double R = t2 + t1, hfsq = 0.5 * f * f;
-    return dk * 6.93147180369123816490e-01 - ((hfsq - __builtin_fma(sq, hfsq + R, dk * 1.90821492927058770002e-10)) - f);
+    return dk * FG_K(6.93147180369123816490e-01) - ((hfsq - __builtin_fma(sq, hfsq + R, dk * FG_K(1.90821492927058770002e-10))) - f);
 }
-FG_HD void fg_fast_sincos(double x, double &sn, double &cs) {   // 0 <= x < 2 pi (any |x| < ~1e5 reduces accurately)
-    const double fn = __builtin_rint(x * 6.36619772367581382433e-01);
-    const double r = __builtin_fma(-fn, 1.57079632673412561417e+00, x);   // 33-bit head of pi / 2: the product is exact
-    const double w = fn * 6.07710050650619224932e-11;
+FG_HD double fg_fast_log(double x) { return fg_fast_log_t<false>(x); }
+template <bool SK> FG_HD void fg_fast_sincos_t(double x, double &sn, double &cs) {   // 0 <= x < 2 pi (any |x| < ~1e5 reduces accurately)
+    const double fn = __builtin_rint(x * FG_K(6.36619772367581382433e-01));
+    const double r = __builtin_fma(-fn, FG_K(1.57079632673412561417e+00), x);   // 33-bit head of pi / 2: the product is exact
+    const double w = fn * FG_K(6.07710050650619224932e-11);
     const double y0 = r - w, y1 = (r - y0) - w;
     const double z = y0 * y0;
     // k_sin
     const double v = z * y0;
-    const double rs = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08), 2.75573137070700676789e-06),
-                                                     -1.98412698298579493134e-04), 8.33333333332248946124e-03);
-    const double s0 = y0 - ((z * (0.5 * y1 - v * rs) - y1) - v * -1.66666666666666324348e-01);
+    const double rs = __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, __builtin_fma(z, FG_K(1.58969099521155010221e-10), FG_K(-2.50507602534068634195e-08)), FG_K(2.75573137070700676789e-06)),
+                                                     FG_K(-1.98412698298579493134e-04)), FG_K(8.33333333332248946124e-03));
+    const double s0 = y0 - ((z * (0.5 * y1 - v * rs) - y1) - v * FG_K(-1.66666666666666324348e-01));
     // k_cos
     const double w2 = z * z;
-    const double rc = z * __builtin_fma(z, __builtin_fma(z, 2.48015872894767294178e-05, -1.38888888888741095749e-03), 4.16666666666666019037e-02) +
-                      (w2 * w2) * __builtin_fma(z, __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09), -2.75573143513906633035e-07);
+    const double rc = z * __builtin_fma(z, __builtin_fma(z, FG_K(2.48015872894767294178e-05), FG_K(-1.38888888888741095749e-03)), FG_K(4.16666666666666019037e-02)) +
+                      (w2 * w2) * __builtin_fma(z, __builtin_fma(z, FG_K(-1.13596475577881948265e-11), FG_K(2.08757232129817482790e-09)), FG_K(-2.75573143513906633035e-07));
     const double hz = 0.5 * z, wc = 1.0 - hz;
     const double c0 = wc + (((1.0 - wc) - hz) + (z * rc - y0 * y1));
     const int n = (int)fn;
     const double sa = (n & 1) ? c0 : s0, ca = (n & 1) ? s0 : c0;
     sn = (n & 2) ? -sa : sa;
     cs = ((n + 1) & 2) ? -ca : ca;
+#undef FG_K
 }
-FG_HD void fg_rng_normal_pair(FgStream &s, double &z0, double &z1) {   // Box-Muller, u1 in (0,1]
-    unsigned long long a, b; fg_rng_block(s, a, b);
+FG_HD void fg_fast_sincos(double x, double &sn, double &cs) { fg_fast_sincos_t<false>(x, sn, cs); }
+// sqrt for the argument of the normal generators, -2 ln u in {-0} u [2.2e-16, 73.5].  Device: the correctly rounded sequence ocml's sqrt
+// runs (v_rsq_f64, g = x y, h = y / 2, one coupled refinement, two residual corrections; +-0 and +inf returned as they are) WITHOUT its
+// range scaling -- a compare, a select and two v_ldexp_f64 that multiply arguments below 2^-767 by 2^256 and the root by 2^-128.  Above
+// 2^-767 the scale factor is 1 and the two ldexp change nothing, so this is sqrt bit for bit there (tests/test_gpu_rng_identity.py);
+// below it the result may be inexact -- no caller gets there.  Host: sqrt.  Taken by the pinned pair (fg_normal_pair_of<true>) only.
+FG_HD double fg_sqrt_pos(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = 0.5 * y;
+    const double r = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, r, g); h = __builtin_fma(h, r, h);
+    double d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    d = __builtin_fma(-g, g, x);
+    g = __builtin_fma(d, h, g);
+    return __builtin_amdgcn_class(x, 0x260) ? x : g;     // -0 | +0 | +inf
+#else
+    return sqrt(x);
+#endif
+}
+// Box-Muller from the two words of a Philox block, u1 in (0,1]
+template <bool SK> FG_HD void fg_normal_pair_of(unsigned long long a, unsigned long long b, double &z0, double &z1) {
     double u1 = ((double)(a >> 11) + 1.0) * 0x1.0p-53;
     double u2 = fg_u01_of(b);
-    double r = sqrt(-2.0 * fg_fast_log(u1));
+    const double x = -2.0 * fg_fast_log_t<SK>(u1);
+    double r = SK ? fg_sqrt_pos(x) : sqrt(x);
     double th = 2.0 * M_PI * u2;
     double sn, cs;
-    fg_fast_sincos(th, sn, cs);
+    fg_fast_sincos_t<SK>(th, sn, cs);
     z0 = r * cs; z1 = r * sn;
+}
+FG_HD void fg_rng_normal_pair(FgStream &s, double &z0, double &z1) {
+    unsigned long long a, b; fg_rng_block(s, a, b);
+    fg_normal_pair_of<false>(a, b, z0, z1);
 }
 FG_HD double fg_rng_normal(FgStream &s) { double a, b; fg_rng_normal_pair(s, a, b); return a; }
 // gaussian_z: /root/reference/src/inference/mh.rs:128-132
