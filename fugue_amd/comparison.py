@@ -1,0 +1,140 @@
+"""Model comparison from the pointwise log-likelihood: WAIC and importance-sampling LOO per observe statement (BDA3 7.2; the
+reference has neither), computed on the device by the log-likelihood stream (`Engine.loglik_stream`, fg_loglik_stream.hip).
+
+The drivers `hmc_chain_summary(pointwise=...)` / `adaptive_mcmc_chain_summary(pointwise=...)` feed the stream chunk by chunk and never
+hold the table (`ChainSummary.comparison`); `model_comparison` takes a stored table ([n][n_sel][C], or a `ChainBatch` of
+`hmc_chain(pointwise=True)`) and feeds it as one chunk -- the same figures bit for bit, since the stream does not depend on the
+chunking.
+
+`p_waic` is the UNBIASED variance of the pointwise log-likelihood over the N = n_draws x n_chains pooled draws (divisor N - 1: BDA3
+eq. 7.12 and the R `loo` package; ArviZ divides by N).  `elpd_loo` is plain importance-sampling LOO with the raw ratios
+r = exp(-log-likelihood): no Pareto smoothing, no k-hat.  `is_ess` = (sum r)^2 / sum r^2 and `max_weight` = max r / sum r are the
+honest diagnostic of those raw ratios: an `is_ess` of a few, or a `max_weight` near 1, says the estimate of that statement rests on
+a handful of draws."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import engine as E
+from . import workloads as W
+
+POINTWISE = ("lppd", "mean_ll", "p_waic", "elpd_waic", "elpd_loo", "p_loo", "is_ess", "max_weight")
+
+
+def _total(a: np.ndarray) -> float:
+    t = 0.0
+    for v in np.asarray(a, dtype=np.float64).tolist():      # a plain sum in index order
+        t += v
+    return t
+
+
+@dataclass
+class PointwiseComparison:
+    """Per selected observe statement (`names`, [n_sel] each) over `n_draws` = N pooled draws: `lppd` = ln((1/N) sum exp x),
+    `mean_ll`, `p_waic` (variance, divisor N - 1), `elpd_waic` = lppd - p_waic, `elpd_loo` = -ln((1/N) sum exp(-x)), `p_loo` = lppd -
+    elpd_loo, `is_ess`, `max_weight`, and the counts of cells that are -inf / +inf / NaN.  A NaN cell makes every figure of its
+    statement NaN; a -inf cell makes elpd_loo -inf; a +inf cell makes lppd +inf."""
+    names: List[str]
+    n_draws: int
+    lppd: np.ndarray
+    mean_ll: np.ndarray
+    p_waic: np.ndarray
+    elpd_waic: np.ndarray
+    elpd_loo: np.ndarray
+    p_loo: np.ndarray
+    is_ess: np.ndarray
+    max_weight: np.ndarray
+    n_neg_inf: np.ndarray
+    n_pos_inf: np.ndarray
+    n_nan: np.ndarray
+
+    @classmethod
+    def from_result(cls, names: Sequence[str], n_draws: int, res: dict) -> "PointwiseComparison":
+        """From `LoglikStream.result()`."""
+        return cls(names=list(names), n_draws=int(n_draws), **{k: res[k] for k in POINTWISE + ("n_neg_inf", "n_pos_inf", "n_nan")})
+
+    @property
+    def n_sel(self) -> int:
+        return len(self.names)
+
+    @property
+    def elpd_waic_total(self) -> float:
+        return _total(self.elpd_waic)
+
+    @property
+    def elpd_loo_total(self) -> float:
+        return _total(self.elpd_loo)
+
+    @property
+    def p_waic_total(self) -> float:
+        return _total(self.p_waic)
+
+    @property
+    def p_loo_total(self) -> float:
+        return _total(self.p_loo)
+
+    @property
+    def lppd_total(self) -> float:
+        return _total(self.lppd)
+
+    def se(self, name: str = "elpd_loo") -> float:
+        """The standard error of the total of a pointwise figure: sqrt(O var(pointwise, ddof=1)), O statements (NaN for O = 1)."""
+        if name not in POINTWISE:
+            raise ValueError(f"se: {name!r} is no pointwise figure {POINTWISE}")
+        return _se(getattr(self, name))
+
+
+def _se(a: np.ndarray) -> float:
+    a = np.asarray(a, dtype=np.float64)
+    if a.size < 2:
+        return float("nan")
+    with np.errstate(invalid="ignore"):
+        return float(math.sqrt(a.size * float(np.var(a, ddof=1)))) if np.isfinite(a).all() else float("nan")
+
+
+def model_comparison(x, names: Optional[Sequence[str]] = None, device: int = 0) -> PointwiseComparison:
+    """WAIC / IS-LOO of a stored pointwise log-likelihood table: `x` is a `ChainBatch` with `log_likelihood` (names default to its
+    `predictive_names`) or an array [n][n_sel][C].  The table is uploaded and run through the log-likelihood stream as one chunk;
+    device memory is the table plus 80 x n_sel x C bytes."""
+    ll = getattr(x, "log_likelihood", x)
+    if ll is None:
+        raise ValueError("model_comparison: the ChainBatch has no log_likelihood (run the driver with pointwise=True)")
+    if names is None:
+        names = getattr(x, "predictive_names", None) if ll is not x else None
+    table = np.ascontiguousarray(ll, dtype=np.float64)
+    if table.ndim != 3 or min(table.shape) < 1:
+        raise ValueError(f"model_comparison: the table must be [n][n_sel][C] with every extent at least 1, not {table.shape}")
+    n, n_sel, C_ = table.shape
+    names = [f"observe#{k}" for k in range(n_sel)] if names is None else [str(a) for a in names]
+    if len(names) != n_sel:
+        raise ValueError(f"model_comparison: {len(names)} names for {n_sel} statements")
+    eng = E.Engine(E.compile_model(W.normal_sites(1)), C_, seed=0, device=device)       # the stream wants the engine's chain count only
+    buf = stream = None
+    try:
+        buf = eng.upload(table)
+        stream = eng.loglik_stream(n, n_sel)
+        stream.update(buf, n)
+        return PointwiseComparison.from_result(names, n * C_, stream.result())
+    finally:
+        if stream is not None:
+            stream.free()
+        if buf is not None:
+            eng.device_free(buf)
+        eng.close()
+
+
+def compare_models(a: PointwiseComparison, b: PointwiseComparison, which: str = "elpd_loo") -> Tuple[float, float]:
+    """(total of a - total of b, the standard error of the pointwise difference sqrt(O var(a_k - b_k, ddof=1))) for `which` =
+    "elpd_loo" | "elpd_waic".  Both must hold the same observe statements in the same order (the same data): ValueError otherwise."""
+    if which not in ("elpd_loo", "elpd_waic"):
+        raise ValueError(f"compare_models: which must be 'elpd_loo' or 'elpd_waic', not {which!r}")
+    if a.n_sel != b.n_sel:
+        raise ValueError(f"compare_models: {a.n_sel} statements against {b.n_sel}")
+    if list(a.names) != list(b.names):
+        raise ValueError("compare_models: the two comparisons name different observe statements")
+    pa, pb = np.asarray(getattr(a, which), dtype=np.float64), np.asarray(getattr(b, which), dtype=np.float64)
+    return _total(pa) - _total(pb), _se(pa - pb)

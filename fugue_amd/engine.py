@@ -97,6 +97,7 @@ ABI_SYMBOLS = [
     "fg_diag_qstream_result", "fg_diag_qstream_free",
     "fg_diag_cstream_new", "fg_diag_cstream_update", "fg_diag_cstream_count", "fg_diag_cstream_result", "fg_diag_cstream_free",
     "fg_diag_cells_f64",
+    "fg_loglik_stream_new", "fg_loglik_stream_update", "fg_loglik_stream_count", "fg_loglik_stream_pooled", "fg_loglik_stream_result", "fg_loglik_stream_free",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -261,6 +262,13 @@ def lib():
     L.fg_diag_cstream_result.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.fg_diag_cstream_free.restype = None
     L.fg_diag_cstream_free.argtypes = [vp]
+    L.fg_loglik_stream_new.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.fg_loglik_stream_update.argtypes = [vp, vp, C.c_int]
+    L.fg_loglik_stream_count.argtypes = [vp]
+    L.fg_loglik_stream_pooled.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.fg_loglik_stream_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.fg_loglik_stream_free.restype = None
+    L.fg_loglik_stream_free.argtypes = [vp]
     L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
@@ -863,6 +871,11 @@ class Engine:
         cells equal to lo[k] + j in bin j of bins[k]; whatever lies outside is counted in `below` / `above`."""
         return DiagCountStream(self, n_total, n_rec, rows, vtypes, lo, bins)
 
+    def loglik_stream(self, n_total: int, n_sel: int) -> "LoglikStream":
+        """A `fg_loglik_stream`: WAIC and importance-sampling LOO of `n_sel` observe statements from chunks [n_chunk][n_sel][C] of the
+        pointwise log-likelihood (`predict_eval`'s `loglik` table) of a run of `n_total` draws that is never stored."""
+        return LoglikStream(self, n_total, n_sel)
+
     def cells_f64(self, d_cells: int, n: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], out: Optional[int] = None) -> int:
         """`fg_diag_cells_f64`: rows `rows` of the device cells [n][n_rec][C] as doubles [n][len(rows)][C] in the device buffer `out`
         (allocated here when None: the caller frees it), asynchronously: an f64 row is copied, a u64 row converted as unsigned
@@ -1125,6 +1138,71 @@ class DiagCountStream:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+LL_POOLED, LL_FIGURES = 8, 8                # FG_LL_POOLED, FG_LL_FIGURES
+LL_POOLED_WORDS = ("mx", "sp", "mn", "sn", "sn2", "n_fin", "mean", "ssd")
+LL_FIGURE_NAMES = ("lppd", "mean_ll", "p_waic", "elpd_waic", "elpd_loo", "p_loo", "is_ess", "max_weight")
+
+
+class LoglikStream:
+    """`fg_loglik_stream` (fg_loglik_stream.hip): WAIC and importance-sampling LOO per observe statement from the pointwise
+    log-likelihood of a run handed over in chunks [n_chunk][n_sel][C] of doubles (`Engine.predict_eval`'s `loglik` table).  Every
+    (statement, chain) column is updated in draw order by one thread and the chains are pooled by a fixed tree on the chain index, so
+    the result does not depend on the chunking, bit for bit.  Device memory: 80 x n_sel x C bytes (5.4 GB at n_sel = 1 024 and
+    C = 65 536; select the statements to compare with `predict_eval`'s `sel`).  Close it before its engine."""
+
+    def __init__(self, engine: Engine, n_total: int, n_sel: int):
+        for name, v in (("n_total", n_total), ("n_sel", n_sel)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        self.engine, self.n, self.n_sel = engine, int(n_total), int(n_sel)
+        self.h = None
+        out = C.c_void_p()
+        _check(lib().fg_loglik_stream_new(engine.h, self.n, self.n_sel, C.byref(out)))
+        self.h = out.value
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the stream is closed")
+        return self.h
+
+    def update(self, d_loglik: int, n_chunk: int):
+        """The next `n_chunk` draws, a device buffer of doubles [n_chunk][n_sel][C]; asynchronous.  n_chunk = 0 does nothing."""
+        _check(lib().fg_loglik_stream_update(self._handle(), d_loglik, int(n_chunk)))
+
+    def count(self) -> int:
+        return int(lib().fg_loglik_stream_count(self._handle()))
+
+    def pooled(self) -> dict:
+        """The pooled words of every statement: `words` float64 [n_sel][8] in the order LL_POOLED_WORDS, `counts` int64 [n_sel][3]
+        (cells that are -inf, +inf, NaN).  Raises EngineError (FG_E_STATE) before `n_total` draws have arrived."""
+        words, counts = np.zeros((self.n_sel, LL_POOLED)), np.zeros((self.n_sel, 3), dtype=np.int64)
+        _check(lib().fg_loglik_stream_pooled(self._handle(), _dp(words), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(words=words, counts=counts)
+
+    def result(self) -> dict:
+        """The figures of every statement, each float64 [n_sel]: lppd, mean_ll, p_waic (divisor N - 1), elpd_waic, elpd_loo, p_loo,
+        is_ess, max_weight; and n_neg_inf, n_pos_inf, n_nan int64 [n_sel].  Raises EngineError (FG_E_STATE) before `n_total` draws."""
+        figs, counts = np.zeros((LL_FIGURES, self.n_sel)), np.zeros((self.n_sel, 3), dtype=np.int64)
+        _check(lib().fg_loglik_stream_result(self._handle(), _dp(figs), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = {name: figs[i].copy() for i, name in enumerate(LL_FIGURE_NAMES)}
+        out.update(n_neg_inf=counts[:, 0].copy(), n_pos_inf=counts[:, 1].copy(), n_nan=counts[:, 2].copy())
+        return out
+
+    def free(self):
+        if getattr(self, "h", None):
+            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
+                lib().fg_loglik_stream_free(self.h)
+            self.h = None
+
+    close = free
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 

@@ -324,6 +324,7 @@ class ChainSummary:
     results: Optional["ChainSummary"] = None      # results=True: the same figures of the model's return value, `sites` = the result names
     discrete: Optional["DiscreteSummary"] = None  # adaptive_mcmc_chain_summary(discrete=True): the frequency tables of the discrete sites
     predictive: Optional["ChainSummary"] = None   # predictive=: the same figures of the replicated data, `sites` = the selected observe addresses
+    comparison: Optional["PointwiseComparison"] = None   # pointwise=: WAIC / IS-LOO per selected observe statement (fugue_amd.comparison)
 
 
 @dataclass
@@ -382,7 +383,7 @@ def _default_bins(cp, j: int) -> Tuple[int, int]:
 
 
 def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
-                    after_first_pass=None, result_rows=False, discrete_bins=False, predict=None):
+                    after_first_pass=None, result_rows=False, discrete_bins=False, predict=None, pointwise=None):
     """step(n, buf) records n draws into buf; one chunk buffer is alive at a time.  A chunk is seen through FEEDS: a view of it as
     doubles [n][rows][C] and the diagnostics stream (with quantiles: and the quantile stream) that take the view.
       - discrete_bins False: buf is [n][d][C] doubles (the f64 sites `sites`) and is its own view.
@@ -394,6 +395,9 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
       - predict (dict(sel=observe indices, rows=as result_rows)) adds the replicated data of the selected f64 observe sites: every
         chunk is turned into one reused [chunk][n_sel][C] buffer (`Engine.predict_eval` with iter0 = the chunk's first draw: the stream
         is keyed by the absolute draw index, so a replayed chunk holds the same bits), a further view.
+      - pointwise (dict(sel=observe indices, rows=as result_rows)) adds WAIC / IS-LOO of the selected observe statements: every chunk's
+        log-likelihood goes into one reused [chunk][n_sel][C] buffer (`Engine.predict_eval`, loglik only) that the log-likelihood stream
+        takes (`Engine.loglik_stream`).  First pass only: a replay pass for quantiles does not feed it.
     A view is called with (chunk buffer, draws in it, index of its first draw in the sampling phase).
     quantiles: the state after warmup is exported, the first sampling pass feeds every stream, `after_first_pass()` reads the
     sampler's statistics, and while a quantile stream wants another pass the blob is imported into the same engine and the same
@@ -452,10 +456,16 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
             pbuf = alloc(chunk * len(psel) * C_)
             prd = feed([cp.observe_names[k] for k in psel], len(psel),
                        lambda buf, n, t0: eng.predict_eval(buf, n, rows=prows, iter0=t0, sel=psel, out=pbuf, loglik=False)[0])
+        lls = None
+        if pointwise is not None:
+            lsel, lrows = list(pointwise["sel"]), pointwise["rows"]
+            lbuf = alloc(chunk * len(lsel) * C_)
+            lls = eng.loglik_stream(n_samples, len(lsel))
+            streams.append(lls)
         blob = eng.state_export() if quantiles else None
         buf = alloc(chunk * chunk_rows * C_)
 
-        def one_pass(live, counters=()):
+        def one_pass(live, counters=(), first=False):
             done = 0
             while done < n_samples:
                 n = min(chunk, n_samples - done)
@@ -468,14 +478,20 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
                             c.update(view, n)
                 for c in counters:
                     c.update(buf, n)
+                if first and lls is not None:
+                    eng.predict_eval(buf, n, rows=lrows, iter0=done, sel=lsel, out=False, loglik=lbuf)
+                    lls.update(lbuf, n)
                 done += n
 
-        one_pass([c for f in feeds for c in (f["stream"], f["qs"]) if c is not None], [cs] if cs is not None else [])
+        one_pass([c for f in feeds for c in (f["stream"], f["qs"]) if c is not None], [cs] if cs is not None else [], first=True)
         out = figures(main, sites)
         if res is not None:
             out.results = figures(res)
         if prd is not None:
             out.predictive = figures(prd)
+        if lls is not None:
+            from .comparison import PointwiseComparison
+            out.comparison = PointwiseComparison.from_result([cp.observe_names[k] for k in lsel], n_samples * int(C_), lls.result())
         if discrete:
             tab = cs.result() if cs is not None else dict(counts=[], below=np.zeros(0, dtype=np.uint64), above=np.zeros(0, dtype=np.uint64), min=[], max=[])
             out.discrete = DiscreteSummary([cp.site_names[j] for j in w_rows], [cp.site_vtypes[j] for j in w_rows], [b[0] for b in bins], tab["counts"],
@@ -512,6 +528,13 @@ def _want_results(cp, results: bool, recorded=None, who: str = ""):
                              "(a streamed MH run records its f64 sites only)")
 
 
+def _summary_pointwise(cp, pointwise, who: str):
+    """The selection of `pointwise=False | True | [addresses]`: any observe statement (the log-likelihood is f64 whatever the site's type)."""
+    if pointwise is False or pointwise is None:
+        return None
+    return _predictive_sel(cp, pointwise, True, who)
+
+
 def _summary_predictive(cp, predictive, who: str):
     """The selection of a summary driver: f64 observe sites only (a discrete one would need the count stream)."""
     sel = _predictive_sel(cp, predictive, False, who)
@@ -525,7 +548,7 @@ def _summary_predictive(cp, predictive, who: str):
 
 def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
                       chunk: int = 64, max_lag: int = 64, device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536,
-                      results: bool = False, predictive=False) -> ChainSummary:
+                      results: bool = False, predictive=False, pointwise=False) -> ChainSummary:
     """`hmc_chain` for runs longer than memory: the same transitions (`fg_hmc_step` is incremental), `chunk` at a time into one
     draw buffer that a diagnostics stream consumes, and the summary of every f64 site instead of the draws.  `max_lag` bounds how
     far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  `quantiles=True` adds the five quantiles
@@ -536,13 +559,17 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
     `ChainSummary.results`: the same figures of the model's return value (the `A` of hmc.rs:566-583), evaluated on the device chunk
     by chunk; the site figures are the ones `results=False` gives.  `predictive=True | [addresses]` adds `ChainSummary.predictive`:
     the same figures of the replicated data of the selected f64 observe sites, sampled on the device chunk by chunk (a replay pass
-    samples a chunk again to the same bits); a selected discrete observe site raises ValueError."""
+    samples a chunk again to the same bits); a selected discrete observe site raises ValueError.  `pointwise=True | [addresses]` adds
+    `ChainSummary.comparison`, a `PointwiseComparison`: WAIC and importance-sampling LOO per (selected) observe statement, discrete ones
+    included, from the log-likelihood of every chunk (`Engine.loglik_stream`; the table is never held; device memory 80 bytes per
+    statement and chain, so a model with very many observe statements names the ones to compare).  Nothing else changes."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     if cp.d == 0:
         raise ValueError("hmc_chain_summary: the model has no f64 site to summarise")
     _want_results(cp, results, who="hmc_chain_summary")
     psel = _summary_predictive(cp, predictive, "hmc_chain_summary")
+    lsel = _summary_pointwise(cp, pointwise, "hmc_chain_summary")
     cfg = config or HMCConfig()
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     try:
@@ -553,7 +580,8 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
             out.accept_rate, out.mean_step_size, out.n_divergent = st.accept_rate, st.mean_step_size, int(st.n_divergent)
 
         out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag, quantiles, quantile_capacity, stats,
-                              result_rows=None if results else False, predict=None if psel is None else dict(sel=psel, rows=None))
+                              result_rows=None if results else False, predict=None if psel is None else dict(sel=psel, rows=None),
+                              pointwise=None if lsel is None else dict(sel=lsel, rows=None))
     finally:
         eng.close()
     return out
@@ -562,7 +590,8 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
 def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, n_chains: int = 1,
                                 overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
                                 device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536, results: bool = False,
-                                discrete: bool = False, discrete_bins: Optional[Dict[str, Tuple[int, int]]] = None, predictive=False) -> ChainSummary:
+                                discrete: bool = False, discrete_bins: Optional[Dict[str, Tuple[int, int]]] = None, predictive=False,
+                                pointwise=False) -> ChainSummary:
     """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
     only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  `quantiles=True` adds the five
     quantiles as `hmc_chain_summary` does: every pass beyond the first REPEATS THE SAMPLING PHASE from the state exported after
@@ -577,13 +606,16 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
     the f64 figures are those `discrete=False` gives.
 
     `predictive=True | [addresses]` adds `ChainSummary.predictive` as `hmc_chain_summary` does.  The parameters of an observe statement
-    must come from recorded sites: a model with a discrete site needs `discrete=True` (which records every site)."""
+    must come from recorded sites: a model with a discrete site needs `discrete=True` (which records every site).
+
+    `pointwise=True | [addresses]` adds `ChainSummary.comparison` as `hmc_chain_summary` does, under the same condition on recorded sites."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     who = "adaptive_mcmc_chain_summary"
     psel = _summary_predictive(cp, predictive, who)
-    if psel is not None and not discrete and cp.d != cp.S:
-        raise ValueError(f"{who}: predictive on a model with discrete sites needs discrete=True (a streamed MH run records its f64 sites only, "
+    lsel = _summary_pointwise(cp, pointwise, who)
+    if (psel is not None or lsel is not None) and not discrete and cp.d != cp.S:
+        raise ValueError(f"{who}: predictive / pointwise on a model with discrete sites needs discrete=True (a streamed MH run records its f64 sites only, "
                          "and the discrete ones move)")
     if discrete_bins is not None and not discrete:
         raise ValueError(f"{who}: discrete_bins is given, but discrete=True is not")
@@ -611,7 +643,8 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
 
         out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag,
                               quantiles, quantile_capacity, stats, result_rows=rec if results else False,
-                              discrete_bins=dict(discrete_bins or {}) if discrete else False, predict=None if psel is None else dict(sel=psel, rows=rec))
+                              discrete_bins=dict(discrete_bins or {}) if discrete else False, predict=None if psel is None else dict(sel=psel, rows=rec),
+                              pointwise=None if lsel is None else dict(sel=lsel, rows=rec))
     finally:
         eng.close()
     return out

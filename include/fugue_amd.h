@@ -640,6 +640,36 @@ void fg_diag_cstream_free(fg_diag_cstream *s);                 /* diagnostics.rs
  * unknown tag. */
 int fg_diag_cells_f64(fg_engine *e, const void *d_cells, int n, int n_rec, const int32_t *h_rows,
                       const int32_t *h_vtypes, int n_sel, double *d_out);
+/* ------------------------------------------------------------------ model comparison without a stored table
+ * WAIC and importance-sampling LOO (BDA3 7.2; the reference has neither) from the pointwise log-likelihood fg_predict_eval writes,
+ * d_loglik [n][n_sel][C], handed over one chunk at a time.  The stream keeps 10 words per (selected observe statement, chain) --
+ * 80 x n_sel x C bytes, 5.4 GB at n_sel = 1 024 and C = 65 536: select the statements to compare with fg_predict_eval's h_sel --
+ * updated in draw order by one thread, so the state does not depend on the chunking, bit for bit.  At read-out the chains of a
+ * statement are pooled by a fixed binary tree on the chain index (a function of C alone) into FG_LL_POOLED finite words
+ *   mx, sum exp(x - mx), mn, sum exp(mn - x), sum exp(mn - x)^2, the finite cells F, their mean, their sum of squared deviations
+ * and three counters of the cells that are -inf, +inf, NaN.  Per statement, over the N = n_total x C pooled cells x, the
+ * FG_LL_FIGURES figures are
+ *   0 lppd = ln((1/N) sum exp x)            1 mean_ll = mean x              2 p_waic = the variance of x, divisor N - 1 (BDA3 eq. 7.12)
+ *   3 elpd_waic = lppd - p_waic             4 elpd_loo = -ln((1/N) sum r), r = exp(-x) the raw importance ratios
+ *   5 p_loo = lppd - elpd_loo               6 is_ess = (sum r)^2 / sum r^2  7 max_weight = max r / sum r
+ * as the two-pass formulas give them in IEEE arithmetic: a NaN cell makes every figure of its statement NaN, a -inf cell is zero
+ * mass in lppd and makes elpd_loo -inf, a +inf cell makes lppd +inf; both count in N.  No Pareto smoothing: is_ess and max_weight
+ * are the diagnostic of the raw ratios.  This engine's chains only.  The stream reads engine state and changes none. */
+#define FG_LL_POOLED 8
+#define FG_LL_FIGURES 8
+typedef struct fg_loglik_stream fg_loglik_stream;
+/* FG_E_BAD_ARG: n_total < 1, n_sel < 1.  The stream must be freed before its engine. */
+int  fg_loglik_stream_new(fg_engine *e, int n_total, int n_sel, fg_loglik_stream **out);
+/* the next n_chunk draws d_loglik [n_chunk][n_sel][C]; asynchronous on the engine's stream; n_chunk == 0 is FG_OK without a
+ * launch.  FG_E_STATE when the chunk would pass n_total. */
+int  fg_loglik_stream_update(fg_loglik_stream *s, const double *d_loglik, int n_chunk);
+int  fg_loglik_stream_count(const fg_loglik_stream *s);        /* draws taken so far */
+/* the pooled words h_words [n_sel][FG_LL_POOLED] and counters h_counts [n_sel][3] (-inf, +inf, NaN).  FG_E_STATE before n_total
+ * draws have arrived. */
+int  fg_loglik_stream_pooled(fg_loglik_stream *s, double *h_words, int64_t *h_counts);
+/* the figures h_figures [FG_LL_FIGURES][n_sel] and the counters as above.  FG_E_STATE before n_total draws have arrived. */
+int  fg_loglik_stream_result(fg_loglik_stream *s, double *h_figures, int64_t *h_counts);
+void fg_loglik_stream_free(fg_loglik_stream *s);
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

@@ -9,6 +9,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_diag_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_qstream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_cstream { _p: [u8; 0] }
+#[repr(C)] pub struct fg_loglik_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_abc { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
@@ -199,6 +200,13 @@ extern "C" {
     pub fn fg_diag_cstream_free(s: *mut fg_diag_cstream);
     pub fn fg_diag_cells_f64(e: *mut fg_engine, d_cells: *const c_void, n: c_int, n_rec: c_int, h_rows: *const i32, h_vtypes: *const i32,
                              n_sel: c_int, d_out: *mut f64) -> c_int;
+    // ---- WAIC / importance-sampling LOO from a streamed pointwise log-likelihood table (fg_loglik_stream.hip)
+    pub fn fg_loglik_stream_new(e: *mut fg_engine, n_total: c_int, n_sel: c_int, out: *mut *mut fg_loglik_stream) -> c_int;
+    pub fn fg_loglik_stream_update(s: *mut fg_loglik_stream, d_loglik: *const f64, n_chunk: c_int) -> c_int;
+    pub fn fg_loglik_stream_count(s: *const fg_loglik_stream) -> c_int;
+    pub fn fg_loglik_stream_pooled(s: *mut fg_loglik_stream, h_words: *mut f64, h_counts: *mut i64) -> c_int;
+    pub fn fg_loglik_stream_result(s: *mut fg_loglik_stream, h_figures: *mut f64, h_counts: *mut i64) -> c_int;
+    pub fn fg_loglik_stream_free(s: *mut fg_loglik_stream);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
