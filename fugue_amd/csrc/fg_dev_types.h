@@ -24,6 +24,9 @@ struct FgHmcDev {
     // derived from h (fg_internal_hmc_set_cfg; never exported): n / (2h) == fma(n, div2_hi, n * div2_lo) when div2 is set (fg_div2.h);
     // k_hmc_sep_steps's folded instantiations, which the plan picks only then, read hi and lo
     double div2_hi, div2_lo; int div2;
+    // derived from the program and h (fg_sep_range.h, same place): every finite n != 0 of a folded trajectory lies in the short quotient's
+    // window, so the folded loop issues no range test
+    int range;
 };
 
 

@@ -13,6 +13,7 @@
 #include "fg_engine_internal.h"
 #include "fg_hmc_sep_plan.h"
 #include "fg_div2.h"
+#include "fg_sep_range.h"
 #include "fg_gradstream.h"
 #include "fg_cold.h"
 
@@ -953,6 +954,14 @@ void fg_internal_hmc_set_cfg(fg_engine *e, const fg_hmc_config *cfg) {
     // k_hmc_sep_steps's folded loop divides by 2h in two instructions: only when the host can prove that exact for this h (else the plan
     // gets no fold, fg_hmc_sep_launch); hi and lo are 0 when refused
     e->H.div2 = fg_div2_prove(2.0 * e->H.h, &e->H.div2_hi, &e->H.div2_lo) ? 1 : 0;
+    // ... and tests the quotient's range only when the host cannot prove that this program's numerators stay inside it for this h
+    e->H.range = 0;
+    if (e->prog && !e->prog->sep_coord.empty()) {
+        std::vector<int> off, n; std::vector<double> c, s, lns;
+        for (const FgSepCoord &cd : e->prog->sep_coord) { off.push_back(cd.off); n.push_back(cd.n & 7); }
+        for (const FgSepRec &r : e->prog->sep) { c.push_back(r.c); s.push_back(r.inv); lns.push_back(r.lns); }
+        e->H.range = fg_sep_range_prove(e->H.h, off.size(), off.data(), n.data(), c.data(), s.data(), lns.data(), nullptr) ? 1 : 0;
+    }
 }
 
 // does fg_hmc_step run this program through the kernel compiled at run time ahead of the stream kernel (fg_hmc_jit_first, fg_hmc_split_plan.h)?
@@ -1224,6 +1233,7 @@ int fg_hmc_set_n_leapfrog(fg_engine *e, int n_leapfrog) {     // hmc.rs:751-753
 const char *fg_hmc_last_kernel(const fg_engine *e) { return e ? e->last_hmc_kernel.c_str() : ""; }
 const char *fg_mh_last_kernel(const fg_engine *e) { return e ? e->last_mh_kernel.c_str() : ""; }
 int fg_hmc_short_quotient(const fg_engine *e) { return (e && e->hmc_ready && e->H.div2) ? 1 : 0; }
+int fg_hmc_range_proved(const fg_engine *e) { return (e && e->hmc_ready && e->H.range) ? 1 : 0; }
 int fg_hmc_is_warming_up(const fg_engine *e) { return (e && e->hmc_ready && e->iter < e->n_warmup) ? 1 : 0; }   // hmc.rs:780-782
 int64_t fg_hmc_iterations(const fg_engine *e) { return (e && e->hmc_ready) ? (int64_t)e->iter : 0; }             // hmc.rs:785-787
 

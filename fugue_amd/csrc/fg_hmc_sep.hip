@@ -122,7 +122,12 @@ template <> struct FgSepScalarRb<const FG_AS4 char *> { static constexpr bool va
 // the host proved for this run's 2h (fg_div2_prove, fg_div2.h) that this is RN(n / (2h)) for every n of the same window, and hands
 // the plan FOLD only then.  c_hi and c_lo are wave-uniform (SGPRs), one per instruction; the chain from n to the kick is 2 long
 // instead of fg_div_const's 5.  The deferred range test and the checked re-run (fg_div_const, true division) are unchanged.
-template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, bool FOLD = false, typename RB = const FG_AS4 char *>
+// RANGED (FOLD only): no range test at all.  The host proved (fg_sep_range.h, per program and h) that a finite n != 0 of this loop lies
+// in [2^-54, 2^953); n = +0 gives g = +0 = +0 / 2h in the two instructions as well, and a non-finite n a non-finite momentum for good,
+// which the caller's test sends through the CHECK instance as before.  A program whose bound is refused runs RANGED = false.
+// The loop is peeled for a run-time L >= 1: first step (half kick, drift), L - 1 middle steps with ONE back-branch, last step (gradient,
+// half kick) -- the same f64 operations in the same order as one loop with uniform branches on the step index.
+template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, bool FOLD = false, typename RB = const FG_AS4 char *, bool RANGED = false>
 __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p_io, double emi, double hk, int L, double h, double two_h,
                                                   double rcp_2h, double *terms, int tw, int nobs_rt, double c_hi = 0.0, double c_lo = 0.0) {
 #define FG_SEP_HAS(k) (NOBS >= 0 ? NOBS >= (k) : nobs_rt >= (k))
@@ -138,8 +143,9 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
     // register allocator may park them in VGPR lanes and read them back in EVERY step (8 v_readlane per step in the headline instantiation)
     // (records by scalar loads only: in the half- and quarter-tile forms, whose records sit in VGPRs, the split costs 12 to 18 spilled VGPRs)
     if (FOLD && !CHECK && !AN && FgSepScalarRb<RB>::value) asm volatile("" : "+s"(h), "+s"(c_hi), "+s"(c_lo));
+    if (CHECK && !AN && NOBS >= 0 && FgSepScalarRb<RB>::value) asm volatile("" : "+s"(h));     // (the resident forms' inline checked loop: h likewise)
     uint32_t nrange = 0u;                                        // FOLD: max over the steps of 2 |hi(n)| - 2 hi(2^-823), mod 2^32
-    for (int gs = 0; gs <= L; ++gs) {
+    auto grad = [&]() __attribute__((always_inline)) -> double {     // the force component at q (L + 1 per trajectory)
         double g;
         if (AN) {
 #define FG_SEP_ANTERM(k) { const double dl = q - fg_dbl(a##k[2], a##k[3]);                                                   \
@@ -188,7 +194,8 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         const double n = tp - tm;
         if (!CHECK && FOLD) g = __builtin_fma(n, c_hi, n * c_lo);   // (lp - lm) / (2h), hmc.rs:322: proved exact for this h on the host
         else g = fg_div_const(n, two_h, rcp_2h);
-        if (!CHECK && FOLD) {                                    // in range iff 2 |hi(n)| - 0x19000000 < 0xde000000 (mod 2^32)
+        if (!CHECK && FOLD && RANGED) {                          // the host bounded n for this program and h: nothing to record
+        } else if (!CHECK && FOLD) {                             // in range iff 2 |hi(n)| - 0x19000000 < 0xde000000 (mod 2^32)
             uint32_t hi = (uint32_t)__double2hiint(n);
             asm("" : "+v"(hi));                                  // (else the shift is folded into the 64-bit word: v_alignbit + v_and)
             const uint32_t nr = (hi << 1) - 0x19000000u;
@@ -199,12 +206,19 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
         }
         }
         if (CHECK) bad = bad || !fg_finite(g);
-        const double kick = hk * g;
-        p = p + kick;                                            // hmc.rs:389 / :400
-        if (gs > 0 && gs < L) { asm volatile(""); p = p + kick; }   // trailing kick of this step + leading kick of the next
-        if (gs < L) { asm volatile(""); q = q + emi * p; }       // hmc.rs:391-393
+        return g;
+    };
+    // first step: half kick, drift | L - 1 middle steps: gradient, the trailing kick of one step and the leading kick of the next (the
+    // empty asm keeps them two additions), drift | last step: gradient, half kick.  L >= 1 (fg_internal_hmc_set_cfg).
+    { const double kick = hk * grad(); p = p + kick; asm volatile(""); q = q + emi * p; }       // hmc.rs:389, :391-393
+    for (int gs = 1; gs < L; ++gs) {
+        const double kick = hk * grad();
+        p = p + kick;                                            // hmc.rs:400
+        asm volatile(""); p = p + kick;                          // hmc.rs:389
+        asm volatile(""); q = q + emi * p;                       // hmc.rs:391-393
     }
-    if (!CHECK && FOLD && nrange >= 0xde000000u) p = __builtin_nan("");   // some quotient out of fg_div_const's range: the checked re-run
+    { const double kick = hk * grad(); p = p + kick; }           // hmc.rs:400
+    if (!CHECK && FOLD && !RANGED && nrange >= 0xde000000u) p = __builtin_nan("");   // some quotient out of fg_div_const's range: the checked re-run
     if (U0) { double lp = FG_SEP_LP_U(q); FG_SEP_NAN_NEG_INF(q, lp) terms[a0[1] * tw] = lp; }
     else FG_SEP_TERM(0)
     if (FG_SEP_HAS(1)) FG_SEP_TERM(1)
@@ -366,7 +380,8 @@ __device__ __forceinline__ bool fg_dense_trajectory(const FgProgramDev &P, const
 // wave 0 adds and decides, the other waves draw the Box-Muller pairs of their next transition.  The arithmetic per coordinate is
 // fg_sep_trajectory's for the shape NC = 0 dispatches to: every result is bit-identical to NC = 0.  (The records themselves are still
 // loaded per trajectory: held for four coordinates they spill SGPRs into the leapfrog loop.)
-template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false, bool FOLD = false>
+template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false, bool FOLD = false,
+          bool RANGED = false /* FOLD without the range test of its quotient (fg_sep_range.h): no part of the plan's key, the launcher's choice */>
 __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgProgramDev P, FgChainCtx X, FgHmcDev H, FgSegSep seg, int iter0, int n_steps,
                                                                              int n_warmup, int welford_on, double *draws, int first_sample_t,
                                                                              double *pos_all /*[n][d][C] or null*/, double *info /*[n][4][C] or null*/) {
@@ -378,6 +393,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     constexpr int NCX = RES ? NC : 1;
     static_assert(!RES || (MODE == 0 && HALF == 0 && NC <= 4 && NOBS_R >= 0 && NOBS_R <= 3), "resident form: sparse 64-chain tiles");
     static_assert(!FOLD || MODE == 0, "the folded trajectory loop: sparse finite difference only");
+    static_assert(!RANGED || FOLD, "the range test is the folded loop's");
     const int lane = threadIdx.x & (tw - 1);                       // chain of the tile
     const int half = HALF == 1 ? (int)((threadIdx.x >> 5) & 1u) : (HALF == 2 ? (int)((threadIdx.x >> 4) & 3u) : 0);   // which of the wave's 2 / 4 coordinates this lane runs
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -509,7 +525,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                 const double emi = MASS ? e * mii : e;
                 const double q0 = q, p0 = p;
                 const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + roff[j]);
-                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo);
+                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD, const FG_AS4 char *, RANGED>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo);
                 if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                     // (inline, not fg_sep_trajectory_checked: no call.  Its generic record mix computes the same bits for this shape:
                     // every record is POW2 -- (x - mu) * (1 / sigma) -- and a U0 record is exactly N(0, 1), see FG_SEP_LP_U)
@@ -655,7 +671,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             const double q0 = q, p0 = p;
             if (HALF) {
                 const char *rb = (const char *)(P.sep + P.sep_coord[ci].off);
-#define FG_SEP_CALLH(NO, UU) fg_sep_trajectory<NO, true, false, false, UU, FOLD, const char *>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO, c_hi, c_lo)
+#define FG_SEP_CALLH(NO, UU) fg_sep_trajectory<NO, true, false, false, UU, FOLD, const char *, RANGED>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO, c_hi, c_lo)
                 if ((cd.n & 512) && nobs == 1) FG_SEP_CALLH(1, true);
                 else if (nobs == 1) FG_SEP_CALLH(1, false); else if (nobs == 0) FG_SEP_CALLH(0, false); else if (nobs == 2) FG_SEP_CALLH(2, false); else FG_SEP_CALLH(3, false);
 #undef FG_SEP_CALLH
@@ -666,8 +682,8 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                 }
             } else {
             const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + cd.off);
-#define FG_SEP_CALL(NO, PP) fg_sep_trajectory<NO, PP, false, AN, false, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO, c_hi, c_lo)
-            if (!AN && (cd.n & 512) && nobs == 1) fg_sep_trajectory<1, true, false, false, true, FOLD>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, 1, c_hi, c_lo);
+#define FG_SEP_CALL(NO, PP) fg_sep_trajectory<NO, PP, false, AN, false, FOLD, const FG_AS4 char *, RANGED>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, NO, c_hi, c_lo)
+            if (!AN && (cd.n & 512) && nobs == 1) fg_sep_trajectory<1, true, false, false, true, FOLD, const FG_AS4 char *, RANGED>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, terms, tw, 1, c_hi, c_lo);
             else if (cd.n & 256) { if (nobs == 1) FG_SEP_CALL(1, true); else if (nobs == 0) FG_SEP_CALL(0, true); else if (nobs == 2) FG_SEP_CALL(2, true); else FG_SEP_CALL(3, true); }
             else { if (nobs == 1) FG_SEP_CALL(1, false); else if (nobs == 0) FG_SEP_CALL(0, false); else if (nobs == 2) FG_SEP_CALL(2, false); else FG_SEP_CALL(3, false); }
 #undef FG_SEP_CALL
@@ -819,8 +835,13 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
 }
 
 using FgSepKernel = void (*)(FgProgramDev, FgChainCtx, FgHmcDev, FgSegSep, int, int, int, int, double *, int, double *, double *);
-struct FgSepVariant { FgSepKey key; FgSepKernel fn; unsigned long long raised; };       // raised: fg_launch
-#define FG_SEP_ENTRY(M, MODE, HALF, NC, NOBS, U0, FOLD) { { M, MODE, HALF, NC, NOBS, U0, FOLD }, k_hmc_sep_steps<M, MODE, HALF, NC, NOBS, U0, FOLD>, 0 },
+// fn_ranged: the FOLD instantiation again without the range test (null otherwise) -- same key, same plan, same name.  The plain
+// 64-chain MASS form keeps the test: without it the register allocator puts scratch accesses into its generic leapfrog loop.
+struct FgSepVariant { FgSepKey key; FgSepKernel fn, fn_ranged; unsigned long long raised, raised_ranged; };       // raised: fg_launch
+template <bool M, int MODE, int HALF, int NC, int NOBS, bool U0, bool FOLD> static constexpr FgSepKernel fg_sep_ranged_fn() {
+    if constexpr (FOLD && !(M && HALF == 0 && NC == 0)) return k_hmc_sep_steps<M, MODE, HALF, NC, NOBS, U0, true, true>; else return nullptr;
+}
+#define FG_SEP_ENTRY(M, MODE, HALF, NC, NOBS, U0, FOLD) { { M, MODE, HALF, NC, NOBS, U0, FOLD }, k_hmc_sep_steps<M, MODE, HALF, NC, NOBS, U0, FOLD>, fg_sep_ranged_fn<M, MODE, HALF, NC, NOBS, U0, FOLD>(), 0, 0 },
 static FgSepVariant fg_sep_variants[] = { FG_SEP_VARIANTS(FG_SEP_ENTRY) };
 #undef FG_SEP_ENTRY
 
@@ -837,7 +858,9 @@ int fg_hmc_sep_launch(fg_engine *e, int iter0, int n, int welford_on, double *dr
     if (rc != FG_OK) return rc;
     FgSepVariant *v = std::find_if(std::begin(fg_sep_variants), std::end(fg_sep_variants), [&](const FgSepVariant &q) { return q.key == pl.key; });
     if (v == std::end(fg_sep_variants)) return FG_E_UNSUPPORTED;
-    rc = fg_launch(e, v->fn, v->raised, dim3(pl.tiles), dim3(FG_WAVE * pl.W), pl.lds, e->P, e->X, e->H, pl.seg, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
+    // the folded loop without its range test when the host proved the range for this program and h (FG_HMC_SEP_RANGE=0: with it, A/B)
+    const bool ranged = v->fn_ranged && e->H.range != 0 && !fg_switch_is(fg_env_switch("FG_HMC_SEP_RANGE"), 0);
+    rc = fg_launch(e, ranged ? v->fn_ranged : v->fn, ranged ? v->raised_ranged : v->raised, dim3(pl.tiles), dim3(FG_WAVE * pl.W), pl.lds, e->P, e->X, e->H, pl.seg, iter0, n, e->n_warmup, welford_on, draws, first_sample_t, pos_all, info);
     if (rc == FG_OK) e->last_hmc_kernel = pl.name;
     return rc;
 }

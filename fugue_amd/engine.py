@@ -81,7 +81,7 @@ ABI_SYMBOLS = [
     "fg_engine_set_values", "fg_engine_get_values", "fg_engine_values_device", "fg_prior_init", "fg_log_joint", "fg_log_joint_stream",
     "fg_program_sample_discrete_uniform",
     "fg_hmc_config_default", "fg_hmc_init", "fg_hmc_step", "fg_hmc_step_info", "fg_hmc_get_mass", "fg_hmc_run", "fg_hmc_get_stats", "fg_hmc_get_step_sizes",
-    "fg_hmc_get_log_joint", "fg_hmc_set_step_size", "fg_hmc_set_n_leapfrog", "fg_hmc_is_warming_up", "fg_hmc_iterations", "fg_hmc_short_quotient", "fg_hmc_step_recorded",
+    "fg_hmc_get_log_joint", "fg_hmc_set_step_size", "fg_hmc_set_n_leapfrog", "fg_hmc_is_warming_up", "fg_hmc_iterations", "fg_hmc_short_quotient", "fg_hmc_range_proved", "fg_hmc_step_recorded",
     "fg_state_size", "fg_state_export", "fg_state_import", "fg_hmc_grad", "fg_hmc_transition_injected",
     "fg_hmc_find_eps_injected", "fg_mh_init", "fg_mh_step", "fg_mh_set_recording", "fg_mh_run", "fg_mh_get_stats", "fg_mh_get_scales",
     "fg_mh_get_log_weight", "fg_smc_config_default", "fg_smc_run", "fg_smc_prior_particles", "fg_smc_normalize", "fg_smc_ess", "fg_smc_resample", "fg_smc_rejuvenate",
@@ -202,6 +202,7 @@ def lib():
     L.fg_hmc_iterations.restype = C.c_int64
     L.fg_hmc_iterations.argtypes = [vp]
     L.fg_hmc_short_quotient.argtypes = [vp]
+    L.fg_hmc_range_proved.argtypes = [vp]
     L.fg_hmc_step_recorded.argtypes = [vp, C.c_int, C.POINTER(C.c_int64), dp, dp, ip, vp]
     L.fg_state_size.restype = C.c_int64
     L.fg_state_size.argtypes = [vp]
@@ -650,6 +651,10 @@ class Engine:
     def hmc_short_quotient(self) -> bool:
         """Whether k_hmc_sep_steps's sparse trajectories divide by 2h in two instructions (the host proved it exact for this h)."""
         return bool(lib().fg_hmc_short_quotient(self.h))
+
+    def hmc_range_proved(self) -> bool:
+        """Whether the folded loop of those trajectories runs without its range test (the host bounded every numerator for this program and h)."""
+        return bool(lib().fg_hmc_range_proved(self.h))
 
     def hmc_step_recorded(self, chain_ids: Sequence[int], n_leapfrog: int):
         """`HmcSession::step_recorded` for every chain; returns (trajectories [K][L+1][d], Hamiltonians [K][L+1],

@@ -339,6 +339,10 @@ int64_t fg_hmc_iterations(const fg_engine *e);
  * trajectories (k_hmc_sep_steps' folded loop) is exact in two instructions; 0 when the divisor was refused -- the kernels then
  * run without the folded loop -- or no HMC session is initialised.  Results are the same bits either way. */
 int     fg_hmc_short_quotient(const fg_engine *e);
+/* 1 when the host proved, for this session's program and finite_diff_eps, that no finite non-zero numerator of that quotient can
+ * leave the window in which the two instructions are exact (fg_sep_range.h): the folded loop then runs without its range test;
+ * 0 when the bound was refused -- the test stays -- or no HMC session is initialised.  Results are the same bits either way. */
+int     fg_hmc_range_proved(const fg_engine *e);
 /* Which kernel the engine's last fg_hmc_step / fg_hmc_run launch ran, with its waves per 64-chain tile, e.g.
  * "k_hmc_sep_steps W=8" (independent sites: whole trajectories in registers), "k_hmc_lin_steps W=8" (dense regressions:
  * observation-major gradient), "k_hmc_stream_steps W=4" (gradient / score streams), "k_hmc_steps W=1" (interpreter);

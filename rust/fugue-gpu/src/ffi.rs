@@ -142,6 +142,7 @@ extern "C" {
     pub fn fg_hmc_is_warming_up(e: *const fg_engine) -> c_int;
     pub fn fg_hmc_iterations(e: *const fg_engine) -> i64;
     pub fn fg_hmc_short_quotient(e: *const fg_engine) -> c_int;
+    pub fn fg_hmc_range_proved(e: *const fg_engine) -> c_int;
     pub fn fg_hmc_last_kernel(e: *const fg_engine) -> *const c_char;
     pub fn fg_mh_last_kernel(e: *const fg_engine) -> *const c_char;
     // ---- single-site MH (mh.rs:921-1014)
