@@ -23,6 +23,22 @@
 
 static_assert(FG_SEP_WAVE == FG_WAVE, "fg_hmc_sep_plan.h sizes tiles for 64-lane waves");
 
+// k_hmc_sep_steps's argument list as a struct: the kernarg segment holds the arguments in order from offset 0, each at its type's
+// alignment -- the layout of this struct -- so the resident form can read an argument again where it needs it (fg_sep_kernargs) instead of
+// holding it in a register for the whole launch.  Keep the two lists the same; the asserts pin what the layout rests on.
+struct FgSepArgs {
+    FgProgramDev P; FgChainCtx X; FgHmcDev H; FgSegSep seg;
+    int iter0, n_steps, n_warmup, welford_on;
+    double *draws; int first_sample_t;
+    double *pos_all, *info;
+};
+static_assert(alignof(FgProgramDev) == 8 && alignof(FgChainCtx) == 8 && alignof(FgHmcDev) == 8 && alignof(FgSegSep) == 4, "kernarg layout of k_hmc_sep_steps");
+static_assert(offsetof(FgSepArgs, X) == sizeof(FgProgramDev) && offsetof(FgSepArgs, H) == offsetof(FgSepArgs, X) + sizeof(FgChainCtx) &&
+              offsetof(FgSepArgs, seg) == offsetof(FgSepArgs, H) + sizeof(FgHmcDev) && offsetof(FgSepArgs, iter0) == offsetof(FgSepArgs, seg) + sizeof(FgSegSep) &&
+              offsetof(FgSepArgs, welford_on) == offsetof(FgSepArgs, iter0) + 12 && offsetof(FgSepArgs, draws) == ((offsetof(FgSepArgs, welford_on) + 4 + 7) & ~(size_t)7) &&
+              offsetof(FgSepArgs, first_sample_t) == offsetof(FgSepArgs, draws) + 8 && offsetof(FgSepArgs, pos_all) == offsetof(FgSepArgs, draws) + 16 &&
+              offsetof(FgSepArgs, info) == offsetof(FgSepArgs, draws) + 24, "kernarg layout of k_hmc_sep_steps: every argument at the next multiple of its alignment");
+
 // FG_HMC_PROF (experiment builds, tools/prof_hmc_phases.py): cycles tile 0's waves spend in each part of a transition
 #ifdef FG_HMC_PROF
 __device__ unsigned long long fg_hmc_prof[FG_SEP_WMAX][8];
@@ -40,6 +56,17 @@ __device__ __forceinline__ fg_u32x8 fg_sep_ld8(const FG_AS4 char *p) { return *(
 __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const FG_AS4 char *p) { return *(const FG_AS4 fg_u32x4 *)p; }
 __device__ __forceinline__ fg_u32x8 fg_sep_ld8(const char *p) { return *(const fg_u32x8 *)p; }
 __device__ __forceinline__ fg_u32x4 fg_sep_ld4(const char *p) { return *(const fg_u32x4 *)p; }
+// RES: a phase of the transition reads its uniform scalars again from the kernarg segment (scalar loads at the phase's head: no VALU slot).
+// The empty asm makes the pointer a new value each time, so nothing read through it can be hoisted out of the transition loop -- where
+// it would live for the launch, one of ~120 SGPRs too many, parked in VGPR lanes and read back (v_readlane) at every use.
+__device__ __forceinline__ const FG_AS4 FgSepArgs *fg_sep_kernargs() {
+    const FG_AS4 FgSepArgs *ka = (const FG_AS4 FgSepArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return ka;
+}
+// a wave-uniform integer the compiler has to keep as ONE scalar: a condition on it is s_cmp + s_cbranch where it is tested, not a 64-bit
+// lane mask formed ahead of the loop (spilled as a pair, tested through v_cndmask / v_cmp)
+__device__ __forceinline__ int fg_sep_scalar(int v) { asm volatile("" : "+s"(v)); return v; }
 #define FG_SEP_LOAD(k) \
     const fg_u32x8 a##k = fg_sep_ld8(rb + 64 * k); \
     const fg_u32x4 b##k = fg_sep_ld4(rb + 64 * k + 32);
@@ -380,6 +407,11 @@ __device__ __forceinline__ bool fg_dense_trajectory(const FgProgramDev &P, const
 // wave 0 adds and decides, the other waves draw the Box-Muller pairs of their next transition.  The arithmetic per coordinate is
 // fg_sep_trajectory's for the shape NC = 0 dispatches to: every result is bit-identical to NC = 0.  (The records themselves are still
 // loaded per trajectory: held for four coordinates they spill SGPRs into the leapfrog loop.)
+// The resident form's uniform scalars live by PHASE of a transition -- (a) the wave's trajectories | barrier | (b) wave 0's sums and accept,
+// the other waves' pre-draw | barrier | (c) the commit -- and at the launch's end: each phase reads what it needs again from the kernarg
+// segment (fg_sep_kernargs: scalar loads, no VALU slot) and tests its uniform conditions as scalar integers (fg_sep_scalar).  Held for the
+// launch, as the other forms hold them, they are ~120 SGPRs too many, parked in VGPR lanes and read back at every use: 113 v_readlane /
+// v_writelane per wave and transition of the headline instantiation, none now.
 template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false, bool FOLD = false,
           bool RANGED = false /* FOLD without the range test of its quotient (fg_sep_range.h): no part of the plan's key, the launcher's choice */>
 __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgProgramDev P, FgChainCtx X, FgHmcDev H, FgSegSep seg, int iter0, int n_steps,
@@ -407,7 +439,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
     // committed value row in HBM (L2-resident: d * C * 8 B split over 8 XCDs) and parks its endpoint in the proposal rows
     // (H.p0_scratch) until the accept decision -- 32 rows less per tile, which is what lets TWO tiles share a CU's 160 KB at
     // d = 32, so one tile's in-order sums / accept step overlap the other tile's trajectories.
-    const int srows = P.n_sep_free > 0 ? P.n_slots : 0;
+    const int srows = RES ? 0 : (P.n_sep_free > 0 ? P.n_slots : 0);   // (the plan gives the resident form to programs without such statements only)
     double *slots = lds + lane;
     // DENSE: (site values) | score terms | exchange | positions | momenta -- q and p live in LDS rows between gradients, and at the
     // end of a trajectory the same rows take the two kinetic-energy terms of each coordinate (p0's is formed again from its random
@@ -506,35 +538,47 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         int lnl = lane;
         long long cl = c;
         if (RES) { asm volatile("" : "+v"(lnl)); asm volatile("" : "+v"(cl)); }
-        double *termsR = RES ? lds + (long long)(srows + 2 * d) * tw + lnl : terms;
-        double *kin0R = RES ? lds + (long long)srows * tw + lnl : kin0;
-        double *kin1R = RES ? kin0R + (long long)d * tw : kin1;
-        if (RES) {
+        int prio_now = prio_turns ? -1 : 0;                          // seg.c[FG_SEP_WMAX] == -1: priority turns
+        if constexpr (RES) {
+            // phase (a)'s scalar state, read here and dead at the barrier (h, c_hi, c_lo, L, d shadow the launch's: the non-resident forms' names)
+            const FG_AS4 FgSepArgs *ka = fg_sep_kernargs();
+            const double h = ka->H.h, c_hi = ka->H.div2_hi, c_lo = ka->H.div2_lo;
+            const int L = ka->H.L, d = ka->P.d;
+            prio_now = ka->seg.c[FG_SEP_WMAX];
+            const FgSepRec *sep = ka->P.sep;
+            const unsigned long long seed = ka->X.seed;
+            const uint32_t sk0 = (uint32_t)seed, sk1 = (uint32_t)(seed >> 32), iter = (uint32_t)(ka->iter0 + t);
+            const int pre = fg_sep_scalar((wv != 0 && t > 0) ? ka->seg.predraw : 0);   // zn holds this transition's pairs (drawn behind wave 0, below)
+            const int nown_a = fg_sep_scalar(nown), k0_a = fg_sep_scalar(k0), turn = fg_sep_scalar((wv >> 2) & 1);
+            // the wave's rows of the two kinetic-term blocks: one base each, the coordinates at immediate offsets
+            double *termsR = lds + (long long)(2 * d) * tw + lnl;
+            double *kin0R = lds + (long long)k0_a * tw + lnl;
+            double *kin1R = kin0R + (long long)d * tw;
 #pragma unroll
             for (int j = 0; j < NCX; ++j) {
-                if (j >= nown) break;
-                const int i = k0 + j;
-                if (prio_turns) { if ((j ^ (wv >> 2)) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+                if (j >= nown_a) break;
+                if (fg_sep_scalar(prio_now) == -1) { if ((j ^ turn) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
                 double z;
-                if (!(j & 1)) { const FgD2 zz = have_pre ? zn[j >> 1] : fg_cold_normal_pair(sk0, sk1, gchain, (uint32_t)(i >> 1), (uint32_t)iter, FG_RNG_HMC); z = zz.a; zb = zz.b; }
+                if (!(j & 1)) { const FgD2 zz = pre ? zn[j >> 1] : fg_cold_normal_pair(sk0, sk1, gchain, (uint32_t)((k0_a + j) >> 1), iter, FG_RNG_HMC); z = zz.a; zb = zz.b; }
                 else z = zb;
                 double p = MASS ? z * msr[j] : z;
                 const double mii = mir[j];
-                kin0R[i * tw] = MASS ? p * p * mii : p * p;
+                kin0R[j * tw] = MASS ? p * p * mii : p * p;
                 double q = qc[j];
                 const double emi = MASS ? e * mii : e;
                 const double q0 = q, p0 = p;
-                const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(P.sep + roff[j]);
-                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD, const FG_AS4 char *, RANGED>(rb, q, p, emi, hk, L, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo);
+                const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(sep + roff[j]);
+                const int Lj = fg_sep_scalar(L);                         // (else L > 1, the peeled loop's test, is one mask for the four trajectories)
+                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD, const FG_AS4 char *, RANGED>(rb, q, p, emi, hk, Lj, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo);
                 if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                     // (inline, not fg_sep_trajectory_checked: no call.  Its generic record mix computes the same bits for this shape:
                     // every record is POW2 -- (x - mu) * (1 / sigma) -- and a U0 record is exactly N(0, 1), see FG_SEP_LP_U)
                     q = q0; p = p0;
                     FG_SEP_2H(th, rc)
-                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R>(rb, q, p, emi, hk, L, h, th, rc, termsR, tw, NOBS_R) || bad;
+                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R>(rb, q, p, emi, hk, Lj, h, th, rc, termsR, tw, NOBS_R) || bad;
                 }
                 qpr[j] = q;                                              // the proposal
-                kin1R[i * tw] = MASS ? p * p * mii : p * p;
+                kin1R[j * tw] = MASS ? p * p * mii : p * p;
             }
         } else if (DFAST) {
             const int own[4] = { seg.own[wv][0], seg.own[wv][1], seg.own[wv][2], seg.own[wv][3] };
@@ -697,7 +741,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             if (on) kin1[ci * tw] = MASS ? p * p * mii : p * p;
         }
         if (bad) atomicOr((unsigned long long *)(xch + 2 * tw), 1ull);
-        if (prio_turns) { if (wv == 0) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0); }   // wave 0's sums, accept and dual averaging are the tile's path
+        if (prio_now == -1) { if (wv == 0) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0); }   // wave 0's sums, accept and dual averaging are the tile's path
         FG_PROF_T(0)
         __syncthreads();                                         // every coordinate's endpoint and terms
         FG_PROF_T(1)
@@ -705,23 +749,38 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         // log_likelihood in program order (score_full, hmc.rs:283-299).  A tile with a CU to itself (small chain counts: nothing else
         // hides wave 0's serial phase) adds them on four waves, a fifth draws the accept uniform; wave 0 keeps the first sum and picks the
         // others up behind a barrier -- the same additions in the same order either way.
+        // RES, phase (b): its scalars from the kernarg segment again (FG_SEP_ARG: the resident form's read, the other forms' launch-long value)
+#define FG_SEP_ARG(kp, field, plain) (RES ? (kp)->field : (plain))
+        const FG_AS4 FgSepArgs *kb = RES ? fg_sep_kernargs() : nullptr;
+        const int d_b = FG_SEP_ARG(kb, P.d, d), n_pri_b = FG_SEP_ARG(kb, P.n_prior_terms, n_pri), n_s_b = FG_SEP_ARG(kb, P.n_sstream, n_s);
+        const int n_steps_b = FG_SEP_ARG(kb, n_steps, n_steps), n_warmup_b = FG_SEP_ARG(kb, n_warmup, n_warmup), iter_b = RES ? kb->iter0 + t : iter;
+        const uint32_t sk0_b = RES ? (uint32_t)kb->X.seed : sk0, sk1_b = RES ? (uint32_t)(kb->X.seed >> 32) : sk1;
+        const int prio_b = FG_SEP_ARG(kb, seg.c[FG_SEP_WMAX], prio_now);
         const int W = (int)(blockDim.x >> 6);
-        const bool sum4 = (HALF != 0 || RES) && seg.sum4 != 0 && W >= 4;        // (compile-time off for plain 64-chain tiles: their instantiation keeps its registers; FG_HMC_SUM4=1 reaches the resident form)
+        // (compile-time off for plain 64-chain tiles: their instantiation keeps its registers; FG_HMC_SUM4=1 reaches the resident form)
+        // RES: the plan's flag (0 / 1) times W, ONE integer compared where it is tested (a bool made an integer is a v_cndmask, and the
+        // compiler knows a sign bit shifted down for the comparison it is)
+        const bool sum4_plain = HALF != 0 && seg.sum4 != 0 && W >= 4;
+        const int sum4_w = RES ? kb->seg.sum4 * W : 0;
+#define FG_SEP_S(x) (RES ? fg_sep_scalar(x) : (x))
+#define FG_SEP_SUM4 (RES ? fg_sep_scalar(sum4_w) >= 4 : sum4_plain)
         double s0 = 0.0;
-        if (sum4) {
-            if (wv == 0) s0 = fg_inorder_sum1(kin0, d, tw);
-            else if (wv == 1) xch[3 * tw] = fg_inorder_sum1(kin1, d, tw);
-            else if (wv == 2) xch[4 * tw] = fg_inorder_sum1(termsE, n_pri, tw);
-            else if (wv == 3) xch[5 * tw] = fg_inorder_sum1(termsE + (long long)n_pri * tw, n_s - n_pri, tw);
-            if (wv == (W > 4 ? 4 : 3)) xch[6 * tw] = fg_cold_u01_pair(sk0, sk1, gchain, (uint32_t)((d + 1) >> 1), (uint32_t)iter, FG_RNG_HMC).a;
+        if (FG_SEP_SUM4) {
+            if (wv == 0) s0 = fg_inorder_sum1(kin0, d_b, tw);
+            else if (wv == 1) xch[3 * tw] = fg_inorder_sum1(kin1, d_b, tw);
+            else if (wv == 2) xch[4 * tw] = fg_inorder_sum1(termsE, n_pri_b, tw);
+            else if (wv == 3) xch[5 * tw] = fg_inorder_sum1(termsE + (long long)n_pri_b * tw, n_s_b - n_pri_b, tw);
+            if (wv == (W > 4 ? 4 : 3)) xch[6 * tw] = fg_cold_u01_pair(sk0_b, sk1_b, gchain, (uint32_t)((d_b + 1) >> 1), (uint32_t)iter_b, FG_RNG_HMC).a;
             __syncthreads();
         }
         have_pre = false;
-        if (RES && seg.predraw && wv != 0 && t + 1 < n_steps) {          // the next transition's momenta, behind wave 0
+        if constexpr (RES) {                                           // the next transition's momenta, behind wave 0 (phase (a) of the next transition knows by seg.predraw, wv and t that zn holds them)
+            if (fg_sep_scalar((wv != 0 && t + 1 < n_steps_b) ? kb->seg.predraw : 0)) {
+                const int nown_b = fg_sep_scalar(nown);
 #pragma unroll
-            for (int jp = 0; jp < (NCX + 1) / 2; ++jp)
-                if (2 * jp < nown) zn[jp] = fg_cold_normal_pair(sk0, sk1, gchain, (uint32_t)(k0 >> 1) + (uint32_t)jp, (uint32_t)(iter + 1), FG_RNG_HMC);
-            have_pre = true;
+                for (int jp = 0; jp < (NCX + 1) / 2; ++jp)
+                    if (2 * jp < nown_b) zn[jp] = fg_cold_normal_pair(sk0_b, sk1_b, gchain, (uint32_t)(k0 >> 1) + (uint32_t)jp, (uint32_t)(iter_b + 1), FG_RNG_HMC);
+            }
         }
         if (HALF != 0 && seg.sum4 != 0 && wv != 0 && t + 1 < n_steps && k0 < k1 && !(k0 & 1)) {
             zpre = fg_cold_normal_pair(sk0, sk1, gchain, first_block, (uint32_t)(iter + 1), FG_RNG_HMC);
@@ -729,10 +788,10 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
         }
         if (wv == 0) {
             double s1, pri, lik;
-            if (sum4) { s1 = xch[3 * tw]; pri = xch[4 * tw]; lik = xch[5 * tw]; }
+            if (FG_SEP_SUM4) { s1 = xch[3 * tw]; pri = xch[4 * tw]; lik = xch[5 * tw]; }
             else {
-                fg_inorder_sums2<8>(kin0, d, kin1, d, tw, s0, s1);
-                fg_inorder_sums2<8>(termsE, n_pri, termsE + (long long)n_pri * tw, n_s - n_pri, tw, pri, lik);
+                fg_inorder_sums2<8>(kin0, d_b, kin1, d_b, tw, s0, s1);
+                fg_inorder_sums2<8>(termsE, n_pri_b, termsE + (long long)n_pri_b * tw, n_s_b - n_pri_b, tw, pri, lik);
             }
             const double h0 = -lj + 0.5 * s0;                        // hmc.rs:442-443
             const double lj_new = pri + lik + 0.0;                   // total_log_weight (log_factors = 0: no factor statement has a record)
@@ -742,66 +801,77 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             if (!div) {
                 const double h_new = -lj_new + 0.5 * s1;
                 ap = fg_cold_accept_prob(h0, h_new);             // hmc.rs:460
-                const double u = sum4 ? xch[6 * tw] : fg_cold_u01_pair(sk0, sk1, gchain, (uint32_t)((d + 1) >> 1), (uint32_t)iter, FG_RNG_HMC).a;
+                const double u = FG_SEP_SUM4 ? xch[6 * tw] : fg_cold_u01_pair(sk0_b, sk1_b, gchain, (uint32_t)((d_b + 1) >> 1), (uint32_t)iter_b, FG_RNG_HMC).a;
                 acc = u < ap;                                    // hmc.rs:461
             }
             if (acc) lj = lj_new;
             xch[tw] = acc ? 1.0 : 0.0;
             asum += ap; ndiv += div ? 1ull : 0ull;
-            if (live0 && info) {                                 // HmcStepInfo: hmc.rs:587-602
-                double *r = info + (long long)t * 4 * X.C + c;
-                r[0] = acc ? 1.0 : 0.0; r[X.C] = div ? 1.0 : 0.0; r[2 * X.C] = ap; r[3 * X.C] = e_cur;
+            double *const info_b = FG_SEP_ARG(kb, info, info);
+            if (live0 && info_b) {                               // HmcStepInfo: hmc.rs:587-602
+                const long long C_b = FG_SEP_ARG(kb, X.C, X.C);
+                double *r = info_b + (long long)t * 4 * C_b + c;
+                r[0] = acc ? 1.0 : 0.0; r[C_b] = div ? 1.0 : 0.0; r[2 * C_b] = ap; r[3 * C_b] = e_cur;
             }
-            if (warming) {                                       // DualAveraging::update: hmc.rs:168-178
+            if (iter_b < n_warmup_b) {                           // DualAveraging::update: hmc.rs:168-178
                 da_m += 1ull;
-                const FgD3 r = fg_cold_da_update(da_hbar, da_leb, (double)da_m, da_mu, H.target, ap);
+                const FgD3 r = fg_cold_da_update(da_hbar, da_leb, (double)da_m, da_mu, FG_SEP_ARG(kb, H.target, H.target), ap);
                 eps = r.a; da_hbar = r.b; da_leb = r.c;
             }
             // the next transition's step size
-            if (iter + 1 < n_warmup) e_cur = eps;
+            if (iter_b + 1 < n_warmup_b) e_cur = eps;
             else {                                               // frozen_or_current: hmc.rs:789-798
                 if (frozen == frozen) e_cur = frozen;
-                else if (n_warmup > 0) e_cur = fg_cold_exp(da_leb);
+                else if (n_warmup_b > 0) e_cur = fg_cold_exp(da_leb);
                 else e_cur = eps;
-                if (t + 1 < n_steps) frozen = e_cur;
+                if (t + 1 < n_steps_b) frozen = e_cur;
             }
-            if (t + 1 < n_steps) xch[0] = e_cur;
+            if (t + 1 < n_steps_b) xch[0] = e_cur;
             xch[2 * tw] = 0.0;
         }
         FG_PROF_T(2)
-        if (prio_turns) __builtin_amdgcn_s_setprio(0);
+        if (prio_b == -1) __builtin_amdgcn_s_setprio(0);
         __syncthreads();
         FG_PROF_T(3)
+        // RES, phase (c): the commit's scalars
+        const FG_AS4 FgSepArgs *kc = RES ? fg_sep_kernargs() : nullptr;
+        const long long C_c = FG_SEP_ARG(kc, X.C, X.C);
+        const int d_c = FG_SEP_ARG(kc, P.d, d), first_c = FG_SEP_ARG(kc, first_sample_t, first_sample_t);
+        double *const draws_c = FG_SEP_ARG(kc, draws, draws), *const pos_c = FG_SEP_ARG(kc, pos_all, pos_all);
+        const int left_c = RES ? kc->n_warmup - (kc->iter0 + t) : 0, welf_c = FG_SEP_ARG(kc, welford_on, welford_on);   // (RES: warmup transitions left, this one included)
+#define FG_SEP_WARM_C (RES ? fg_sep_scalar(left_c) > 0 : warming)
         const bool acc = xch[tw] != 0.0;
         unsigned long long wn = 0;
         double wnd = 0.0;                                         // (double)wn, Welford::push's divisor
-        if (warming && welford_on) {                              // every wave reads the old count before wave 0 bumps it below
-            wn = H.w_n[c] + 1ull;
+        if (FG_SEP_WARM_C && FG_SEP_S(welf_c)) {               // every wave reads the old count before wave 0 bumps it below
+            wn = FG_SEP_ARG(kc, H.w_n, H.w_n)[c] + 1ull;
             wnd = (double)wn;
             asm volatile("" : "+v"(wnd));                         // load and conversion stay behind the uniform branch: the sampling phase issues neither
         }
         // the committed value x of coordinate i: draws, positions, Welford (cc: the lane's chain)
         auto commit = [&](int i, double x, bool on, long long cc) {
-            if (live && on && pos_all) pos_all[((long long)t * d + i) * X.C + cc] = x;
-            if (warming) {
-                if (welford_on) {                                 // Welford::push: hmc.rs:202-211
-                    const long long gi = (long long)i * X.C + cc;
+            if (live && on && pos_c) pos_c[((long long)t * d_c + i) * C_c + cc] = x;
+            if (FG_SEP_WARM_C) {
+                if (FG_SEP_S(welf_c)) {                                     // Welford::push: hmc.rs:202-211
+                    double *const w_mean = FG_SEP_ARG(kc, H.w_mean, H.w_mean), *const w_m2 = FG_SEP_ARG(kc, H.w_m2, H.w_m2);
+                    const long long gi = (long long)i * C_c + cc;
                     const double n = wnd;
-                    double mean = H.w_mean[gi];
+                    double mean = w_mean[gi];
                     const double delta = x - mean;
                     mean += delta / n;
                     const double delta2 = x - mean;
-                    if (live && on) { H.w_mean[gi] = mean; H.w_m2[gi] += delta * delta2; }
+                    if (live && on) { w_mean[gi] = mean; w_m2[gi] += delta * delta2; }
                 }
-            } else if (draws && live && on) draws[((long long)(t - first_sample_t) * d + i) * X.C + cc] = x;   // hmc.rs:577-582
+            } else if (draws_c && live && on) draws_c[((long long)(t - first_c) * d_c + i) * C_c + cc] = x;   // hmc.rs:577-582
         };
         if (RES) {                                                  // commit or roll back: a select (the value rows: at the launch's end)
+            const int nown_c = fg_sep_scalar(nown), k0_c = fg_sep_scalar(k0);
 #pragma unroll
             for (int j = 0; j < NCX; ++j) {
-                if (j >= nown) break;
+                if (j >= nown_c) break;
                 const double x = acc ? qpr[j] : qc[j];
                 qc[j] = x;
-                commit(k0 + j, x, true, cl);
+                commit(k0_c + j, x, true, cl);
             }
         } else
         for (int jo = 0; jo < (DFAST ? seg.n_own[wv] : k1 - k0); jo += 1 << HALF) {   // commit or roll back the own f64 sites
@@ -813,24 +883,30 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             if (acc && live && on) X.values[g] = fg_as_i64(x);
             commit(i, x, on, c);
         }
-        if (warming && welford_on) {
+        if (FG_SEP_WARM_C && FG_SEP_S(welf_c)) {
             __syncthreads();                                      // all waves hold the old count
-            if (wv == 0 && live0) H.w_n[c] = wn;
+            if (wv == 0 && live0) FG_SEP_ARG(kc, H.w_n, H.w_n)[c] = wn;
         }
         FG_PROF_T(4)
     }
+#undef FG_SEP_ARG
+#undef FG_SEP_S
+#undef FG_SEP_SUM4
+#undef FG_SEP_WARM_C
 #ifdef FG_HMC_PROF
     if (blockIdx.x == 0 && lane == 0) for (int q = 0; q < 8; ++q) fg_hmc_prof[wv][q] = prof_[q];
 #endif
+    const FG_AS4 FgSepArgs *ke = RES ? fg_sep_kernargs() : nullptr;   // RES: the value rows and wave 0's state through the kernarg segment, like a phase
     if (RES && live) {
 #pragma unroll
         for (int j = 0; j < NCX; ++j)
-            if (j < nown) X.values[(long long)P.f64_site[k0 + j] * X.C + c] = fg_as_i64(qc[j]);
+            if (j < nown) ke->X.values[(long long)ke->P.f64_site[k0 + j] * ke->X.C + c] = fg_as_i64(qc[j]);
     }
     if (wv == 0 && live0) {
-        H.lj[c] = lj; H.eps[c] = eps; H.frozen[c] = frozen;
-        H.da_mu[c] = da_mu; H.da_leb[c] = da_leb; H.da_hbar[c] = da_hbar; H.da_m[c] = da_m;
-        H.alpha_sum[c] += asum; H.n_div[c] += ndiv;
+        const FgHmcDev &Hs = RES ? *(const FgHmcDev *)&ke->H : H;
+        Hs.lj[c] = lj; Hs.eps[c] = eps; Hs.frozen[c] = frozen;
+        Hs.da_mu[c] = da_mu; Hs.da_leb[c] = da_leb; Hs.da_hbar[c] = da_hbar; Hs.da_m[c] = da_m;
+        Hs.alpha_sum[c] += asum; Hs.n_div[c] += ndiv;
     }
 }
 
