@@ -154,9 +154,14 @@ template <> struct FgSepScalarRb<const FG_AS4 char *> { static constexpr bool va
 // which the caller's test sends through the CHECK instance as before.  A program whose bound is refused runs RANGED = false.
 // The loop is peeled for a run-time L >= 1: first step (half kick, drift), L - 1 middle steps with ONE back-branch, last step (gradient,
 // half kick) -- the same f64 operations in the same order as one loop with uniform branches on the step index.
-template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, bool FOLD = false, typename RB = const FG_AS4 char *, bool RANGED = false>
+// CARRY (the resident forms, see k_hmc_sep_steps): what *g_io is to the trajectory.  0: nothing (g_io is not read: every other caller).
+// 1: the force component at q_io on entry -- the first step takes it instead of calling grad(), L gradients instead of L + 1 -- and the
+// last step's g on return.  2: all L + 1 gradients are computed here as with 0, and the last one is handed back (the checked re-run).
+// 3: the gradient at q_io alone, no step and no term (the launch's first gradient, with CHECK: the reference's bits for every record mix).
+// The f64 operations that follow a gradient are the same in every mode: kick = hk * g, p = p + kick, drift.
+template <int NOBS, bool P2, bool CHECK, bool AN = false, bool U0 = false, bool FOLD = false, typename RB = const FG_AS4 char *, bool RANGED = false, int CARRY = 0>
 __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p_io, double emi, double hk, int L, double h, double two_h,
-                                                  double rcp_2h, double *terms, int tw, int nobs_rt, double c_hi = 0.0, double c_lo = 0.0) {
+                                                  double rcp_2h, double *terms, int tw, int nobs_rt, double c_hi = 0.0, double c_lo = 0.0, double *g_io = nullptr) {
 #define FG_SEP_HAS(k) (NOBS >= 0 ? NOBS >= (k) : nobs_rt >= (k))
     FG_SEP_LOAD(0) FG_SEP_LOAD(1) FG_SEP_LOAD(2) FG_SEP_LOAD(3)
     double q = q_io, p = p_io;
@@ -237,14 +242,17 @@ __device__ __forceinline__ bool fg_sep_trajectory(RB rb, double &q_io, double &p
     };
     // first step: half kick, drift | L - 1 middle steps: gradient, the trailing kick of one step and the leading kick of the next (the
     // empty asm keeps them two additions), drift | last step: gradient, half kick.  L >= 1 (fg_internal_hmc_set_cfg).
-    { const double kick = hk * grad(); p = p + kick; asm volatile(""); q = q + emi * p; }       // hmc.rs:389, :391-393
+    if constexpr (CARRY == 3) { *g_io = grad(); return bad; }
+    double g_first = 0.0;
+    if constexpr (CARRY == 1) g_first = *g_io; else g_first = grad();
+    { const double kick = hk * g_first; p = p + kick; asm volatile(""); q = q + emi * p; }       // hmc.rs:389, :391-393
     for (int gs = 1; gs < L; ++gs) {
         const double kick = hk * grad();
         p = p + kick;                                            // hmc.rs:400
         asm volatile(""); p = p + kick;                          // hmc.rs:389
         asm volatile(""); q = q + emi * p;                       // hmc.rs:391-393
     }
-    { const double kick = hk * grad(); p = p + kick; }           // hmc.rs:400
+    { const double g_last = grad(); if constexpr (CARRY != 0) *g_io = g_last; const double kick = hk * g_last; p = p + kick; }   // hmc.rs:400
     if (!CHECK && FOLD && !RANGED && nrange >= 0xde000000u) p = __builtin_nan("");   // some quotient out of fg_div_const's range: the checked re-run
     if (U0) { double lp = FG_SEP_LP_U(q); FG_SEP_NAN_NEG_INF(q, lp) terms[a0[1] * tw] = lp; }
     else FG_SEP_TERM(0)
@@ -412,6 +420,27 @@ __device__ __forceinline__ bool fg_dense_trajectory(const FgProgramDev &P, const
 // segment (fg_sep_kernargs: scalar loads, no VALU slot) and tests its uniform conditions as scalar integers (fg_sep_scalar).  Held for the
 // launch, as the other forms hold them, they are ~120 SGPRs too many, parked in VGPR lanes and read back at every use: 113 v_readlane /
 // v_writelane per wave and transition of the headline instantiation, none now.
+// The resident form CARRIES the start gradient (fg_sep_carries: the instantiations whose registers hold it without a new spill).  The first
+// of a trajectory's L + 1 gradients is taken at the committed position, where one has been computed before -- it depends on q, h and the
+// records only, not on step size, mass or momentum.  Beside qc[] / qpr[] a wave keeps gc[] / gpr[], the gradient at the committed position
+// and at the proposal, for the launch and nowhere else: phase (a) passes gc[j] in and takes the trajectory's last gradient as gpr[j], the
+// commit selects g as it selects q.  INVARIANT: gc[j] is always the reference's bits of the gradient at qc[j].  It gets there (1) from the
+// launch's prologue, in the checked arithmetic (unfused densities, fg_div_const with its true-division fallback: right for every record
+// mix and every n, no proof needed); (2) from a checked re-run, whose last gradient replaces the fast form's (required: the re-run can end
+// finite where the fast form did not -- z^2 in [2^1024, 2^1025) of FG_SEP_LPF, an out-of-range n of the tested twin); (3) from a fast
+// trajectory whose endpoint momentum was finite, which is what already proves every g of it, the last included, equal to the checked
+// form's.  A divergent transition is never accepted, so a non-finite proposal gradient is never committed; a non-finite gc[j] (the
+// prologue's, at a q where the force is not finite) makes the momentum non-finite and the trajectory goes through the re-run, which
+// computes its own start gradient -- as a non-finite first gradient does without the carry.  Nothing is read from or written to the engine:
+// a launch of n transitions runs 16 n + 1 gradients per coordinate at L = 16.
+// Which instantiations: those whose compiled form has no more spilled VGPRs and no more scratch than without the carry, and no scratch
+// access in a leapfrog loop (profiles/round12_sep_carry_resource_usage.txt, tools/isa_sep_carry.py).  Every NC = 2 form (112 .. 123 VGPRs)
+// and the NC = 4 forms without a mass (128 VGPRs, nothing spilled) -- but the unfolded one with three observations, which spills 2 VGPRs
+// with it, and the NC = 4 forms with a mass, which stand at 128 VGPRs with 2 spilled as they are and have no room for 16 more: they keep the code they had.
+constexpr bool fg_sep_carries(bool MASS, int NC, int NOBS, bool U0, bool FOLD, bool RANGED) {
+    (void)U0; (void)RANGED;
+    return NC > 0 && !(NC == 4 && (MASS || (NOBS == 3 && !FOLD)));
+}
 template <bool MASS, int MODE, int HALF = 0 /* 1: half tiles, 2: quarter tiles */, int NC = 0, int NOBS_R = 0, bool U0_R = false, bool FOLD = false,
           bool RANGED = false /* FOLD without the range test of its quotient (fg_sep_range.h): no part of the plan's key, the launcher's choice */>
 __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgProgramDev P, FgChainCtx X, FgHmcDev H, FgSegSep seg, int iter0, int n_steps,
@@ -479,6 +508,25 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
             qpr[j] = qc[j];
             mir[j] = MASS ? H.m_inv[(long long)i * X.C + c] : 1.0;
             msr[j] = MASS ? H.mass_sqrt[(long long)i * X.C + c] : 1.0;
+        }
+    }
+    // CARRIES: the gradient at the committed position and at the proposal.  The launch's first: once per own coordinate, checked arithmetic
+    constexpr bool CARRIES = fg_sep_carries(MASS, NC, NOBS_R, U0_R, FOLD, RANGED);
+    constexpr int NCG = CARRIES ? NC : 1;
+    double gc[NCG], gpr[NCG];
+    if constexpr (CARRIES) {
+        const FG_AS4 FgSepArgs *kp = fg_sep_kernargs();
+        const double h = kp->H.h;
+        const FgSepRec *sep = kp->P.sep;
+        const int nown_p = fg_sep_scalar(nown);
+        FG_SEP_2H(th, rc)
+#pragma unroll
+        for (int j = 0; j < NCG; ++j) {
+            gc[j] = 0.0; gpr[j] = 0.0;
+            if (j >= nown_p) continue;
+            double q = qc[j], p = 0.0;
+            const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(sep + roff[j]);
+            fg_sep_trajectory<NOBS_R, true, true, false, U0_R, false, const FG_AS4 char *, false, 3>(rb, q, p, 0.0, 0.0, 0, h, th, rc, nullptr, tw, NOBS_R, 0.0, 0.0, &gc[j]);
         }
     }
     // wave 0 owns the per-chain sampler state
@@ -569,14 +617,18 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                 const double q0 = q, p0 = p;
                 const FG_AS4 char *rb = (const FG_AS4 char *)(uintptr_t)(sep + roff[j]);
                 const int Lj = fg_sep_scalar(L);                         // (else L > 1, the peeled loop's test, is one mask for the four trajectories)
-                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD, const FG_AS4 char *, RANGED>(rb, q, p, emi, hk, Lj, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo);
+                double g = 0.0;
+                if constexpr (CARRIES) g = gc[j];                        // CARRIES: in, the gradient at qc[j]; out, the trajectory's last
+                fg_sep_trajectory<NOBS_R, true, false, false, U0_R, FOLD, const FG_AS4 char *, RANGED, CARRIES ? 1 : 0>(rb, q, p, emi, hk, Lj, h, two_h, rcp_2h, termsR, tw, NOBS_R, c_hi, c_lo, &g);
                 if (__builtin_expect(__any(!fg_finite(p)), 0)) {       // a force component may have been non-finite (FOLD: or n out of range): the exact per-step test
                     // (inline, not fg_sep_trajectory_checked: no call.  Its generic record mix computes the same bits for this shape:
                     // every record is POW2 -- (x - mu) * (1 / sigma) -- and a U0 record is exactly N(0, 1), see FG_SEP_LP_U)
+                    // CARRIES: it starts from q0, p0 and its own start gradient, and its last gradient replaces the fast form's
                     q = q0; p = p0;
                     FG_SEP_2H(th, rc)
-                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R>(rb, q, p, emi, hk, Lj, h, th, rc, termsR, tw, NOBS_R) || bad;
+                    bad = fg_sep_trajectory<NOBS_R, true, true, false, U0_R, false, const FG_AS4 char *, false, CARRIES ? 2 : 0>(rb, q, p, emi, hk, Lj, h, th, rc, termsR, tw, NOBS_R, 0.0, 0.0, &g) || bad;
                 }
+                if constexpr (CARRIES) gpr[j] = g;                                 // the gradient at the proposal
                 qpr[j] = q;                                              // the proposal
                 kin1R[j * tw] = MASS ? p * p * mii : p * p;
             }
@@ -871,6 +923,7 @@ __global__ __launch_bounds__(FG_WAVE * FG_SEP_WMAX, 4) void k_hmc_sep_steps(FgPr
                 if (j >= nown_c) break;
                 const double x = acc ? qpr[j] : qc[j];
                 qc[j] = x;
+                if constexpr (CARRIES) gc[j] = acc ? gpr[j] : gc[j];               // the gradient goes where the position goes
                 commit(k0_c + j, x, true, cl);
             }
         } else
