@@ -961,6 +961,16 @@ int fg_program_observe_dist(const fg_program *p, int k) {
     const FgStmt *s = observe_stmt(p, k);
     return s ? s->dist : FG_ERR_ADDRESS_NOT_FOUND;
 }
+// the observed value where the model states it (a literal or a data element, folded to a constant by parse): the `observations` a
+// workflow compares its replicates with (end_to_end_workflows.rs:650-745)
+int fg_program_observe_value(const fg_program *p, int k, double *out) {
+    NEED_FINAL(p);
+    const FgStmt *s = observe_stmt(p, k);
+    if (!s || !out) { fg_set_error("fg_program_observe_value: k outside [0, O) or a null output"); return FG_E_BAD_ARG; }
+    if (s->value < 0 || !p->nodes[s->value].is_const) return 0;
+    *out = p->nodes[s->value].cval;
+    return 1;
+}
 int fg_program_stream_records(const fg_program *p, int which) {
     if (!p || !p->finalized) return FG_E_STATE;
     if (which == 0) return p->n_gstream;

@@ -98,6 +98,8 @@ ABI_SYMBOLS = [
     "fg_diag_cstream_new", "fg_diag_cstream_update", "fg_diag_cstream_count", "fg_diag_cstream_result", "fg_diag_cstream_free",
     "fg_diag_cells_f64",
     "fg_loglik_stream_new", "fg_loglik_stream_update", "fg_loglik_stream_count", "fg_loglik_stream_pooled", "fg_loglik_stream_result", "fg_loglik_stream_free",
+    "fg_ppc_stream_new", "fg_ppc_stream_update", "fg_ppc_stream_count", "fg_ppc_stream_n_slots", "fg_ppc_stream_observed", "fg_ppc_stream_pooled",
+    "fg_ppc_stream_chains", "fg_ppc_stream_free", "fg_program_observe_value",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -270,6 +272,16 @@ def lib():
     L.fg_loglik_stream_result.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.fg_loglik_stream_free.restype = None
     L.fg_loglik_stream_free.argtypes = [vp]
+    L.fg_ppc_stream_new.argtypes = [vp, C.c_int, C.c_int, ip, C.c_int, ip, ip, ip, C.POINTER(C.c_double), C.POINTER(vp)]
+    L.fg_ppc_stream_update.argtypes = [vp, vp, C.c_int]
+    L.fg_ppc_stream_count.argtypes = [vp]
+    L.fg_ppc_stream_n_slots.argtypes = [vp]
+    L.fg_ppc_stream_observed.argtypes = [vp, C.POINTER(C.c_double)]
+    L.fg_ppc_stream_pooled.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.fg_ppc_stream_chains.argtypes = [vp, C.c_int, C.POINTER(C.c_int64)]
+    L.fg_ppc_stream_free.restype = None
+    L.fg_ppc_stream_free.argtypes = [vp]
+    L.fg_program_observe_value.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
     L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
@@ -446,6 +458,13 @@ class CompiledProgram:
             self.observe_names.append(buf.value.decode("utf-8"))
         self.observe_vtypes = [L.fg_program_observe_vtype(self.h, k) for k in range(self.O)]     # program order, as the names
         self.observe_dists = [L.fg_program_observe_dist(self.h, k) for k in range(self.O)]
+        self.observe_values = []                      # the observed value where the model states it (a literal or a data element), else None
+        v = C.c_double()
+        for k in range(self.O):
+            rc = L.fg_program_observe_value(self.h, k, C.byref(v))
+            if rc < 0:
+                _check(rc)
+            self.observe_values.append(float(v.value) if rc == 1 else None)
         rs = (C.c_int32 * max(1, self.S))()
         self.result_sites = list(rs[:L.fg_program_result_sites(self.h, rs, self.S)])   # sorted site indices some result reads
 
@@ -881,6 +900,12 @@ class Engine:
         pointwise log-likelihood (`predict_eval`'s `loglik` table) of a run of `n_total` draws that is never stored."""
         return LoglikStream(self, n_total, n_sel)
 
+    def ppc_stream(self, n_total: int, vtypes: Sequence[int], checks: Sequence) -> "PpcStream":
+        """A `fg_ppc_stream`: posterior predictive checks from chunks [n_chunk][len(vtypes)][C] of replicated data (`predict_eval`'s cell
+        table; `vtypes` the value type of every row) of a run of `n_total` draws that is never stored.  `checks`: one (member rows,
+        statistics, observed values) per check -- statistics as indices or names of PPC_STATS, observed aligned with the members."""
+        return PpcStream(self, n_total, vtypes, checks)
+
     def cells_f64(self, d_cells: int, n: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], out: Optional[int] = None) -> int:
         """`fg_diag_cells_f64`: rows `rows` of the device cells [n][n_rec][C] as doubles [n][len(rows)][C] in the device buffer `out`
         (allocated here when None: the caller frees it), asynchronously: an f64 row is copied, a u64 row converted as unsigned
@@ -1201,6 +1226,94 @@ class LoglikStream:
         if getattr(self, "h", None):
             if getattr(self.engine, "h", None):          # the state lives in the engine's device context
                 lib().fg_loglik_stream_free(self.h)
+            self.h = None
+
+    close = free
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+PPC_STATS = ("mean", "var", "min", "max", "sum")          # FG_PPC_MEAN .. FG_PPC_SUM
+PPC_COUNTS = ("n_lt", "n_eq", "n_gt", "n_nan", "n_fin")
+PPC_SCRATCH_DRAWS = 16                                    # FG_PPC_SCRATCH_DRAWS (fg_ppc_stream_plan.h): an update walks its chunk in pieces of that many draws
+
+
+class PpcStream:
+    """`fg_ppc_stream` (fg_ppc_stream.hip): test statistics of every replicated data set of a run handed over in chunks
+    [n_chunk][n_rows][C] of raw cells (`Engine.predict_eval`'s cell table), compared with the observed ones -- what the reference's
+    workflows do on the host after replicating the data (tests/end_to_end_workflows.rs:650-745).  A slot is a (check, statistic)
+    pair, in check order, then in the order of PPC_STATS; `slots` lists them.  Every (slot, chain) column is updated in draw order by
+    one thread and the chains are pooled by a fixed tree on the chain index, so the result does not depend on the chunking, bit for
+    bit.  Device memory: 48 x n_slots x C bytes of state and a scratch table of 16 draws' statistics.  Close it before its engine."""
+
+    def __init__(self, engine: Engine, n_total: int, vtypes: Sequence[int], checks):
+        if isinstance(n_total, bool) or not isinstance(n_total, (int, np.integer)):
+            raise TypeError(f"n_total must be an integer, not {type(n_total).__name__}")
+        self.engine, self.n, self.h = engine, int(n_total), None
+        vt = [int(v) for v in vtypes]
+        offsets, members, masks, observed, self.slots = [0], [], [], [], []
+        for q, (rows, stats, obs) in enumerate(checks):
+            rows, obs = [int(r) for r in rows], [float(v) for v in obs]
+            if len(rows) != len(obs):
+                raise ValueError(f"check {q}: {len(rows)} members and {len(obs)} observed values")
+            ids = sorted({PPC_STATS.index(st) if isinstance(st, str) else int(st) for st in stats})
+            mask = 0
+            for st in ids:
+                mask |= 1 << st
+            members += rows
+            observed += obs
+            offsets.append(len(members))
+            masks.append(mask)
+            self.slots += [(q, st) for st in ids if 0 <= st < len(PPC_STATS)]
+        i32 = lambda v: (C.c_int32 * max(1, len(v)))(*v)
+        out = C.c_void_p()
+        _check(lib().fg_ppc_stream_new(engine.h, self.n, len(vt), i32(vt), len(masks), i32(offsets), i32(members), i32(masks),
+                                       (C.c_double * max(1, len(observed)))(*observed), C.byref(out)))
+        self.h = out.value
+        self.n_slots = int(lib().fg_ppc_stream_n_slots(self.h))
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the stream is closed")
+        return self.h
+
+    def update(self, d_yrep: int, n_chunk: int):
+        """The next `n_chunk` draws, a device buffer of cells [n_chunk][n_rows][C]; asynchronous.  n_chunk = 0 does nothing."""
+        _check(lib().fg_ppc_stream_update(self._handle(), d_yrep, int(n_chunk)))
+
+    def count(self) -> int:
+        return int(lib().fg_ppc_stream_count(self._handle()))
+
+    def observed(self) -> np.ndarray:
+        """T_obs float64 [n_slots]: the statistic of every slot's observed vector."""
+        t = np.zeros(self.n_slots)
+        _check(lib().fg_ppc_stream_observed(self._handle(), _dp(t)))
+        return t
+
+    def pooled(self) -> dict:
+        """Pooled over the chains, per slot: n_lt, n_eq, n_gt, n_nan, n_fin int64 [n_slots] (draws whose statistic is below / equal to /
+        above the observed one, NaN draws, finite statistics) and `mean`, `ssd` float64 [n_slots] of the finite statistics.  Raises
+        EngineError (FG_E_STATE) before `n_total` draws have arrived."""
+        counts, mom = np.zeros((self.n_slots, 5), dtype=np.int64), np.zeros((self.n_slots, 2))
+        _check(lib().fg_ppc_stream_pooled(self._handle(), counts.ctypes.data_as(C.POINTER(C.c_int64)), _dp(mom)))
+        out = {name: counts[:, i].copy() for i, name in enumerate(PPC_COUNTS)}
+        out.update(mean=mom[:, 0].copy(), ssd=mom[:, 1].copy())
+        return out
+
+    def chains(self, slot: int) -> dict:
+        """The five counters of one slot per chain, each int64 [C]."""
+        counts = np.zeros((5, self.engine.C), dtype=np.int64)
+        _check(lib().fg_ppc_stream_chains(self._handle(), int(slot), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return {name: counts[i].copy() for i, name in enumerate(PPC_COUNTS)}
+
+    def free(self):
+        if getattr(self, "h", None):
+            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
+                lib().fg_ppc_stream_free(self.h)
             self.h = None
 
     close = free

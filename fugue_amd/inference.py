@@ -80,6 +80,7 @@ class ChainBatch:
     predictive_vtypes: List[int] = field(default_factory=list)
     predictive: Optional[np.ndarray] = None                   # [n_samples][n_sel][n_chains] int64 cells like `cells`: replicated data, draw t from stream (seed, chain, t, 9)
     log_likelihood: Optional[np.ndarray] = None               # pointwise=True: [n_samples][n_sel][n_chains] float64, log p(observed value | draw) per observe statement
+    observe_values: Dict[str, Optional[float]] = field(default_factory=dict)   # every observe address -> the observed value the model states (a literal or a data element), None where it reads a site; filled whatever `predictive` is
 
     def get_predictive(self, address: str) -> np.ndarray:     # [n_samples][n_chains]: float64 for an f64 observe site, int64 otherwise
         if self.predictive is None or address not in self.predictive_names:
@@ -126,6 +127,7 @@ class SMCResult:
     predictive_vtypes: List[int] = field(default_factory=list)
     predictive: Optional[np.ndarray] = None                   # [n_sel][n_particles] int64 cells: one replicate per particle
     log_likelihood: Optional[np.ndarray] = None               # pointwise=True: [n_sel][n_particles] float64
+    observe_values: Dict[str, Optional[float]] = field(default_factory=dict)   # as ChainBatch.observe_values
 
     def get_f64(self, address: str) -> np.ndarray:
         return np.ascontiguousarray(self.cells[self.sites.index(address)]).view(np.float64)
@@ -193,6 +195,10 @@ def _predictive_fields(cp, sel, y, ll):
     return dict(predictive_names=[cp.observe_names[k] for k in sel], predictive_vtypes=[cp.observe_vtypes[k] for k in sel], predictive=y, log_likelihood=ll)
 
 
+def _observe_values(cp) -> Dict[str, Optional[float]]:
+    return dict(zip(cp.observe_names, cp.observe_values))
+
+
 def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
               device: int = 0, predictive=False, pointwise: bool = False) -> ChainBatch:
     """`predictive=True | [addresses]`: `ChainBatch.predictive`, replicated data of the (selected) observe sites at every draw, sampled
@@ -239,7 +245,8 @@ def hmc_chain(seed: int, model_fn, n_samples: int, n_warmup: int, config: Option
         eng.device_free(buf)
         cells[:] = eng.get_values()[None]                       # HMC moves the f64 sites; discrete sites keep their prior draw (hmc.rs:238-260)
         cells[:, cp.f64_sites, :] = draws
-    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, st.mean_step_size, int(st.n_divergent), list(cp.result_names), results)
+    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, st.mean_step_size, int(st.n_divergent), list(cp.result_names), results,
+                     observe_values=_observe_values(cp))
     if sel is not None:
         for k, v in _predictive_fields(cp, sel, pred_y, pred_ll).items():
             setattr(out, k, v)
@@ -289,7 +296,7 @@ def adaptive_mcmc_chain_with_overrides(seed: int, model_fn, n_samples: int, n_wa
             ll = np.concatenate([q[1] for q in parts]) if pointwise else None
         pred = _predictive_fields(cp, sel, y, ll)
     eng.device_free(buf)
-    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, result_names=list(cp.result_names), results=results, **pred)
+    out = ChainBatch(list(cp.site_names), list(cp.site_vtypes), cells, st.accept_rate, result_names=list(cp.result_names), results=results, observe_values=_observe_values(cp), **pred)
     eng.close()
     return out
 
@@ -325,6 +332,7 @@ class ChainSummary:
     discrete: Optional["DiscreteSummary"] = None  # adaptive_mcmc_chain_summary(discrete=True): the frequency tables of the discrete sites
     predictive: Optional["ChainSummary"] = None   # predictive=: the same figures of the replicated data, `sites` = the selected observe addresses
     comparison: Optional["PointwiseComparison"] = None   # pointwise=: WAIC / IS-LOO per selected observe statement (fugue_amd.comparison)
+    checks: Optional["PredictiveCheck"] = None    # checks=: posterior predictive checks of the replicated data (fugue_amd.checks)
 
 
 @dataclass
@@ -383,7 +391,7 @@ def _default_bins(cp, j: int) -> Tuple[int, int]:
 
 
 def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_lag: int, quantiles: bool = False, quantile_capacity: int = 65536,
-                    after_first_pass=None, result_rows=False, discrete_bins=False, predict=None, pointwise=None):
+                    after_first_pass=None, result_rows=False, discrete_bins=False, predict=None, pointwise=None, checks=None):
     """step(n, buf) records n draws into buf; one chunk buffer is alive at a time.  A chunk is seen through FEEDS: a view of it as
     doubles [n][rows][C] and the diagnostics stream (with quantiles: and the quantile stream) that take the view.
       - discrete_bins False: buf is [n][d][C] doubles (the f64 sites `sites`) and is its own view.
@@ -398,6 +406,10 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
       - pointwise (dict(sel=observe indices, rows=as result_rows)) adds WAIC / IS-LOO of the selected observe statements: every chunk's
         log-likelihood goes into one reused [chunk][n_sel][C] buffer (`Engine.predict_eval`, loglik only) that the log-likelihood stream
         takes (`Engine.loglik_stream`).  First pass only: a replay pass for quantiles does not feed it.
+      - checks (dict(sel=observe indices, rows=as result_rows, specs, tuples: `fugue_amd.checks.resolve_checks` over the addresses of sel))
+        adds posterior predictive checks: every chunk's replicates of the member statements go into one reused [chunk][n_sel][C] cell
+        buffer (`Engine.predict_eval`, cells only, discrete observe sites included) that the check stream takes (`Engine.ppc_stream`).
+        First pass only.
     A view is called with (chunk buffer, draws in it, index of its first draw in the sampling phase).
     quantiles: the state after warmup is exported, the first sampling pass feeds every stream, `after_first_pass()` reads the
     sampler's statistics, and while a quantile stream wants another pass the blob is imported into the same engine and the same
@@ -462,6 +474,12 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
             lbuf = alloc(chunk * len(lsel) * C_)
             lls = eng.loglik_stream(n_samples, len(lsel))
             streams.append(lls)
+        pcs = None
+        if checks is not None:
+            csel, crows = list(checks["sel"]), checks["rows"]
+            cbuf = alloc(chunk * len(csel) * C_)
+            pcs = eng.ppc_stream(n_samples, [cp.observe_vtypes[k] for k in csel], checks["tuples"])
+            streams.append(pcs)
         blob = eng.state_export() if quantiles else None
         buf = alloc(chunk * chunk_rows * C_)
 
@@ -481,6 +499,9 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
                 if first and lls is not None:
                     eng.predict_eval(buf, n, rows=lrows, iter0=done, sel=lsel, out=False, loglik=lbuf)
                     lls.update(lbuf, n)
+                if first and pcs is not None:
+                    eng.predict_eval(buf, n, rows=crows, iter0=done, sel=csel, out=cbuf, loglik=False)
+                    pcs.update(cbuf, n)
                 done += n
 
         one_pass([c for f in feeds for c in (f["stream"], f["qs"]) if c is not None], [cs] if cs is not None else [], first=True)
@@ -492,6 +513,9 @@ def _stream_summary(eng, step, sites, d: int, n_samples: int, chunk: int, max_la
         if lls is not None:
             from .comparison import PointwiseComparison
             out.comparison = PointwiseComparison.from_result([cp.observe_names[k] for k in lsel], n_samples * int(C_), lls.result())
+        if pcs is not None:
+            from .checks import PredictiveCheck
+            out.checks = PredictiveCheck.from_stream(checks["specs"], pcs, n_samples * int(C_), int(C_))
         if discrete:
             tab = cs.result() if cs is not None else dict(counts=[], below=np.zeros(0, dtype=np.uint64), above=np.zeros(0, dtype=np.uint64), min=[], max=[])
             out.discrete = DiscreteSummary([cp.site_names[j] for j in w_rows], [cp.site_vtypes[j] for j in w_rows], [b[0] for b in bins], tab["counts"],
@@ -535,6 +559,20 @@ def _summary_pointwise(cp, pointwise, who: str):
     return _predictive_sel(cp, pointwise, True, who)
 
 
+def _summary_checks(cp, checks, who: str):
+    """`checks=False | True | [CheckSpec]` of a summary driver: None, or what `_stream_summary` takes -- the union of the member
+    statements in program order (`sel`, the rows of the cell buffer), and the checks over the addresses of those rows.  Any observe
+    statement may be a member, discrete ones included; the observed values are the ones the model states."""
+    if checks is False or checks is None:
+        return None
+    from .checks import resolve_checks
+    if cp.O == 0:
+        raise ValueError(f"{who}: checks asked for, but the model has no observe statement")
+    specs, tuples = resolve_checks(checks, cp.observe_names, cp.observe_values, None, who)
+    sel = sorted({k for rows, _, _ in tuples for k in rows})
+    return dict(sel=sel, specs=specs, tuples=[([sel.index(k) for k in rows], stats, obs) for rows, stats, obs in tuples])
+
+
 def _summary_predictive(cp, predictive, who: str):
     """The selection of a summary driver: f64 observe sites only (a discrete one would need the count stream)."""
     sel = _predictive_sel(cp, predictive, False, who)
@@ -548,7 +586,7 @@ def _summary_predictive(cp, predictive, who: str):
 
 def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config: Optional[HMCConfig] = None, n_chains: int = 1,
                       chunk: int = 64, max_lag: int = 64, device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536,
-                      results: bool = False, predictive=False, pointwise=False) -> ChainSummary:
+                      results: bool = False, predictive=False, pointwise=False, checks=False) -> ChainSummary:
     """`hmc_chain` for runs longer than memory: the same transitions (`fg_hmc_step` is incremental), `chunk` at a time into one
     draw buffer that a diagnostics stream consumes, and the summary of every f64 site instead of the draws.  `max_lag` bounds how
     far Geyer's sequence may run (an ESS that needs more raises EngineError FG_E_LIMIT).  `quantiles=True` adds the five quantiles
@@ -562,7 +600,11 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
     samples a chunk again to the same bits); a selected discrete observe site raises ValueError.  `pointwise=True | [addresses]` adds
     `ChainSummary.comparison`, a `PointwiseComparison`: WAIC and importance-sampling LOO per (selected) observe statement, discrete ones
     included, from the log-likelihood of every chunk (`Engine.loglik_stream`; the table is never held; device memory 80 bytes per
-    statement and chain, so a model with very many observe statements names the ones to compare).  Nothing else changes."""
+    statement and chain, so a model with very many observe statements names the ones to compare).  `checks=True | [CheckSpec]` adds
+    `ChainSummary.checks`, a `PredictiveCheck` (fugue_amd.checks): the replicates of every chunk of the first pass are reduced to the
+    test statistics of the checks on the device and compared with the observed data (`Engine.ppc_stream`; True is one check "all" over
+    every observe statement with all five statistics; discrete observe sites are fine; device memory 48 bytes per statistic, check and
+    chain).  Nothing else changes."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     if cp.d == 0:
@@ -570,6 +612,7 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
     _want_results(cp, results, who="hmc_chain_summary")
     psel = _summary_predictive(cp, predictive, "hmc_chain_summary")
     lsel = _summary_pointwise(cp, pointwise, "hmc_chain_summary")
+    csel = _summary_checks(cp, checks, "hmc_chain_summary")
     cfg = config or HMCConfig()
     eng = E.Engine(cp, n_chains, seed=seed, device=device)
     try:
@@ -581,7 +624,7 @@ def hmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: int, config
 
         out = _stream_summary(eng, eng.hmc_step, [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag, quantiles, quantile_capacity, stats,
                               result_rows=None if results else False, predict=None if psel is None else dict(sel=psel, rows=None),
-                              pointwise=None if lsel is None else dict(sel=lsel, rows=None))
+                              pointwise=None if lsel is None else dict(sel=lsel, rows=None), checks=None if csel is None else dict(csel, rows=None))
     finally:
         eng.close()
     return out
@@ -591,7 +634,7 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
                                 overrides: Sequence[Tuple[str, SiteProposal]] = (), chunk: int = 64, max_lag: int = 64,
                                 device: int = 0, quantiles: bool = False, quantile_capacity: int = 65536, results: bool = False,
                                 discrete: bool = False, discrete_bins: Optional[Dict[str, Tuple[int, int]]] = None, predictive=False,
-                                pointwise=False) -> ChainSummary:
+                                pointwise=False, checks=False) -> ChainSummary:
     """`adaptive_mcmc_chain_with_overrides` for runs longer than memory: the same steps (`fg_mh_step` is incremental), recording
     only the f64 sites, `chunk` at a time into one draw buffer that a diagnostics stream consumes.  `quantiles=True` adds the five
     quantiles as `hmc_chain_summary` does: every pass beyond the first REPEATS THE SAMPLING PHASE from the state exported after
@@ -608,12 +651,17 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
     `predictive=True | [addresses]` adds `ChainSummary.predictive` as `hmc_chain_summary` does.  The parameters of an observe statement
     must come from recorded sites: a model with a discrete site needs `discrete=True` (which records every site).
 
-    `pointwise=True | [addresses]` adds `ChainSummary.comparison` as `hmc_chain_summary` does, under the same condition on recorded sites."""
+    `pointwise=True | [addresses]` adds `ChainSummary.comparison` as `hmc_chain_summary` does, under the same condition on recorded sites.
+    `checks=True | [CheckSpec]` adds `ChainSummary.checks` as `hmc_chain_summary` does, under the same condition; discrete OBSERVE sites
+    need nothing."""
     _summary_args(n_samples, chunk, max_lag)
     cp = _compile(model_fn)
     who = "adaptive_mcmc_chain_summary"
     psel = _summary_predictive(cp, predictive, who)
     lsel = _summary_pointwise(cp, pointwise, who)
+    csel = _summary_checks(cp, checks, who)
+    if csel is not None and psel is None and lsel is None and not discrete and cp.d != cp.S:
+        raise ValueError(f"{who}: checks on a model with discrete sites needs discrete=True (a streamed MH run records its f64 sites only, and the discrete ones move)")
     if (psel is not None or lsel is not None) and not discrete and cp.d != cp.S:
         raise ValueError(f"{who}: predictive / pointwise on a model with discrete sites needs discrete=True (a streamed MH run records its f64 sites only, "
                          "and the discrete ones move)")
@@ -644,7 +692,7 @@ def adaptive_mcmc_chain_summary(seed: int, model_fn, n_samples: int, n_warmup: i
         out = _stream_summary(eng, lambda n, buf: eng.mh_step(n, rec, buf), [cp.site_names[j] for j in cp.f64_sites], cp.d, n_samples, chunk, max_lag,
                               quantiles, quantile_capacity, stats, result_rows=rec if results else False,
                               discrete_bins=dict(discrete_bins or {}) if discrete else False, predict=None if psel is None else dict(sel=psel, rows=rec),
-                              pointwise=None if lsel is None else dict(sel=lsel, rows=rec))
+                              pointwise=None if lsel is None else dict(sel=lsel, rows=rec), checks=None if csel is None else dict(csel, rows=rec))
     finally:
         eng.close()
     return out
@@ -661,11 +709,11 @@ def adaptive_smc(seed: int, num_particles: int, model_fn, config: Optional[SMCCo
     if num_particles == 0:                                         # smc.rs:462-467
         pred = {} if sel is None else _predictive_fields(cp, sel, np.zeros((len(sel), 0), dtype=np.int64) if want_y else None, np.zeros((len(sel), 0)) if pointwise else None)
         return SMCResult(list(cp.site_names), list(cp.site_vtypes), np.zeros((cp.S, 0), dtype=np.int64), np.zeros(0), np.zeros(0), 0.0,   # empty population: log_evidence 0.0
-                         result_names=list(cp.result_names), results=np.zeros((cp.R, 0)) if cp.R > 0 else None, **pred)
+                         result_names=list(cp.result_names), results=np.zeros((cp.R, 0)) if cp.R > 0 else None, observe_values=_observe_values(cp), **pred)
     eng = E.Engine(cp, num_particles, seed=seed, device=device)
     r = eng.smc_run(cfg.resampling_method, cfg.ess_threshold, cfg.rejuvenation_steps)
     out = SMCResult(list(cp.site_names), list(cp.site_vtypes), r["values"], r["weights"], r["log_w"], r["log_evidence"], r["betas"],
-                    list(cp.result_names), eng.result_values() if cp.R > 0 else None)
+                    list(cp.result_names), eng.result_values() if cp.R > 0 else None, observe_values=_observe_values(cp))
     if sel is not None:
         y, ll = _predict(eng, sel, want_y, pointwise, None, 1)
         for k, v in _predictive_fields(cp, sel, None if y is None else y[0], None if ll is None else ll[0]).items():
@@ -685,6 +733,7 @@ class PriorPredictive:
     predictive_vtypes: List[int]
     predictive: np.ndarray            # [n_sel][n_chains] int64 cells
     log_likelihood: Optional[np.ndarray] = None   # pointwise=True: [n_sel][n_chains]
+    observe_values: Dict[str, Optional[float]] = field(default_factory=dict)   # as ChainBatch.observe_values
 
     def get_f64(self, address: str) -> np.ndarray:
         return np.ascontiguousarray(self.cells[self.sites.index(address)]).view(np.float64)
@@ -707,6 +756,7 @@ def prior_predictive(seed: int, model_fn, n_chains: int, iteration: int = 0, pre
         eng.prior_init(iteration)
         y, ll = _predict(eng, sel, True, pointwise, None, 1, iter0=iteration)
         f = _predictive_fields(cp, sel, y[0], None if ll is None else ll[0])
-        return PriorPredictive(list(cp.site_names), list(cp.site_vtypes), eng.get_values(), f["predictive_names"], f["predictive_vtypes"], f["predictive"], f["log_likelihood"])
+        return PriorPredictive(list(cp.site_names), list(cp.site_vtypes), eng.get_values(), f["predictive_names"], f["predictive_vtypes"], f["predictive"], f["log_likelihood"],
+                               _observe_values(cp))
     finally:
         eng.close()

@@ -115,6 +115,11 @@ int fg_program_site_of_handle(const fg_program *p, int handle);
 int fg_program_observe_name(const fg_program *p, int k, char *buf, int buf_len);
 int fg_program_observe_vtype(const fg_program *p, int k);
 int fg_program_observe_dist(const fg_program *p, int k);
+/* the observed value of observe statement k (program order) where the model states it: returns 1 and *out = the value as the double
+ * `x as f64` when it reads no site (a literal or a data element: the `observations` slice of the reference's workflows,
+ * tests/end_to_end_workflows.rs:650-745), 0 when it reads a site (its value moves with the draw; *out is left alone).  FG_E_BAD_ARG:
+ * k outside [0, O), a null argument. */
+int fg_program_observe_value(const fg_program *p, int k, double *out);
 int fg_program_f64_site(const fg_program *p, int k);
 /* number of instructions re-evaluated when f64 coordinate k is perturbed (sparse FD) */
 int fg_program_dep_count(const fg_program *p, int k);
@@ -674,6 +679,48 @@ int  fg_loglik_stream_pooled(fg_loglik_stream *s, double *h_words, int64_t *h_co
 /* the figures h_figures [FG_LL_FIGURES][n_sel] and the counters as above.  FG_E_STATE before n_total draws have arrived. */
 int  fg_loglik_stream_result(fg_loglik_stream *s, double *h_figures, int64_t *h_counts);
 void fg_loglik_stream_free(fg_loglik_stream *s);
+/* ------------------------------------------------------------------ posterior predictive checks without a stored table
+ * What the reference's workflows do by hand after replicating the data (tests/end_to_end_workflows.rs:650-745,
+ * tests/inference_integration.rs:717-740, examples/bayesian_coin_flip.rs:211-): the mean of every replicated data set, its variance
+ * with divisor K - 1, or its number of heads, compared with the same statistic of the observed data and read as a p-value.  Here from
+ * the replicate table fg_predict_eval writes, d_yrep [n][n_rows][C] raw cells, handed over one chunk at a time.
+ * A CHECK is a group of K >= 1 rows of the table (members, in the order given; a row may belong to several checks) and an observed
+ * vector y[K].  Cells become doubles as fg_diag_cells_f64 converts them (`x as f64` by the row's value type).  The statistics of a
+ * data set, in member order, every operation rounded:
+ *   FG_PPC_MEAN  the in-order sum onto +0.0 over (double)K (end_to_end_workflows.rs:700-703)
+ *   FG_PPC_VAR   a second in-order pass of (x - mean)(x - mean) onto +0.0 over (double)(K - 1) (:720-726); K = 1: 0/0 = NaN
+ *   FG_PPC_MIN / FG_PPC_MAX  from the first member by x < m ? x : m and x > m ? x : m
+ *   FG_PPC_SUM   the in-order sum itself (the number of heads of Bernoulli rows, bayesian_coin_flip.rs:211-)
+ * and a NaN cell anywhere in the group makes all five NaN.  A SLOT is a (check, statistic) pair asked for by the check's mask (bit
+ * FG_PPC_x), numbered in check order, then in statistic order.  Per (slot, chain) the stream keeps 6 words -- 48 bytes; a model with
+ * 1 024 observe statements selects the checks it needs -- updated in draw order by one thread, so the state does not depend on the
+ * chunking, bit for bit: counters of draws whose statistic T is <, ==, > the observed one (-0.0 == +0.0, infinities as IEEE compares
+ * them) and of draws where either is NaN (u32: n_total < 2^31), and the pivoted sums of the finite T.  At read-out the counters pool
+ * over the chains by addition and the moments by the fixed tree on the chain index of the log-likelihood stream.  This engine's chains
+ * only; unweighted draws only (not an SMC population).  The stream reads engine state and changes none. */
+enum { FG_PPC_MEAN = 0, FG_PPC_VAR = 1, FG_PPC_MIN = 2, FG_PPC_MAX = 3, FG_PPC_SUM = 4, FG_PPC_N_STATS = 5 };
+typedef struct fg_ppc_stream fg_ppc_stream;
+/* h_vtypes [n_rows]: the value type of every table row (FG_F64 .. FG_I64); h_offsets [n_checks + 1] into h_members (rows in
+ * [0, n_rows)) and h_observed (aligned with h_members); h_stat_mask [n_checks].  FG_E_BAD_ARG: n_total < 1, n_rows < 1, no check, an
+ * empty check, an empty mask or a mask bit >= FG_PPC_N_STATS, a member outside the rows, an unknown value type, offsets that do not
+ * start at 0 or decrease.  The stream must be freed before its engine. */
+int  fg_ppc_stream_new(fg_engine *e, int n_total, int n_rows, const int32_t *h_vtypes, int n_checks, const int32_t *h_offsets,
+                       const int32_t *h_members, const int32_t *h_stat_mask, const double *h_observed, fg_ppc_stream **out);
+/* the next n_chunk draws d_yrep [n_chunk][n_rows][C]; asynchronous on the engine's stream; n_chunk == 0 is FG_OK without a launch.
+ * FG_E_STATE when the chunk would pass n_total. */
+int  fg_ppc_stream_update(fg_ppc_stream *s, const void *d_yrep, int n_chunk);
+int  fg_ppc_stream_count(const fg_ppc_stream *s);              /* draws taken so far */
+int  fg_ppc_stream_n_slots(const fg_ppc_stream *s);
+/* h_t_obs [n_slots]: the statistic of the observed vector of every slot (the `obs_mean` / `obs_var` of the workflows) */
+int  fg_ppc_stream_observed(const fg_ppc_stream *s, double *h_t_obs);
+/* pooled over the chains: h_counts [n_slots][5] draws with T < / == / > T_obs, NaN draws, finite T; h_moments [n_slots][2] the mean of
+ * the finite T and their sum of squared deviations (NaN without a finite draw; +0.0 deviations with one).  FG_E_STATE before n_total
+ * draws have arrived. */
+int  fg_ppc_stream_pooled(fg_ppc_stream *s, int64_t *h_counts, double *h_moments);
+/* the same five counters of one slot per chain, h_counts [5][C]: the between-chain spread of a p-value.  FG_E_STATE as above;
+ * FG_E_BAD_ARG: a slot outside [0, n_slots). */
+int  fg_ppc_stream_chains(fg_ppc_stream *s, int slot, int64_t *h_counts);
+void fg_ppc_stream_free(fg_ppc_stream *s);
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

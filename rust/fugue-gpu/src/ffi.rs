@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_diag_qstream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_diag_cstream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_loglik_stream { _p: [u8; 0] }
+#[repr(C)] pub struct fg_ppc_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_abc { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
@@ -91,6 +92,7 @@ extern "C" {
     pub fn fg_program_observe_name(p: *const fg_program, k: c_int, buf: *mut c_char, buf_len: c_int) -> c_int;
     pub fn fg_program_observe_vtype(p: *const fg_program, k: c_int) -> c_int;
     pub fn fg_program_observe_dist(p: *const fg_program, k: c_int) -> c_int;
+    pub fn fg_program_observe_value(p: *const fg_program, k: c_int, out: *mut f64) -> c_int;
     // the model's return value, `A` of Model<A> (model.rs `pure`; hmc.rs:566-583 returns it with every trace)
     pub fn fg_program_result(p: *mut fg_program, name_utf8: *const c_char, toks: *const fg_tok, n: c_int) -> c_int;
     pub fn fg_program_n_results(p: *const fg_program) -> c_int;
@@ -208,6 +210,16 @@ extern "C" {
     pub fn fg_loglik_stream_pooled(s: *mut fg_loglik_stream, h_words: *mut f64, h_counts: *mut i64) -> c_int;
     pub fn fg_loglik_stream_result(s: *mut fg_loglik_stream, h_figures: *mut f64, h_counts: *mut i64) -> c_int;
     pub fn fg_loglik_stream_free(s: *mut fg_loglik_stream);
+    // ---- posterior predictive checks from a streamed replicate table (fg_ppc_stream.hip)
+    pub fn fg_ppc_stream_new(e: *mut fg_engine, n_total: c_int, n_rows: c_int, h_vtypes: *const i32, n_checks: c_int, h_offsets: *const i32,
+                             h_members: *const i32, h_stat_mask: *const i32, h_observed: *const f64, out: *mut *mut fg_ppc_stream) -> c_int;
+    pub fn fg_ppc_stream_update(s: *mut fg_ppc_stream, d_yrep: *const c_void, n_chunk: c_int) -> c_int;
+    pub fn fg_ppc_stream_count(s: *const fg_ppc_stream) -> c_int;
+    pub fn fg_ppc_stream_n_slots(s: *const fg_ppc_stream) -> c_int;
+    pub fn fg_ppc_stream_observed(s: *const fg_ppc_stream, h_t_obs: *mut f64) -> c_int;
+    pub fn fg_ppc_stream_pooled(s: *mut fg_ppc_stream, h_counts: *mut i64, h_moments: *mut f64) -> c_int;
+    pub fn fg_ppc_stream_chains(s: *mut fg_ppc_stream, slot: c_int, h_counts: *mut i64) -> c_int;
+    pub fn fg_ppc_stream_free(s: *mut fg_ppc_stream);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
