@@ -14,38 +14,19 @@
 // State size: FG_LL_WORDS x n_sel x C x 8 bytes -- 80 bytes per (statement, chain), 5.4 GB at n_sel = 1 024, C = 65 536: a model
 // with many observe statements selects the ones it compares (`sel` of fg_predict_eval, `pointwise=[addresses]` of the drivers).
 //
-// Read-out: the chains of a statement are pooled by a FIXED binary tree on the chain index -- for stride s = 1, 2, 4, ... element
-// i (a multiple of 2 s) takes in element i + s when i + s < C and passes through unchanged otherwise -- so the pooled words are a
-// function of the table and of C alone.  A missing partner is the empty element, and merging with it is the identity, bit for bit;
-// so a block of FG_LL_POOL_THREADS consecutive elements is a subtree whatever C is, and the tree is run level by level:
-// level 0 turns C columns into ceil(C / 256) elements, level 1 those into ceil(. / 256), ... down to one.
+// Read-out: the chains of a statement are pooled by fg_chain_pool.h's fixed tree on the chain index, FgLlPool its elements.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
-#include <algorithm>
 #include <cmath>
-#include <string>
-#include <vector>
 
-#include "../../include/fugue_amd.h"
-
-#ifndef FG_HD
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define FG_HD __host__ __device__ __forceinline__
-#else
-#define FG_HD inline
-#endif
-#endif
+#include "fg_chain_pool.h"
 
 #define FG_LL_WORDS 10               // state words per column
 // FG_LL_POOLED (fugue_amd.h) = 8 pooled finite words per statement: mx sp mn sn sn2 n_fin mean ssd
 #define FG_LL_ELEM 11                // a tree element in memory: the pooled words, then n_neg_inf, n_pos_inf, n_nan as int64 bits
 #define FG_LL_UPDATE_THREADS 256
-#define FG_LL_POOL_THREADS 256       // elements per block of a tree level; a power of two (the block is a subtree)
-#define FG_LL_MAX_GRID_X 0x7fffff    // blocks of an update launch: threads stay below 2^31
-#define FG_LL_MAX_GRID_Y 65535
 
 struct FgLlState {                   // a column while a chunk is walked
     double mx, sp, mn, sn, sn2, pivot, s1, s2;
@@ -53,8 +34,9 @@ struct FgLlState {                   // a column while a chunk is walked
 };
 
 struct FgLlElem {                    // a tree element: a chain, or chains pooled
-    double mx, sp, mn, sn, sn2, n, mean, ssd;      // n: the finite cells (below 2^47, exact)
-    int64_t n_neg_inf, n_pos_inf, n_nan;
+    double mx = 0.0, sp = 0.0, mn = 0.0, sn = 0.0, sn2 = 0.0;
+    FgMoments m;                     // of the finite cells
+    int64_t n_neg_inf = 0, n_pos_inf = 0, n_nan = 0;
 };
 
 FG_HD void fg_ll_state_load(FgLlState &s, const double *w, long long stride) {
@@ -94,77 +76,66 @@ FG_HD void fg_ll_update(FgLlState &s, double x) {
     s.s1 += d; s.s2 += d * d; s.n_fin += 1;
 }
 
-FG_HD FgLlElem fg_ll_empty() {
-    FgLlElem e;
-    e.mx = e.sp = e.mn = e.sn = e.sn2 = e.n = e.mean = e.ssd = 0.0;
-    e.n_neg_inf = e.n_pos_inf = e.n_nan = 0;
-    return e;
-}
-
-// a chain as a tree leaf: (n, mean, ssd) by fg_diag_stream's identities, mu = s1 / n, mean = pivot + mu, ssd = s2 - s1 mu
-FG_HD FgLlElem fg_ll_leaf(const FgLlState &s) {
-    FgLlElem e = fg_ll_empty();
-    e.n_neg_inf = (int64_t)s.n_neg_inf; e.n_pos_inf = (int64_t)s.n_pos_inf; e.n_nan = (int64_t)s.n_nan;
-    if (s.n_fin == 0) return e;
-    e.mx = s.mx; e.sp = s.sp; e.mn = s.mn; e.sn = s.sn; e.sn2 = s.sn2;
-    e.n = (double)s.n_fin;
-    const double mu = s.s1 / e.n;
-    e.mean = s.pivot + mu;
-    e.ssd = s.s2 - s.s1 * mu;
-    return e;
-}
-
-// element i takes in element i + s.  Counters add; a side without finite cells passes the other side's finite words through
-// untouched; else the larger maximum (the smaller minimum) stays the reference point, and the moments merge by Chan's formulas.
-FG_HD FgLlElem fg_ll_merge(const FgLlElem &a, const FgLlElem &b) {
-    FgLlElem r = a;
-    if (a.n == 0.0) r = b;
-    else if (b.n != 0.0) {
-        if (a.mx >= b.mx) { r.sp = a.sp + b.sp * exp(b.mx - a.mx); r.mx = a.mx; }
-        else { r.sp = b.sp + a.sp * exp(a.mx - b.mx); r.mx = b.mx; }
-        if (a.mn <= b.mn) { const double f = exp(a.mn - b.mn); r.sn = a.sn + b.sn * f; r.sn2 = a.sn2 + b.sn2 * (f * f); r.mn = a.mn; }
-        else { const double f = exp(b.mn - a.mn); r.sn = b.sn + a.sn * f; r.sn2 = b.sn2 + a.sn2 * (f * f); r.mn = b.mn; }
-        const double n = a.n + b.n, delta = b.mean - a.mean;
-        r.n = n;
-        r.mean = a.mean + delta * (b.n / n);
-        r.ssd = a.ssd + b.ssd + delta * delta * (a.n * b.n / n);
+struct FgLlPool {
+    typedef FgLlElem Elem;
+    typedef FgLlState State;
+    enum { WORDS = FG_LL_ELEM };
+    static FG_HD Elem empty() { return Elem(); }
+    static FG_HD void state_load(State &s, const double *w, long long stride) { fg_ll_state_load(s, w, stride); }
+    // a chain as a tree leaf
+    static FG_HD Elem leaf(const State &s) {
+        Elem e;
+        e.n_neg_inf = (int64_t)s.n_neg_inf; e.n_pos_inf = (int64_t)s.n_pos_inf; e.n_nan = (int64_t)s.n_nan;
+        if (s.n_fin == 0) return e;
+        e.mx = s.mx; e.sp = s.sp; e.mn = s.mn; e.sn = s.sn; e.sn2 = s.sn2;
+        e.m = fg_moments_leaf((double)s.n_fin, s.pivot, s.s1, s.s2);
+        return e;
     }
-    r.n_neg_inf = a.n_neg_inf + b.n_neg_inf; r.n_pos_inf = a.n_pos_inf + b.n_pos_inf; r.n_nan = a.n_nan + b.n_nan;
-    return r;
-}
-
-FG_HD void fg_ll_elem_store(const FgLlElem &e, double *w) {
-    w[0] = e.mx; w[1] = e.sp; w[2] = e.mn; w[3] = e.sn; w[4] = e.sn2; w[5] = e.n; w[6] = e.mean; w[7] = e.ssd;
-    __builtin_memcpy(w + 8, &e.n_neg_inf, 8); __builtin_memcpy(w + 9, &e.n_pos_inf, 8); __builtin_memcpy(w + 10, &e.n_nan, 8);
-}
-FG_HD FgLlElem fg_ll_elem_load(const double *w) {
-    FgLlElem e;
-    e.mx = w[0]; e.sp = w[1]; e.mn = w[2]; e.sn = w[3]; e.sn2 = w[4]; e.n = w[5]; e.mean = w[6]; e.ssd = w[7];
-    __builtin_memcpy(&e.n_neg_inf, w + 8, 8); __builtin_memcpy(&e.n_pos_inf, w + 9, 8); __builtin_memcpy(&e.n_nan, w + 10, 8);
-    return e;
-}
+    // element i takes in element i + s.  Counters add; a side without finite cells passes the other side's finite words through
+    // untouched; else the larger maximum (the smaller minimum) stays the reference point, and the moments merge as FgMoments do.
+    static FG_HD Elem merge(const Elem &a, const Elem &b) {
+        Elem r = a;
+        if (a.m.n == 0.0) r = b;
+        else if (b.m.n != 0.0) {
+            if (a.mx >= b.mx) { r.sp = a.sp + b.sp * exp(b.mx - a.mx); r.mx = a.mx; }
+            else { r.sp = b.sp + a.sp * exp(a.mx - b.mx); r.mx = b.mx; }
+            if (a.mn <= b.mn) { const double f = exp(a.mn - b.mn); r.sn = a.sn + b.sn * f; r.sn2 = a.sn2 + b.sn2 * (f * f); r.mn = a.mn; }
+            else { const double f = exp(b.mn - a.mn); r.sn = b.sn + a.sn * f; r.sn2 = b.sn2 + a.sn2 * (f * f); r.mn = b.mn; }
+            r.m = fg_moments_merge(a.m, b.m);
+        }
+        r.n_neg_inf = a.n_neg_inf + b.n_neg_inf; r.n_pos_inf = a.n_pos_inf + b.n_pos_inf; r.n_nan = a.n_nan + b.n_nan;
+        return r;
+    }
+    static FG_HD void elem_store(const Elem &e, double *w) {
+        w[0] = e.mx; w[1] = e.sp; w[2] = e.mn; w[3] = e.sn; w[4] = e.sn2; w[5] = e.m.n; w[6] = e.m.mean; w[7] = e.m.ssd;
+        __builtin_memcpy(w + 8, &e.n_neg_inf, 8); __builtin_memcpy(w + 9, &e.n_pos_inf, 8); __builtin_memcpy(w + 10, &e.n_nan, 8);
+    }
+    static FG_HD Elem elem_load(const double *w) {
+        Elem e;
+        e.mx = w[0]; e.sp = w[1]; e.mn = w[2]; e.sn = w[3]; e.sn2 = w[4]; e.m.n = w[5]; e.m.mean = w[6]; e.m.ssd = w[7];
+        __builtin_memcpy(&e.n_neg_inf, w + 8, 8); __builtin_memcpy(&e.n_pos_inf, w + 9, 8); __builtin_memcpy(&e.n_nan, w + 10, 8);
+        return e;
+    }
+};
 
 // ------------------------------------------------------------------ host side
 
-struct FgLlLaunch { long long col0 = 0, cols = 0; };          // columns [col0, col0 + cols) of the n_sel x C columns
-struct FgLlLevel { long long m_in = 0, m_out = 0; };          // a tree level: m_in elements per statement -> m_out = ceil(m_in / 256)
-struct FgLlSlice { int k0 = 0, nk = 0; };                     // statements [k0, k0 + nk) of a pool launch (grid y)
-
 struct FgLlPlan {
-    int n_total = 0, n_sel = 0, count = 0;
+    FgDraws draws;
+    int n_sel = 0;
     long long C = 0;
-    std::vector<FgLlLaunch> launches;                         // of every update
-    std::vector<FgLlLevel> levels;                            // of the pooling tree
-    std::vector<FgLlSlice> slices;                            // of every level
+    std::vector<FgPoolLaunch> launches;                       // of every update: columns of the n_sel x C
+    std::vector<FgPoolLevel> levels;                          // of the pooling tree
+    std::vector<FgPoolSlice> slices;                          // statements of every level
 };
 
 inline size_t fg_ll_state_words(const FgLlPlan &P) { return (size_t)FG_LL_WORDS * (size_t)P.n_sel * (size_t)P.C; }
 // the two buffers the tree alternates between, in elements per statement
 inline long long fg_ll_scratch_elems(const FgLlPlan &P) { return P.levels.empty() ? 1 : P.levels[0].m_out; }
 
-// max_grid_x / max_grid_y: FG_LL_MAX_GRID_X / _Y; the tests pass small ones to see the cuts
-inline int fg_ll_init(FgLlPlan &P, int n_total, long long C, int n_sel, std::string *err, long long max_grid_x = FG_LL_MAX_GRID_X,
-                      int max_grid_y = FG_LL_MAX_GRID_Y) {
+// max_grid_x / max_grid_y: the tests pass small ones to see the cuts
+inline int fg_ll_init(FgLlPlan &P, int n_total, long long C, int n_sel, std::string *err, long long max_grid_x = FG_POOL_MAX_GRID_X,
+                      long long max_grid_y = FG_POOL_MAX_GRID_Y) {
     std::string bad;
     if (n_total < 1) bad = "n_total < 1";
     else if (n_sel < 1) bad = "n_sel < 1";
@@ -172,52 +143,11 @@ inline int fg_ll_init(FgLlPlan &P, int n_total, long long C, int n_sel, std::str
     else if (max_grid_x < 1 || max_grid_y < 1) bad = "a grid limit below 1";
     if (!bad.empty()) { if (err) *err = "fg_loglik_stream_new: " + bad; return FG_E_BAD_ARG; }
     P = FgLlPlan();
-    P.n_total = n_total; P.n_sel = n_sel; P.C = C;
-    const long long cols = (long long)n_sel * C, per = max_grid_x * FG_LL_UPDATE_THREADS;
-    for (long long c0 = 0; c0 < cols; c0 += per) {
-        FgLlLaunch L;
-        L.col0 = c0; L.cols = std::min(per, cols - c0);
-        P.launches.push_back(L);
-    }
-    long long m = C;
-    do {
-        FgLlLevel L;
-        L.m_in = m; L.m_out = (m + FG_LL_POOL_THREADS - 1) / FG_LL_POOL_THREADS;
-        P.levels.push_back(L);
-        m = L.m_out;
-    } while (m > 1);
-    for (int k0 = 0; k0 < n_sel; k0 += max_grid_y) {
-        FgLlSlice S;
-        S.k0 = k0; S.nk = std::min(max_grid_y, n_sel - k0);
-        P.slices.push_back(S);
-    }
+    P.draws.n_total = n_total; P.n_sel = n_sel; P.C = C;
+    P.launches = fg_pool_launches((long long)n_sel * C, FG_LL_UPDATE_THREADS, max_grid_x);
+    P.levels = fg_pool_levels(C);
+    P.slices = fg_pool_slices(n_sel, max_grid_y);
     return FG_OK;
-}
-
-// n_chunk more draws: FG_E_STATE past n_total.  n_chunk == 0 is FG_OK (the caller launches nothing).
-inline int fg_ll_take(FgLlPlan &P, int n_chunk, std::string *err) {
-    if (n_chunk < 0) { if (err) *err = "fg_loglik_stream_update: n_chunk < 0"; return FG_E_BAD_ARG; }
-    if (n_chunk > P.n_total - P.count) {
-        if (err) *err = "fg_loglik_stream_update: " + std::to_string(P.count) + " + " + std::to_string(n_chunk) + " draws pass n_total = " + std::to_string(P.n_total);
-        return FG_E_STATE;
-    }
-    P.count += n_chunk;
-    return FG_OK;
-}
-inline void fg_ll_untake(FgLlPlan &P, int n_chunk) { P.count -= n_chunk; }       // a launch that never ran gives its draws back
-
-inline int fg_ll_complete(const FgLlPlan &P, const char *who, std::string *err) {
-    if (P.count == P.n_total) return FG_OK;
-    if (err) *err = std::string(who) + ": " + std::to_string(P.count) + " of " + std::to_string(P.n_total) + " draws have arrived";
-    return FG_E_STATE;
-}
-
-// One block of a tree level on the host: elements e[0 .. n) (n <= 256) by the stride rule; the result is e[0].  The device block
-// runs the same pairs with the missing partners as empty elements.
-inline FgLlElem fg_ll_block_tree(FgLlElem *e, int n) {
-    for (int s = 1; s < n; s *= 2)
-        for (int i = 0; i + s < n; i += 2 * s) e[i] = fg_ll_merge(e[i], e[i + s]);
-    return e[0];
 }
 
 enum { FG_LL_LPPD = 0, FG_LL_MEAN_LL = 1, FG_LL_P_WAIC = 2, FG_LL_ELPD_WAIC = 3, FG_LL_ELPD_LOO = 4, FG_LL_P_LOO = 5, FG_LL_IS_ESS = 6, FG_LL_MAX_WEIGHT = 7 };
@@ -228,13 +158,13 @@ enum { FG_LL_LPPD = 0, FG_LL_MEAN_LL = 1, FG_LL_P_WAIC = 2, FG_LL_ELPD_WAIC = 3,
 inline void fg_ll_finish(const FgLlElem &e, double N, double *fig /*[FG_LL_FIGURES]*/) {
     const double nan = std::nan(""), inf = INFINITY;
     const int64_t a = e.n_neg_inf, b = e.n_pos_inf, z = e.n_nan;
-    const bool none = e.n == 0.0;
+    const bool none = e.m.n == 0.0;
     if (z > 0) { for (int i = 0; i < FG_LL_FIGURES; ++i) fig[i] = nan; return; }
     const double lnN = std::log(N);
     fig[FG_LL_LPPD] = b > 0 ? inf : (none ? -inf : e.mx + std::log(e.sp) - lnN);
     fig[FG_LL_ELPD_LOO] = a > 0 ? -inf : (none ? inf : lnN + e.mn - std::log(e.sn));
-    fig[FG_LL_MEAN_LL] = a > 0 && b > 0 ? nan : (a > 0 ? -inf : (b > 0 ? inf : e.mean));
-    fig[FG_LL_P_WAIC] = a == 0 && b == 0 && N > 1.0 ? e.ssd / (N - 1.0) : nan;
+    fig[FG_LL_MEAN_LL] = a > 0 && b > 0 ? nan : (a > 0 ? -inf : (b > 0 ? inf : e.m.mean));
+    fig[FG_LL_P_WAIC] = a == 0 && b == 0 && N > 1.0 ? e.m.ssd / (N - 1.0) : nan;
     fig[FG_LL_ELPD_WAIC] = fig[FG_LL_LPPD] - fig[FG_LL_P_WAIC];
     fig[FG_LL_P_LOO] = fig[FG_LL_LPPD] - fig[FG_LL_ELPD_LOO];
     const bool ratios = a == 0 && !none;

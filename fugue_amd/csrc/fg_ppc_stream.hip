@@ -10,7 +10,7 @@
 //   variance pass reads the K cells again (from cache); the statistics asked for go to the scratch table [draw][slot][C].
 // k_ppc_stream_update: one thread per (slot, chain); the six state words live in registers for the launch and the piece's draws
 //   are walked in order (k_loglik_stream_update's shape).  No atomics: a column has one writer.  A lane beyond C stores nothing.
-// k_ppc_stream_pool: one block row per slot, one level of the fixed tree on the chain index per launch (k_loglik_stream_pool's shape).
+// k_chain_pool<FgPpcPool, .> (fg_chain_pool.h): one block row per slot, one level of the fixed tree on the chain index per launch.
 #include "fg_engine_internal.h"
 #include "fg_ppc_stream_plan.h"
 
@@ -58,59 +58,6 @@ __global__ __launch_bounds__(FG_PPC_THREADS) void k_ppc_stream_update(const doub
     fg_ppc_state_store(s, state + col, stride);
 }
 
-__device__ __forceinline__ FgPpcElem ppc_shfl_down(const FgPpcElem &e, int s) {
-    FgPpcElem r;
-    r.n = __shfl_down(e.n, s, 64); r.mean = __shfl_down(e.mean, s, 64); r.ssd = __shfl_down(e.ssd, s, 64);
-    r.n_lt = __shfl_down((long long)e.n_lt, s, 64); r.n_eq = __shfl_down((long long)e.n_eq, s, 64);
-    r.n_gt = __shfl_down((long long)e.n_gt, s, 64); r.n_nan = __shfl_down((long long)e.n_nan, s, 64);
-    return r;
-}
-
-// One level: element i of slot k0 + blockIdx.y is the state column (LEAF) or in[k][i]; a block pools 256 consecutive elements (an
-// index past m_in: the empty element, whose merge is the identity) by strides 1 .. 32 inside each wave, 64 and 128 through LDS, and
-// writes out[k][blockIdx.x].  The pairs are those of the stride rule on the chain index, whatever the grid.
-template <bool LEAF>
-__global__ __launch_bounds__(FG_PPC_POOL_THREADS) void k_ppc_stream_pool(const double *in, long long m_in, long long stride, long long k0, double *out, long long m_out) {
-    __shared__ double sh[FG_PPC_POOL_THREADS / 64][FG_PPC_ELEM];
-    const long long i = (long long)blockIdx.x * FG_PPC_POOL_THREADS + threadIdx.x;
-    const long long k = k0 + blockIdx.y;
-    FgPpcElem e = fg_ppc_empty();
-    if (i < m_in) {
-        if (LEAF) {
-            FgPpcState s;
-            fg_ppc_state_load(s, in + k * m_in + i, stride);
-            e = fg_ppc_leaf(s);
-        } else e = fg_ppc_elem_load(in + (k * m_in + i) * FG_PPC_ELEM);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int s = 1; s < 64; s *= 2) {
-        const FgPpcElem o = ppc_shfl_down(e, s);
-        if ((lane & (2 * s - 1)) == 0) e = fg_ppc_merge(e, o);
-    }
-    if (lane == 0) fg_ppc_elem_store(e, sh[wave]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const FgPpcElem lo = fg_ppc_merge(fg_ppc_elem_load(sh[0]), fg_ppc_elem_load(sh[1]));
-        const FgPpcElem hi = fg_ppc_merge(fg_ppc_elem_load(sh[2]), fg_ppc_elem_load(sh[3]));
-        fg_ppc_elem_store(fg_ppc_merge(lo, hi), out + (k * m_out + blockIdx.x) * FG_PPC_ELEM);
-    }
-}
-
-static int need_stream(const fg_ppc_stream *s) {
-    if (!s || !s->e) { fg_set_error("null stream"); return FG_E_BAD_ARG; }
-    if (hipSetDevice(s->e->device) != hipSuccess) { fg_set_error("hipSetDevice failed"); return FG_E_HIP; }
-    return FG_OK;
-}
-
-static int ready(const fg_ppc_stream *s, const char *who) {
-    int rc = need_stream(s);
-    if (rc) return rc;
-    std::string err;
-    rc = fg_ppc_complete(s->P, who, &err);
-    if (rc) fg_set_error(err);
-    return rc;
-}
-
 extern "C" {
 
 int fg_ppc_stream_new(fg_engine *e, int n_total, int n_rows, const int32_t *h_vtypes, int n_checks, const int32_t *h_offsets, const int32_t *h_members,
@@ -143,28 +90,28 @@ int fg_ppc_stream_new(fg_engine *e, int n_total, int n_rows, const int32_t *h_vt
 }
 
 int fg_ppc_stream_update(fg_ppc_stream *s, const void *d_yrep, int n_chunk) {
-    int rc = need_stream(s);
+    int rc = fg_need_stream(s);
     if (rc) return rc;
     std::string err;
-    rc = fg_ppc_take(s->P, n_chunk, &err);
+    rc = s->P.draws.take(n_chunk, "fg_ppc_stream_update", &err);
     if (rc) { fg_set_error(err); return rc; }
     if (n_chunk == 0) return FG_OK;
-    if (!d_yrep) { fg_ppc_untake(s->P, n_chunk); fg_set_error("fg_ppc_stream_update: null table"); return FG_E_BAD_ARG; }
+    if (!d_yrep) { s->P.draws.untake(n_chunk); fg_set_error("fg_ppc_stream_update: null table"); return FG_E_BAD_ARG; }
     const FgPpcPlan &P = s->P;
     bool launched = false;
     for (int t0 = 0; t0 < n_chunk; t0 += P.scratch_draws) {
         const int n_piece = std::min(P.scratch_draws, n_chunk - t0);
         const unsigned long long *cells = (const unsigned long long *)d_yrep + (size_t)t0 * (size_t)P.n_rows * (size_t)P.C;
-        const std::vector<FgPpcSlice> pairs = fg_ppc_pair_slices(P, n_piece);
+        const std::vector<FgPoolSlice> pairs = fg_ppc_pair_slices(P, n_piece);
         for (int pass = 0; pass < 2; ++pass)
-            for (const FgPpcLaunch &L : P.launches) {
+            for (const FgPoolLaunch &L : P.launches) {
                 const unsigned nb = (unsigned)((L.cols + FG_PPC_THREADS - 1) / FG_PPC_THREADS);
-                for (const FgPpcSlice &S : pass == 0 ? pairs : P.slices) {
+                for (const FgPoolSlice &S : pass == 0 ? pairs : P.slices) {
                     const dim3 grid(nb, (unsigned)S.nk), block(FG_PPC_THREADS);
-                    if (pass == 0) hipLaunchKernelGGL(k_ppc_stream_stats, grid, block, 0, s->e->stream, cells, (long long)P.n_rows, P.C, L.c0, L.cols, S.k0, P.n_checks, P.n_slots, s->csr, s->scratch);
-                    else hipLaunchKernelGGL(k_ppc_stream_update, grid, block, 0, s->e->stream, s->scratch, n_piece, P.C, L.c0, L.cols, S.k0, (long long)P.n_slots, s->t_obs, s->state);
+                    if (pass == 0) hipLaunchKernelGGL(k_ppc_stream_stats, grid, block, 0, s->e->stream, cells, (long long)P.n_rows, P.C, L.col0, L.cols, S.k0, P.n_checks, P.n_slots, s->csr, s->scratch);
+                    else hipLaunchKernelGGL(k_ppc_stream_update, grid, block, 0, s->e->stream, s->scratch, n_piece, P.C, L.col0, L.cols, S.k0, (long long)P.n_slots, s->t_obs, s->state);
                     if (hipGetLastError() != hipSuccess) {
-                        if (!launched) fg_ppc_untake(s->P, n_chunk);                  // nothing ran: the draws go back
+                        if (!launched) s->P.draws.untake(n_chunk);                  // nothing ran: the draws go back
                         fg_set_error("fg_ppc_stream_update: a kernel did not launch");
                         return FG_E_HIP;
                     }
@@ -175,7 +122,7 @@ int fg_ppc_stream_update(fg_ppc_stream *s, const void *d_yrep, int n_chunk) {
     return FG_OK;
 }
 
-int fg_ppc_stream_count(const fg_ppc_stream *s) { return s ? s->P.count : 0; }
+int fg_ppc_stream_count(const fg_ppc_stream *s) { return s ? s->P.draws.count : 0; }
 int fg_ppc_stream_n_slots(const fg_ppc_stream *s) { return s ? s->P.n_slots : 0; }
 
 int fg_ppc_stream_observed(const fg_ppc_stream *s, double *h_t_obs) {
@@ -186,33 +133,19 @@ int fg_ppc_stream_observed(const fg_ppc_stream *s, double *h_t_obs) {
 
 int fg_ppc_stream_pooled(fg_ppc_stream *s, int64_t *h_counts, double *h_moments) {
     if (!h_counts || !h_moments) { fg_set_error("fg_ppc_stream_pooled: null output"); return FG_E_BAD_ARG; }
-    const int rc = ready(s, "fg_ppc_stream_pooled");
+    int rc = fg_stream_ready(s, "fg_ppc_stream_pooled");
     if (rc) return rc;
     const FgPpcPlan &P = s->P;
-    fg_engine *e = s->e;
-    const double *in = s->state;
-    int side = 0;
-    for (size_t l = 0; l < P.levels.size(); ++l) {
-        const FgPpcLevel &L = P.levels[l];
-        for (const FgPpcSlice &S : P.slices) {
-            const dim3 grid((unsigned)L.m_out, (unsigned)S.nk), block(FG_PPC_POOL_THREADS);
-            if (l == 0) hipLaunchKernelGGL(k_ppc_stream_pool<true>, grid, block, 0, e->stream, in, L.m_in, (long long)P.n_slots * P.C, S.k0, s->tree[side], L.m_out);
-            else hipLaunchKernelGGL(k_ppc_stream_pool<false>, grid, block, 0, e->stream, in, L.m_in, 0ll, S.k0, s->tree[side], L.m_out);
-            HIPCHK(hipGetLastError());
-        }
-        in = s->tree[side];
-        side ^= 1;
-    }
-    std::vector<double> h((size_t)P.n_slots * FG_PPC_ELEM);
-    HIPCHK(hipMemcpyAsync(h.data(), in, h.size() * 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int k = 0; k < P.n_slots; ++k) fg_ppc_finish(fg_ppc_elem_load(&h[(size_t)k * FG_PPC_ELEM]), h_counts + 5 * (size_t)k, h_moments + 2 * (size_t)k);
+    std::vector<double> h;
+    rc = fg_chain_pool_run<FgPpcPool>(s->e->stream, P.levels, P.slices, s->state, (long long)P.n_slots * P.C, s->tree, h);
+    if (rc) return rc;
+    for (int k = 0; k < P.n_slots; ++k) fg_ppc_finish(FgPpcPool::elem_load(&h[(size_t)k * FG_PPC_ELEM]), h_counts + 5 * (size_t)k, h_moments + 2 * (size_t)k);
     return FG_OK;
 }
 
 int fg_ppc_stream_chains(fg_ppc_stream *s, int slot, int64_t *h_counts) {
     if (!h_counts) { fg_set_error("fg_ppc_stream_chains: null output"); return FG_E_BAD_ARG; }
-    const int rc = ready(s, "fg_ppc_stream_chains");
+    const int rc = fg_stream_ready(s, "fg_ppc_stream_chains");
     if (rc) return rc;
     const FgPpcPlan &P = s->P;
     if (slot < 0 || slot >= P.n_slots) { fg_set_error("fg_ppc_stream_chains: slot " + std::to_string(slot) + " lies outside [0, " + std::to_string(P.n_slots) + ")"); return FG_E_BAD_ARG; }

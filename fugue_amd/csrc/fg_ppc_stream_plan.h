@@ -14,28 +14,15 @@
 // statements: a model with that many selects the checks it needs.  A column has one writer and is walked in draw order, so the state
 // after a run does not depend on the chunking, bit for bit.  The pivoted sums are k_diag_stream_update's.
 //
-// Read-out: counters pool over chains by integer addition; a chain's sums become (n, mean, ssd) by fg_diag_stream's identities and the
-// chains merge by the FIXED tree on the chain index of fg_loglik_stream_plan.h (stride s = 1, 2, 4, ...: element i, a multiple of
-// 2 s, takes in element i + s when that exists) with its pair rule for (n, mean, ssd); run level by level, 256 elements per block.
+// Read-out: counters pool over chains by integer addition and the moments by (n, mean, ssd) merges, along fg_chain_pool.h's fixed tree
+// on the chain index, FgPpcPool its elements.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
-#include <algorithm>
 #include <cmath>
-#include <string>
-#include <vector>
 
-#include "../../include/fugue_amd.h"
-
-#ifndef FG_HD
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define FG_HD __host__ __device__ __forceinline__
-#else
-#define FG_HD inline
-#endif
-#endif
+#include "fg_chain_pool.h"
 
 #if defined(__HIPCC__)
 #define FG_PPC_UNROLL _Pragma("unroll 8")   // the member loads of several iterations in flight; the sums stay in member order
@@ -45,9 +32,6 @@
 #define FG_PPC_WORDS 6               // state words per (slot, chain)
 #define FG_PPC_ELEM 7                // a tree element in memory: n, mean, ssd, then n_lt, n_eq, n_gt, n_nan as int64 bits
 #define FG_PPC_THREADS 256           // of the statistics and the update kernel
-#define FG_PPC_POOL_THREADS 256      // elements per block of a tree level; a power of two (the block is a subtree)
-#define FG_PPC_MAX_GRID_X 0x7fffff   // blocks along the chains of one launch: threads stay below 2^31
-#define FG_PPC_MAX_GRID_Y 65535
 #define FG_PPC_SCRATCH_DRAWS 16      // draws whose statistics the scratch table holds: a longer chunk is walked in pieces of that many
 #define FG_PPC_COPY 0                // conversion of a member's cells, as fg_diag_cells_f64: f64 bits copied
 #define FG_PPC_UNSIGNED 1            // (double)(uint64_t)
@@ -124,72 +108,56 @@ FG_HD void fg_ppc_update(FgPpcState &s, double T, double t_obs) {
     s.s1 += d; s.s2 += d * d; s.n_fin += 1;
 }
 
-struct FgPpcElem {                   // a tree element: a chain, or chains pooled (the n, mean, ssd part of FgLlElem, and the counters)
-    double n, mean, ssd;             // n: the finite draws (below 2^47, exact)
-    int64_t n_lt, n_eq, n_gt, n_nan;
+struct FgPpcElem {                   // a tree element: a chain, or chains pooled
+    FgMoments m;                     // of the finite draws
+    int64_t n_lt = 0, n_eq = 0, n_gt = 0, n_nan = 0;
 };
 
-FG_HD FgPpcElem fg_ppc_empty() {
-    FgPpcElem e;
-    e.n = e.mean = e.ssd = 0.0;
-    e.n_lt = e.n_eq = e.n_gt = e.n_nan = 0;
-    return e;
-}
-
-// a chain as a tree leaf: (n, mean, ssd) by fg_diag_stream's identities, mu = s1 / n, mean = pivot + mu, ssd = s2 - s1 mu
-FG_HD FgPpcElem fg_ppc_leaf(const FgPpcState &s) {
-    FgPpcElem e = fg_ppc_empty();
-    e.n_lt = (int64_t)s.n_lt; e.n_eq = (int64_t)s.n_eq; e.n_gt = (int64_t)s.n_gt; e.n_nan = (int64_t)s.n_nan;
-    if (s.n_fin == 0) return e;
-    e.n = (double)s.n_fin;
-    const double mu = s.s1 / e.n;
-    e.mean = s.pivot + mu;
-    e.ssd = s.s2 - s.s1 * mu;
-    return e;
-}
-
-// element i takes in element i + s: counters add; a side without finite draws passes the other's moments through untouched; else
-// Chan's formulas in the order fg_ll_merge writes them
-FG_HD FgPpcElem fg_ppc_merge(const FgPpcElem &a, const FgPpcElem &b) {
-    FgPpcElem r = a;
-    if (a.n == 0.0) r = b;
-    else if (b.n != 0.0) {
-        const double n = a.n + b.n, delta = b.mean - a.mean;
-        r.n = n;
-        r.mean = a.mean + delta * (b.n / n);
-        r.ssd = a.ssd + b.ssd + delta * delta * (a.n * b.n / n);
+struct FgPpcPool {
+    typedef FgPpcElem Elem;
+    typedef FgPpcState State;
+    enum { WORDS = FG_PPC_ELEM };
+    static FG_HD Elem empty() { return Elem(); }
+    static FG_HD void state_load(State &s, const double *w, long long stride) { fg_ppc_state_load(s, w, stride); }
+    // a chain as a tree leaf
+    static FG_HD Elem leaf(const State &s) {
+        Elem e;
+        e.m = fg_moments_leaf((double)s.n_fin, s.pivot, s.s1, s.s2);
+        e.n_lt = (int64_t)s.n_lt; e.n_eq = (int64_t)s.n_eq; e.n_gt = (int64_t)s.n_gt; e.n_nan = (int64_t)s.n_nan;
+        return e;
     }
-    r.n_lt = a.n_lt + b.n_lt; r.n_eq = a.n_eq + b.n_eq; r.n_gt = a.n_gt + b.n_gt; r.n_nan = a.n_nan + b.n_nan;
-    return r;
-}
-
-FG_HD void fg_ppc_elem_store(const FgPpcElem &e, double *w) {
-    w[0] = e.n; w[1] = e.mean; w[2] = e.ssd;
-    __builtin_memcpy(w + 3, &e.n_lt, 8); __builtin_memcpy(w + 4, &e.n_eq, 8); __builtin_memcpy(w + 5, &e.n_gt, 8); __builtin_memcpy(w + 6, &e.n_nan, 8);
-}
-FG_HD FgPpcElem fg_ppc_elem_load(const double *w) {
-    FgPpcElem e;
-    e.n = w[0]; e.mean = w[1]; e.ssd = w[2];
-    __builtin_memcpy(&e.n_lt, w + 3, 8); __builtin_memcpy(&e.n_eq, w + 4, 8); __builtin_memcpy(&e.n_gt, w + 5, 8); __builtin_memcpy(&e.n_nan, w + 6, 8);
-    return e;
-}
+    // element i takes in element i + s: counters add, the moments merge
+    static FG_HD Elem merge(const Elem &a, const Elem &b) {
+        Elem r;
+        r.m = fg_moments_merge(a.m, b.m);
+        r.n_lt = a.n_lt + b.n_lt; r.n_eq = a.n_eq + b.n_eq; r.n_gt = a.n_gt + b.n_gt; r.n_nan = a.n_nan + b.n_nan;
+        return r;
+    }
+    static FG_HD void elem_store(const Elem &e, double *w) {
+        w[0] = e.m.n; w[1] = e.m.mean; w[2] = e.m.ssd;
+        __builtin_memcpy(w + 3, &e.n_lt, 8); __builtin_memcpy(w + 4, &e.n_eq, 8); __builtin_memcpy(w + 5, &e.n_gt, 8); __builtin_memcpy(w + 6, &e.n_nan, 8);
+    }
+    static FG_HD Elem elem_load(const double *w) {
+        Elem e;
+        e.m.n = w[0]; e.m.mean = w[1]; e.m.ssd = w[2];
+        __builtin_memcpy(&e.n_lt, w + 3, 8); __builtin_memcpy(&e.n_eq, w + 4, 8); __builtin_memcpy(&e.n_gt, w + 5, 8); __builtin_memcpy(&e.n_nan, w + 6, 8);
+        return e;
+    }
+};
 
 // ------------------------------------------------------------------ host side
 
-struct FgPpcLaunch { long long c0 = 0, cols = 0; };           // chains [c0, c0 + cols) of a statistics / update launch (grid x)
-struct FgPpcLevel { long long m_in = 0, m_out = 0; };         // a tree level: m_in elements per slot -> m_out = ceil(m_in / 256)
-struct FgPpcSlice { long long k0 = 0, nk = 0; };              // slots (update, pool) or (draw, check) pairs (statistics) of a launch (grid y)
-
 struct FgPpcPlan {
-    int n_total = 0, n_rows = 0, n_checks = 0, n_slots = 0, count = 0, scratch_draws = 0;
-    long long C = 0, max_grid_y = FG_PPC_MAX_GRID_Y;
+    FgDraws draws;
+    int n_rows = 0, n_checks = 0, n_slots = 0, scratch_draws = 0;
+    long long C = 0, max_grid_y = FG_POOL_MAX_GRID_Y;
     std::vector<int32_t> offsets;                             // [n_checks + 1] into members
     std::vector<int32_t> members;                             // row << 2 | conversion, the CSR list the statistics kernel reads
     std::vector<int32_t> mask, slot0;                         // [n_checks]: the statistics asked for, the check's first slot
     std::vector<double> t_obs;                                // [n_slots]: fg_ppc_stats of the observed vectors
-    std::vector<FgPpcLaunch> launches;                        // chain ranges of every statistics / update launch
-    std::vector<FgPpcLevel> levels;                           // of the pooling tree
-    std::vector<FgPpcSlice> slices;                           // slot ranges of an update launch and of every tree level
+    std::vector<FgPoolLaunch> launches;                       // chain ranges of every statistics / update launch
+    std::vector<FgPoolLevel> levels;                          // of the pooling tree
+    std::vector<FgPoolSlice> slices;                          // slot ranges of an update launch and of every tree level
 };
 
 inline size_t fg_ppc_state_words(const FgPpcPlan &P) { return (size_t)FG_PPC_WORDS * (size_t)P.n_slots * (size_t)P.C; }
@@ -200,10 +168,10 @@ inline int fg_ppc_how(int vtype) {
     return vtype == FG_F64 ? FG_PPC_COPY : vtype == FG_U64 ? FG_PPC_UNSIGNED : (vtype == FG_BOOL || vtype == FG_USIZE || vtype == FG_I64) ? FG_PPC_SIGNED : -1;
 }
 
-// max_grid_x / max_grid_y: FG_PPC_MAX_GRID_X / _Y; the tests pass small ones to see the cuts
+// max_grid_x / max_grid_y: the tests pass small ones to see the cuts
 inline int fg_ppc_init(FgPpcPlan &P, int n_total, long long C, int n_rows, const int32_t *vtypes, int n_checks, const int32_t *offsets, const int32_t *members,
-                       const int32_t *stat_mask, const double *observed, std::string *err, long long max_grid_x = FG_PPC_MAX_GRID_X,
-                       long long max_grid_y = FG_PPC_MAX_GRID_Y) {
+                       const int32_t *stat_mask, const double *observed, std::string *err, long long max_grid_x = FG_POOL_MAX_GRID_X,
+                       long long max_grid_y = FG_POOL_MAX_GRID_Y) {
     std::string bad;
     if (n_total < 1) bad = "n_total < 1";
     else if (C < 1) bad = "no chains";
@@ -224,7 +192,7 @@ inline int fg_ppc_init(FgPpcPlan &P, int n_total, long long C, int n_rows, const
     }
     if (!bad.empty()) { if (err) *err = "fg_ppc_stream_new: " + bad; return FG_E_BAD_ARG; }
     P = FgPpcPlan();
-    P.n_total = n_total; P.n_rows = n_rows; P.n_checks = n_checks; P.C = C; P.max_grid_y = max_grid_y;
+    P.draws.n_total = n_total; P.n_rows = n_rows; P.n_checks = n_checks; P.C = C; P.max_grid_y = max_grid_y;
     P.scratch_draws = std::min(n_total, FG_PPC_SCRATCH_DRAWS);
     P.offsets.assign(offsets, offsets + n_checks + 1);
     for (int q = 0; q < n_checks; ++q) {
@@ -237,68 +205,18 @@ inline int fg_ppc_init(FgPpcPlan &P, int n_total, long long C, int n_rows, const
         for (int st = 0; st < FG_PPC_N_STATS; ++st)
             if ((stat_mask[q] >> st) & 1) { P.t_obs.push_back(T[st]); ++P.n_slots; }
     }
-    const long long per = max_grid_x * FG_PPC_THREADS;
-    for (long long c0 = 0; c0 < C; c0 += per) {
-        FgPpcLaunch L;
-        L.c0 = c0; L.cols = std::min(per, C - c0);
-        P.launches.push_back(L);
-    }
-    long long m = C;
-    do {
-        FgPpcLevel L;
-        L.m_in = m; L.m_out = (m + FG_PPC_POOL_THREADS - 1) / FG_PPC_POOL_THREADS;
-        P.levels.push_back(L);
-        m = L.m_out;
-    } while (m > 1);
-    for (long long k0 = 0; k0 < P.n_slots; k0 += max_grid_y) {
-        FgPpcSlice S;
-        S.k0 = k0; S.nk = std::min<long long>(max_grid_y, P.n_slots - k0);
-        P.slices.push_back(S);
-    }
+    P.launches = fg_pool_launches(C, FG_PPC_THREADS, max_grid_x);
+    P.levels = fg_pool_levels(C);
+    P.slices = fg_pool_slices(P.n_slots, max_grid_y);
     return FG_OK;
 }
 
 // the (draw, check) pairs of a piece of n_piece draws, cut at the grid limit: pair p is draw p / n_checks, check p % n_checks
-inline std::vector<FgPpcSlice> fg_ppc_pair_slices(const FgPpcPlan &P, int n_piece) {
-    std::vector<FgPpcSlice> out;
-    const long long pairs = (long long)n_piece * P.n_checks;
-    for (long long p0 = 0; p0 < pairs; p0 += P.max_grid_y) {
-        FgPpcSlice S;
-        S.k0 = p0; S.nk = std::min(P.max_grid_y, pairs - p0);
-        out.push_back(S);
-    }
-    return out;
-}
-
-// n_chunk more draws: FG_E_STATE past n_total.  n_chunk == 0 is FG_OK (the caller launches nothing).
-inline int fg_ppc_take(FgPpcPlan &P, int n_chunk, std::string *err) {
-    if (n_chunk < 0) { if (err) *err = "fg_ppc_stream_update: n_chunk < 0"; return FG_E_BAD_ARG; }
-    if (n_chunk > P.n_total - P.count) {
-        if (err) *err = "fg_ppc_stream_update: " + std::to_string(P.count) + " + " + std::to_string(n_chunk) + " draws pass n_total = " + std::to_string(P.n_total);
-        return FG_E_STATE;
-    }
-    P.count += n_chunk;
-    return FG_OK;
-}
-inline void fg_ppc_untake(FgPpcPlan &P, int n_chunk) { P.count -= n_chunk; }     // a launch that never ran gives its draws back
-
-inline int fg_ppc_complete(const FgPpcPlan &P, const char *who, std::string *err) {
-    if (P.count == P.n_total) return FG_OK;
-    if (err) *err = std::string(who) + ": " + std::to_string(P.count) + " of " + std::to_string(P.n_total) + " draws have arrived";
-    return FG_E_STATE;
-}
-
-// One block of a tree level on the host: elements e[0 .. n) (n <= 256) by the stride rule; the result is e[0].  The device block
-// runs the same pairs with the missing partners as empty elements.
-inline FgPpcElem fg_ppc_block_tree(FgPpcElem *e, int n) {
-    for (int s = 1; s < n; s *= 2)
-        for (int i = 0; i + s < n; i += 2 * s) e[i] = fg_ppc_merge(e[i], e[i + s]);
-    return e[0];
-}
+inline std::vector<FgPoolSlice> fg_ppc_pair_slices(const FgPpcPlan &P, int n_piece) { return fg_pool_slices((long long)n_piece * P.n_checks, P.max_grid_y); }
 
 // a pooled element as the read-out hands it over: counts lt eq gt nan fin, moments mean ssd (NaN without a finite draw)
 inline void fg_ppc_finish(const FgPpcElem &e, int64_t *counts /*[5]*/, double *moments /*[2]*/) {
-    counts[0] = e.n_lt; counts[1] = e.n_eq; counts[2] = e.n_gt; counts[3] = e.n_nan; counts[4] = (int64_t)e.n;
-    moments[0] = e.n == 0.0 ? fg_ppc_nan() : e.mean;
-    moments[1] = e.n == 0.0 ? fg_ppc_nan() : e.ssd;
+    counts[0] = e.n_lt; counts[1] = e.n_eq; counts[2] = e.n_gt; counts[3] = e.n_nan; counts[4] = (int64_t)e.m.n;
+    moments[0] = e.m.n == 0.0 ? fg_ppc_nan() : e.m.mean;
+    moments[1] = e.m.n == 0.0 ? fg_ppc_nan() : e.m.ssd;
 }

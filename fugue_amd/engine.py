@@ -956,15 +956,46 @@ class Engine:
         return ptr
 
 
-class DiagStream:
+class _Stream:
+    """What the stream classes share: the engine, the handle `h` of the C object (None before it exists and once it is closed), its
+    release through the entry the subclass names in `_free`, and the check of the integer arguments."""
+
+    _free = None                     # "fg_..._free"
+    engine, h = None, None
+
+    @staticmethod
+    def _integers(**named):
+        for name, v in named.items():
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the stream is closed")
+        return self.h
+
+    def close(self):
+        if self.h:
+            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
+                getattr(lib(), self._free)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DiagStream(_Stream):
     """`fg_diag_stream` (fg_diag_stream.hip): split R-hat, multi-chain ESS and the pooled mean / std of a run handed over in chunks.
     Constant memory per (coordinate, chain): (3 K + 7) doubles, K = `max_lag` rounded up to a multiple of 32.  Close it before its
     engine."""
 
+    _free = "fg_diag_stream_free"
+
     def __init__(self, engine: Engine, n_total: int, d: int, max_lag: int = 64):
-        for name, v in (("n_total", n_total), ("d", d), ("max_lag", max_lag)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        self._integers(n_total=n_total, d=d, max_lag=max_lag)
         if n_total < 1:
             raise ValueError("n_total must be at least 1")
         if not 1 <= d <= 65535:
@@ -977,11 +1008,6 @@ class DiagStream:
         out = C.c_void_p()
         _check(lib().fg_diag_stream_new(engine.h, self.n, self.d, int(max_lag), C.byref(out)))
         self.h = out.value
-
-    def _handle(self):
-        if not self.h:
-            raise ValueError("the stream is closed")
-        return self.h
 
     def update(self, d_draws: int, n_chunk: int):
         """The next `n_chunk` draws, a device buffer [n_chunk][d][C]."""
@@ -1018,29 +1044,18 @@ class DiagStream:
         return dict(r_hat=rhat, ess=ess if want_ess else None, mean=mean, std=std, chains=tot.value,
                     exchange_bytes=int(lib().fg_diag_exchange_bytes(self.engine.h)))
 
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
-                lib().fg_diag_stream_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class DiagQuantileStream:
+class DiagQuantileStream(_Stream):
     """`fg_diag_qstream` (fg_diag_qstream.hip): summarize_f64_parameter's quantiles (diagnostics.rs:355-371) by exact radix select
     over a run that is presented once per pass.  A pass is `n_total` draws through `update`, then `end_pass()`; while that returns
     False the same draws must be presented again (in any chunking).  A pass that does not reproduce the previous one raises
     EngineError (FG_E_STATE).  Device memory: d x len(probs) x (2^digit_bits counters + capacity keys).  Close it before its engine."""
 
+    _free = "fg_diag_qstream_free"
+
     def __init__(self, engine: Engine, n_total: int, d: int, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digit_bits: int = 12, capacity: int = 65536):
-        for name, v in (("n_total", n_total), ("d", d), ("digit_bits", digit_bits), ("capacity", capacity)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        self._integers(n_total=n_total, d=d, digit_bits=digit_bits, capacity=capacity)
         pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
         if n_total < 1:
             raise ValueError("n_total must be at least 1")
@@ -1059,11 +1074,6 @@ class DiagQuantileStream:
         out = C.c_void_p()
         _check(lib().fg_diag_qstream_new(engine.h, self.n, self.d, _dp(pr), pr.size, int(digit_bits), int(capacity), C.byref(out)))
         self.h = out.value
-
-    def _handle(self):
-        if not self.h:
-            raise ValueError("the stream is closed")
-        return self.h
 
     def update(self, d_draws: int, n_chunk: int):
         """The next `n_chunk` draws of the current pass, a device buffer [n_chunk][d][C]."""
@@ -1092,28 +1102,17 @@ class DiagQuantileStream:
         _check(lib().fg_diag_qstream_result(self._handle(), _dp(out), sp.ctypes.data_as(C.POINTER(C.c_int32))))
         return out, sp
 
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
-                lib().fg_diag_qstream_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class DiagCountStream:
+class DiagCountStream(_Stream):
     """`fg_diag_cstream` (fg_diag_cstream.hip): exact posterior frequency tables of integer rows (the tabulation of the reference's
     extract_bool_values / extract_u64_values / extract_usize_values / extract_i64_values, diagnostics.rs:76-98) of a run handed over
     in chunks of cells [n_chunk][n_rec][C].  Integer sums: the result does not depend on the chunking.  Close it before its engine."""
 
+    _free = "fg_diag_cstream_free"
+
     def __init__(self, engine: Engine, n_total: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], lo: Sequence[int], bins: Sequence[int]):
-        for name, v in (("n_total", n_total), ("n_rec", n_rec)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        self._integers(n_total=n_total, n_rec=n_rec)
         self.rows, self.vtypes = [int(r) for r in rows], [int(v) for v in vtypes]
         self.lo, self.bins = [int(v) for v in lo], [int(b) for b in bins]
         nw = len(self.rows)
@@ -1129,11 +1128,6 @@ class DiagCountStream:
         i32 = lambda v: (C.c_int32 * nw)(*v)
         _check(lib().fg_diag_cstream_new(engine.h, self.n, self.n_rec, i32(self.rows), i32(self.vtypes), (C.c_int64 * nw)(*self.lo), i32(self.bins), nw, C.byref(out)))
         self.h = out.value
-
-    def _handle(self):
-        if not self.h:
-            raise ValueError("the stream is closed")
-        return self.h
 
     def update(self, d_cells: int, n_chunk: int):
         """The next `n_chunk` draws, a device buffer of cells [n_chunk][n_rec][C]."""
@@ -1159,17 +1153,6 @@ class DiagCountStream:
         unsigned = lambda a: [int(v) & (2 ** 64 - 1) if self.vtypes[k] == M.U64 else int(v) for k, v in enumerate(a)]
         return dict(counts=counts, below=below, above=above, min=unsigned(mn), max=unsigned(mx))
 
-    def close(self):
-        if getattr(self, "h", None):
-            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
-                lib().fg_diag_cstream_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 LL_POOLED, LL_FIGURES = 8, 8                # FG_LL_POOLED, FG_LL_FIGURES
@@ -1177,27 +1160,22 @@ LL_POOLED_WORDS = ("mx", "sp", "mn", "sn", "sn2", "n_fin", "mean", "ssd")
 LL_FIGURE_NAMES = ("lppd", "mean_ll", "p_waic", "elpd_waic", "elpd_loo", "p_loo", "is_ess", "max_weight")
 
 
-class LoglikStream:
+class LoglikStream(_Stream):
     """`fg_loglik_stream` (fg_loglik_stream.hip): WAIC and importance-sampling LOO per observe statement from the pointwise
     log-likelihood of a run handed over in chunks [n_chunk][n_sel][C] of doubles (`Engine.predict_eval`'s `loglik` table).  Every
     (statement, chain) column is updated in draw order by one thread and the chains are pooled by a fixed tree on the chain index, so
     the result does not depend on the chunking, bit for bit.  Device memory: 80 x n_sel x C bytes (5.4 GB at n_sel = 1 024 and
     C = 65 536; select the statements to compare with `predict_eval`'s `sel`).  Close it before its engine."""
 
+    _free = "fg_loglik_stream_free"
+
     def __init__(self, engine: Engine, n_total: int, n_sel: int):
-        for name, v in (("n_total", n_total), ("n_sel", n_sel)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, not {type(v).__name__}")
+        self._integers(n_total=n_total, n_sel=n_sel)
         self.engine, self.n, self.n_sel = engine, int(n_total), int(n_sel)
         self.h = None
         out = C.c_void_p()
         _check(lib().fg_loglik_stream_new(engine.h, self.n, self.n_sel, C.byref(out)))
         self.h = out.value
-
-    def _handle(self):
-        if not self.h:
-            raise ValueError("the stream is closed")
-        return self.h
 
     def update(self, d_loglik: int, n_chunk: int):
         """The next `n_chunk` draws, a device buffer of doubles [n_chunk][n_sel][C]; asynchronous.  n_chunk = 0 does nothing."""
@@ -1222,19 +1200,7 @@ class LoglikStream:
         out.update(n_neg_inf=counts[:, 0].copy(), n_pos_inf=counts[:, 1].copy(), n_nan=counts[:, 2].copy())
         return out
 
-    def free(self):
-        if getattr(self, "h", None):
-            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
-                lib().fg_loglik_stream_free(self.h)
-            self.h = None
-
-    close = free
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    free = _Stream.close
 
 
 PPC_STATS = ("mean", "var", "min", "max", "sum")          # FG_PPC_MEAN .. FG_PPC_SUM
@@ -1242,7 +1208,7 @@ PPC_COUNTS = ("n_lt", "n_eq", "n_gt", "n_nan", "n_fin")
 PPC_SCRATCH_DRAWS = 16                                    # FG_PPC_SCRATCH_DRAWS (fg_ppc_stream_plan.h): an update walks its chunk in pieces of that many draws
 
 
-class PpcStream:
+class PpcStream(_Stream):
     """`fg_ppc_stream` (fg_ppc_stream.hip): test statistics of every replicated data set of a run handed over in chunks
     [n_chunk][n_rows][C] of raw cells (`Engine.predict_eval`'s cell table), compared with the observed ones -- what the reference's
     workflows do on the host after replicating the data (tests/end_to_end_workflows.rs:650-745).  A slot is a (check, statistic)
@@ -1250,9 +1216,10 @@ class PpcStream:
     one thread and the chains are pooled by a fixed tree on the chain index, so the result does not depend on the chunking, bit for
     bit.  Device memory: 48 x n_slots x C bytes of state and a scratch table of 16 draws' statistics.  Close it before its engine."""
 
+    _free = "fg_ppc_stream_free"
+
     def __init__(self, engine: Engine, n_total: int, vtypes: Sequence[int], checks):
-        if isinstance(n_total, bool) or not isinstance(n_total, (int, np.integer)):
-            raise TypeError(f"n_total must be an integer, not {type(n_total).__name__}")
+        self._integers(n_total=n_total)
         self.engine, self.n, self.h = engine, int(n_total), None
         vt = [int(v) for v in vtypes]
         offsets, members, masks, observed, self.slots = [0], [], [], [], []
@@ -1275,11 +1242,6 @@ class PpcStream:
                                        (C.c_double * max(1, len(observed)))(*observed), C.byref(out)))
         self.h = out.value
         self.n_slots = int(lib().fg_ppc_stream_n_slots(self.h))
-
-    def _handle(self):
-        if not self.h:
-            raise ValueError("the stream is closed")
-        return self.h
 
     def update(self, d_yrep: int, n_chunk: int):
         """The next `n_chunk` draws, a device buffer of cells [n_chunk][n_rows][C]; asynchronous.  n_chunk = 0 does nothing."""
@@ -1310,19 +1272,7 @@ class PpcStream:
         _check(lib().fg_ppc_stream_chains(self._handle(), int(slot), counts.ctypes.data_as(C.POINTER(C.c_int64))))
         return {name: counts[i].copy() for i, name in enumerate(PPC_COUNTS)}
 
-    def free(self):
-        if getattr(self, "h", None):
-            if getattr(self.engine, "h", None):          # the state lives in the engine's device context
-                lib().fg_ppc_stream_free(self.h)
-            self.h = None
-
-    close = free
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    free = _Stream.close
 
 
 # ---- population-wide device primitives (no program needed) -----------------------------------

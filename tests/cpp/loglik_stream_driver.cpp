@@ -1,7 +1,7 @@
-// loglik_stream_driver.cpp -- the log-likelihood stream on the host: fg_loglik_stream_plan.h (the update, merge and finish functions
-// the device code runs, the launch cuts and the tree schedule) with the two kernels of fg_loglik_stream.hip replaced by plain
-// loops.  tests/test_loglik_stream_cpu.py builds it with g++ (once more with -fsanitize=address,undefined) and compares its output
-// bit for bit with the Python restatement.
+// loglik_stream_driver.cpp -- the log-likelihood stream on the host: fg_loglik_stream_plan.h and fg_chain_pool.h (the update, merge and
+// finish functions the device code runs, the launch cuts and the tree schedule) with k_loglik_stream_update and k_chain_pool replaced
+// by plain loops.  tests/test_loglik_stream_cpu.py builds it with g++ (once more with -fsanitize=address,undefined) and compares its
+// output bit for bit with the Python restatement.
 //
 //   loglik_stream_driver N_TOTAL N_SEL C FILE C1,C2,... [MAX_GRID_X MAX_GRID_Y]
 //
@@ -24,8 +24,8 @@ int main(int argc, char **argv) {
     if (argc < 6) { std::fprintf(stderr, "usage: loglik_stream_driver N_TOTAL N_SEL C FILE C1,C2,... [MAX_GRID_X MAX_GRID_Y]\n"); return 1; }
     const int n_total = std::atoi(argv[1]), n_sel = std::atoi(argv[2]);
     const long long C = std::atoll(argv[3]);
-    const long long gx = argc > 6 ? std::atoll(argv[6]) : FG_LL_MAX_GRID_X;
-    const int gy = argc > 7 ? std::atoi(argv[7]) : FG_LL_MAX_GRID_Y;
+    const long long gx = argc > 6 ? std::atoll(argv[6]) : FG_POOL_MAX_GRID_X;
+    const long long gy = argc > 7 ? std::atoll(argv[7]) : FG_POOL_MAX_GRID_Y;
     FgLlPlan P;
     std::string err;
     int rc = fg_ll_init(P, n_total, C, n_sel, &err, gx, gy);
@@ -43,11 +43,11 @@ int main(int argc, char **argv) {
         if (end == std::string::npos) end = chunks.size();
         const int n_c = std::atoi(chunks.substr(at, end - at).c_str());
         at = end + 1;
-        rc = fg_ll_take(P, n_c, &err);
+        rc = P.draws.take(n_c, "fg_loglik_stream_update", &err);
         if (rc) return fail(rc, err);
         if (n_c == 0) continue;
         const double *chunk = x.data() + (size_t)t0 * (size_t)stride;
-        for (const FgLlLaunch &L : P.launches)                                     // k_loglik_stream_update
+        for (const FgPoolLaunch &L : P.launches)                                   // k_loglik_stream_update
             for (long long j = 0; j < L.cols; ++j) {
                 const long long col = L.col0 + j;
                 FgLlState s;
@@ -57,35 +57,14 @@ int main(int argc, char **argv) {
             }
         t0 += n_c;
     }
-    rc = fg_ll_complete(P, "fg_loglik_stream_result", &err);
+    rc = P.draws.complete("fg_loglik_stream_result", &err);
     if (rc) return fail(rc, err);
-    // k_loglik_stream_pool, level by level
-    std::vector<FgLlElem> cur, next;
-    for (size_t l = 0; l < P.levels.size(); ++l) {
-        const FgLlLevel &L = P.levels[l];
-        next.assign((size_t)n_sel * (size_t)L.m_out, fg_ll_empty());
-        for (const FgLlSlice &S : P.slices)
-            for (int k = S.k0; k < S.k0 + S.nk; ++k)
-                for (long long blk = 0; blk < L.m_out; ++blk) {
-                    FgLlElem e[FG_LL_POOL_THREADS];
-                    const long long i0 = blk * FG_LL_POOL_THREADS;
-                    const int n = (int)std::min<long long>(FG_LL_POOL_THREADS, L.m_in - i0);
-                    for (int i = 0; i < n; ++i) {
-                        if (l == 0) {
-                            FgLlState s;
-                            fg_ll_state_load(s, state.data() + (long long)k * C + i0 + i, stride);
-                            e[i] = fg_ll_leaf(s);
-                        } else e[i] = cur[(size_t)k * (size_t)L.m_in + (size_t)(i0 + i)];
-                    }
-                    next[(size_t)k * (size_t)L.m_out + (size_t)blk] = fg_ll_block_tree(e, n);
-                }
-        cur.swap(next);
-    }
+    const std::vector<FgLlElem> cur = fg_pool_host<FgLlPool>(P.levels, P.slices, state.data(), stride);      // k_chain_pool, level by level
     const double N = (double)n_total * (double)C;
     for (int k = 0; k < n_sel; ++k) {
         double w[FG_LL_ELEM], fig[FG_LL_FIGURES];
-        fg_ll_elem_store(cur[(size_t)k], w);
-        const FgLlElem e = fg_ll_elem_load(w);
+        FgLlPool::elem_store(cur[(size_t)k], w);
+        const FgLlElem e = FgLlPool::elem_load(w);
         std::printf("pooled %d", k);
         for (int i = 0; i < FG_LL_POOLED; ++i) std::printf(" %016llx", bits(w[i]));
         std::printf("\ncounts %d %lld %lld %lld\n", k, (long long)e.n_neg_inf, (long long)e.n_pos_inf, (long long)e.n_nan);

@@ -1,7 +1,7 @@
-// ppc_stream_driver.cpp -- the posterior predictive check stream on the host: fg_ppc_stream_plan.h (the statistics, update, merge and
-// finish functions the device code runs, the pieces, the launch cuts and the tree schedule) with the three kernels of
-// fg_ppc_stream.hip replaced by plain loops.  tests/test_ppc_cpu.py builds it with g++ (once more with -fsanitize=address,undefined)
-// and compares its output bit for bit with the Python restatement.
+// ppc_stream_driver.cpp -- the posterior predictive check stream on the host: fg_ppc_stream_plan.h and fg_chain_pool.h (the statistics,
+// update, merge and finish functions the device code runs, the pieces, the launch cuts and the tree schedule) with the two kernels of
+// fg_ppc_stream.hip and k_chain_pool replaced by plain loops.  tests/test_ppc_cpu.py builds it with g++ (once more with
+// -fsanitize=address,undefined) and compares its output bit for bit with the Python restatement.
 //
 //   ppc_stream_driver N_TOTAL N_ROWS C SPEC TABLE C1,C2,... [MAX_GRID_X MAX_GRID_Y]
 //
@@ -35,8 +35,8 @@ int main(int argc, char **argv) {
     if (argc < 7) { std::fprintf(stderr, "usage: ppc_stream_driver N_TOTAL N_ROWS C SPEC TABLE C1,C2,... [MAX_GRID_X MAX_GRID_Y]\n"); return 1; }
     const int n_total = std::atoi(argv[1]), n_rows = std::atoi(argv[2]);
     const long long C = std::atoll(argv[3]);
-    const long long gx = argc > 7 ? std::atoll(argv[7]) : FG_PPC_MAX_GRID_X;
-    const long long gy = argc > 8 ? std::atoll(argv[8]) : FG_PPC_MAX_GRID_Y;
+    const long long gx = argc > 7 ? std::atoll(argv[7]) : FG_POOL_MAX_GRID_X;
+    const long long gy = argc > 8 ? std::atoll(argv[8]) : FG_POOL_MAX_GRID_Y;
     std::ifstream spec(argv[4]);
     std::vector<int32_t> lists[4];                                                  // vtypes, offsets, members, masks
     std::vector<double> observed;
@@ -75,17 +75,17 @@ int main(int argc, char **argv) {
         if (end == std::string::npos) end = chunks.size();
         const int n_c = std::atoi(chunks.substr(at, end - at).c_str());
         at = end + 1;
-        rc = fg_ppc_take(P, n_c, &err);
+        rc = P.draws.take(n_c, "fg_ppc_stream_update", &err);
         if (rc) return fail(rc, err);
         for (int t0 = 0; t0 < n_c; t0 += P.scratch_draws) {                         // fg_ppc_stream_update
             const int n_piece = std::min(P.scratch_draws, n_c - t0);
             const uint64_t *cells = x.data() + (size_t)(done + t0) * (size_t)n_rows * (size_t)C;
-            for (const FgPpcLaunch &L : P.launches)                                 // k_ppc_stream_stats
-                for (const FgPpcSlice &S : fg_ppc_pair_slices(P, n_piece)) {
+            for (const FgPoolLaunch &L : P.launches)                               // k_ppc_stream_stats
+                for (const FgPoolSlice &S : fg_ppc_pair_slices(P, n_piece)) {
                     ++stat_launches;
                     for (long long y = 0; y < S.nk; ++y)
                         for (long long j = 0; j < L.cols; ++j) {
-                            const long long c = L.c0 + j, p = S.k0 + y, t = p / P.n_checks;
+                            const long long c = L.col0 + j, p = S.k0 + y, t = p / P.n_checks;
                             const int q = (int)(p - t * P.n_checks);
                             const int o0 = P.offsets[q], K = P.offsets[q + 1] - o0, mask = P.mask[q];
                             const int32_t *members = P.members.data() + o0;
@@ -97,12 +97,12 @@ int main(int argc, char **argv) {
                                 if ((mask >> st) & 1) { *out = T[st]; out += C; }
                         }
                 }
-            for (const FgPpcLaunch &L : P.launches)                                 // k_ppc_stream_update
-                for (const FgPpcSlice &S : P.slices) {
+            for (const FgPoolLaunch &L : P.launches)                               // k_ppc_stream_update
+                for (const FgPoolSlice &S : P.slices) {
                     ++update_launches;
                     for (long long y = 0; y < S.nk; ++y)
                         for (long long j = 0; j < L.cols; ++j) {
-                            const long long k = S.k0 + y, col = k * C + L.c0 + j;
+                            const long long k = S.k0 + y, col = k * C + L.col0 + j;
                             FgPpcState s;
                             fg_ppc_state_load(s, state.data() + col, stride);
                             for (int t = 0; t < n_piece; ++t) fg_ppc_update(s, scratch[(size_t)((long long)t * stride + col)], P.t_obs[(size_t)k]);
@@ -112,30 +112,9 @@ int main(int argc, char **argv) {
         }
         done += n_c;
     }
-    rc = fg_ppc_complete(P, "fg_ppc_stream_pooled", &err);
+    rc = P.draws.complete("fg_ppc_stream_pooled", &err);
     if (rc) return fail(rc, err);
-    // k_ppc_stream_pool, level by level
-    std::vector<FgPpcElem> cur, next;
-    for (size_t l = 0; l < P.levels.size(); ++l) {
-        const FgPpcLevel &L = P.levels[l];
-        next.assign((size_t)P.n_slots * (size_t)L.m_out, fg_ppc_empty());
-        for (const FgPpcSlice &S : P.slices)
-            for (long long k = S.k0; k < S.k0 + S.nk; ++k)
-                for (long long blk = 0; blk < L.m_out; ++blk) {
-                    FgPpcElem e[FG_PPC_POOL_THREADS];
-                    const long long i0 = blk * FG_PPC_POOL_THREADS;
-                    const int n = (int)std::min<long long>(FG_PPC_POOL_THREADS, L.m_in - i0);
-                    for (int i = 0; i < n; ++i) {
-                        if (l == 0) {
-                            FgPpcState s;
-                            fg_ppc_state_load(s, state.data() + k * C + i0 + i, stride);
-                            e[i] = fg_ppc_leaf(s);
-                        } else e[i] = cur[(size_t)k * (size_t)L.m_in + (size_t)(i0 + i)];
-                    }
-                    next[(size_t)k * (size_t)L.m_out + (size_t)blk] = fg_ppc_block_tree(e, n);
-                }
-        cur.swap(next);
-    }
+    const std::vector<FgPpcElem> cur = fg_pool_host<FgPpcPool>(P.levels, P.slices, state.data(), stride);     // k_chain_pool, level by level
     for (int k = 0; k < P.n_slots; ++k) std::printf("tobs %d %016llx\n", k, bits(P.t_obs[(size_t)k]));
     for (int k = 0; k < P.n_slots; ++k)
         for (int w = 0; w < FG_PPC_WORDS; ++w) {
@@ -146,8 +125,8 @@ int main(int argc, char **argv) {
     for (int k = 0; k < P.n_slots; ++k) {
         double w[FG_PPC_ELEM], mom[2];
         int64_t cnt[5];
-        fg_ppc_elem_store(cur[(size_t)k], w);
-        fg_ppc_finish(fg_ppc_elem_load(w), cnt, mom);
+        FgPpcPool::elem_store(cur[(size_t)k], w);
+        fg_ppc_finish(FgPpcPool::elem_load(w), cnt, mom);
         std::printf("pooled %d %lld %lld %lld %lld %lld %016llx %016llx\n", k, (long long)cnt[0], (long long)cnt[1], (long long)cnt[2], (long long)cnt[3], (long long)cnt[4],
                     bits(mom[0]), bits(mom[1]));
     }

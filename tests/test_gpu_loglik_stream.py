@@ -82,11 +82,20 @@ def test_pooled_words_do_not_depend_on_the_chunking_and_match_the_restatement(en
     restatement: counters exact; n_fin, mean, ssd bit-equal (no transcendental; -ffp-contract=off), so mean_ll and p_waic are exact;
     figures in the same class (NaN / +-inf / finite); lppd and elpd_loo within (N + 8) 2^-52 absolute, is_ess and max_weight within
     the same bound relative (ocml's exp against glibc's, each within an ulp or two, in a sum of N positive terms)."""
-    eng = engines.get(C)
+    _check_tables(engines.get(C), C, n, _tables(n, C))
+
+
+def test_a_tree_of_three_levels(engines):
+    """C = 65 537 chains: 65 537 -> 257 -> 2 -> 1, the last block of every level partial.  One statement with a -inf cell, one draw;
+    held to what the test above holds every table to."""
+    _check_tables(engines.get(65537), 65537, 1, [(("neg_inf",), L.table(["neg_inf"], 1, 65537, seed=3))])
+
+
+def _check_tables(eng, C, n, tables):
     N = n * C
     bound = (N + 8) * EPS
     worst = dict(lppd=0.0, elpd_loo=0.0, is_ess=0.0, max_weight=0.0)
-    for kinds, x in _tables(n, C):
+    for kinds, x in tables:
         ptr = eng.upload(x)
         try:
             runs = [_feed(eng, ptr, x.shape, ch) for ch in _chunkings(n)]

@@ -88,11 +88,20 @@ def _chunkings(n):
 def test_counters_and_moments_do_not_depend_on_the_chunking_and_equal_the_restatement(engines, C, n):
     """One chunk against (1, 7, rest) (n = 2: (1, 1)), device against device: pooled counters, mean and ssd, and chains(slot), bit-equal.
     Against the restatement everything is exact: T_obs, the counters pooled and per chain, the mean and ssd bits."""
-    eng = engines.get(C)
+    _check_configs(engines.get(C), C, n, _configs(C))
+
+
+def test_a_tree_of_three_levels(engines):
+    """C = 65 537 chains: 65 537 -> 257 -> 2 -> 1, the last block of every level partial.  One check of one N(0, 1) member, its mean,
+    one draw; held to what the test above holds every configuration to."""
+    _check_configs(engines.get(65537), 65537, 1, [("one member", [([0], 1 << R.MEAN, [0.25])])])
+
+
+def _check_configs(eng, C, n, configs):
     x, vtypes = R.table(KINDS, n, C, seed=C)
     ptr = eng.upload(x)
     try:
-        for label, checks in _configs(C):
+        for label, checks in configs:
             runs = [_feed(eng, ptr, x.shape, vtypes, checks, ch) for ch in _chunkings(n)]
             got = runs[0]
             for other in runs[1:]:

@@ -122,6 +122,14 @@ def test_launch_cuts_and_slices_change_nothing(driver, tmp_path):
     assert base == (1, 2, 1) and cut == (math.ceil(3 * 600 / 256), 2, 2)
 
 
+def test_a_tree_of_three_levels(driver, tmp_path):
+    """C = 65 537 chains: 65 537 -> 257 -> 2 -> 1, the last block of every level partial.  One statement, one draw, the default grid;
+    the -inf cell's counter crosses the three levels with the finite words."""
+    shape = check_driver(driver, tmp_path, L.table(["neg_inf"], 1, 65537, seed=3), "C 65537")
+    print("launches, levels, slices:", shape)
+    assert shape == (1, 3, 1)
+
+
 def test_driver_under_address_and_ub_sanitizers(driver_san, tmp_path):
     for C in (1, 3, 65):
         check_driver(driver_san, tmp_path, L.table(["normal", "far", "both_inf"], 23, C, seed=C), f"sanitizers C {C}")

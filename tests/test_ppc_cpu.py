@@ -169,6 +169,15 @@ def test_launch_cuts_and_slices_change_nothing(driver, tmp_path):
     assert cut == (3, 2, 9, 3 * (pairs(1) + pairs(7) + 2 * pairs(16)), 3 * 9 * 4)
 
 
+def test_a_tree_of_three_levels(driver, tmp_path):
+    """C = 65 537 chains: 65 537 -> 257 -> 2 -> 1, the last block of every level partial.  One check of one N(0, 1) member, its mean,
+    one draw, the default grid."""
+    x, vtypes = R.table(["normal"], 1, 65537, seed=3)
+    shape, want = check_driver(driver, tmp_path, x, vtypes, [([0], 1 << R.MEAN, [0.25])], "C 65537")
+    print("launches, levels, slices, statistics launches, update launches:", shape, "counts", want["counts"])
+    assert shape == (1, 3, 1, 1, 1) and sum(want["counts"][0][:4]) == 65537 and want["counts"][0][4] == 65537
+
+
 def test_driver_under_address_and_ub_sanitizers(driver_san, tmp_path):
     for C, K in ((1, 1), (3, 3), (65, 8)):
         kinds, checks, labels = R.standard_checks(K, seed=C)
