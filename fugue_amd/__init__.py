@@ -8,9 +8,9 @@
 from .model import (Bernoulli, Beta, Binomial, Categorical, Cauchy, ChiSquared, DiscreteUniform, Exponential, FugueError, Gamma,  # noqa: F401
                     InverseGamma, Laplace, LogNormal, Model, Normal, Poisson, Program, StudentT, Uniform, Weibull, addr, factor, guard,
                     observe, plate, pure, sample, sequence_vec, traverse_vec, zip_models)
-from .inference import (ChainBatch, ChainSummary, HMCConfig, PriorPredictive, ResamplingMethod, SMCConfig, SMCResult, SiteProposal,  # noqa: F401
-                        adaptive_mcmc_chain, adaptive_mcmc_chain_summary, adaptive_mcmc_chain_with_overrides, adaptive_smc, hmc_chain,
-                        hmc_chain_summary, prior_predictive)
+from .inference import (ChainBatch, ChainSummary, HMCConfig, PopulationSummary, PriorPredictive, ResamplingMethod, SMCConfig, SMCResult,  # noqa: F401
+                        SiteProposal, WeightedTables, adaptive_mcmc_chain, adaptive_mcmc_chain_summary, adaptive_mcmc_chain_with_overrides,
+                        adaptive_smc, adaptive_smc_summary, hmc_chain, hmc_chain_summary, population_summary, prior_predictive)
 from .diagnostics import (ParameterSummary, StreamMoments, classic_r_hat_f64, effective_sample_size, effective_sample_size_multichain,  # noqa: F401
                           geweke_diagnostic, r_hat_f64, summarize_f64_parameter)
 from .comparison import PointwiseComparison, compare_models, model_comparison  # noqa: F401

@@ -215,6 +215,7 @@ void fg_internal_hmc_set_cfg(fg_engine *e, const fg_hmc_config *cfg);
 int fg_internal_hmc_step(fg_engine *e, int n_transitions, double *d_draws, double *d_pos_all, double *d_info);
 int fg_internal_mh_alloc(fg_engine *e);
 int fg_internal_mh_set_overrides(fg_engine *e, const fg_site_proposal *overrides);
+int fg_internal_smc_weights(fg_engine *e, const double **d_w);   // fg_smc.hip, for fg_wpop.hip: FG_E_STATE without a population
 }
 
 // fg_mh_interp.hip: multi-wave single-site MH for interpreter programs (FG_E_UNSUPPORTED: not applicable)

@@ -1731,6 +1731,12 @@ int fg_smc_get_weights(fg_engine *e, double *h_log_w, double *h_w) {
     HIPCHK(hipStreamSynchronize(e->stream));
     return FG_OK;
 }
+int fg_internal_smc_weights(fg_engine *e, const double **d_w) {         // fg_wpop.hip: the population's normalised weights where they lie
+    SmcWs W;
+    if (int rc = smc_pop(e, W, true)) return rc;
+    *d_w = W.d_w;
+    return FG_OK;
+}
 int fg_smc_set_log_weights(fg_engine *e, const double *h_log_w) {       // a caller's own reweighting step; follow with fg_smc_normalize
     NEED_ENGINE(e);
     if (!h_log_w) return FG_E_BAD_ARG;

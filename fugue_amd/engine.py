@@ -100,6 +100,7 @@ ABI_SYMBOLS = [
     "fg_loglik_stream_new", "fg_loglik_stream_update", "fg_loglik_stream_count", "fg_loglik_stream_pooled", "fg_loglik_stream_result", "fg_loglik_stream_free",
     "fg_ppc_stream_new", "fg_ppc_stream_update", "fg_ppc_stream_count", "fg_ppc_stream_n_slots", "fg_ppc_stream_observed", "fg_ppc_stream_pooled",
     "fg_ppc_stream_chains", "fg_ppc_stream_free", "fg_program_observe_value",
+    "fg_wpop_new", "fg_wpop_units", "fg_wpop_moments", "fg_wpop_quantiles", "fg_wpop_counts", "fg_wpop_free",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -282,6 +283,14 @@ def lib():
     L.fg_ppc_stream_free.restype = None
     L.fg_ppc_stream_free.argtypes = [vp]
     L.fg_program_observe_value.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
+    u64p = C.POINTER(C.c_uint64)
+    L.fg_wpop_new.argtypes = [vp, C.c_int64, vp, C.POINTER(vp)]
+    L.fg_wpop_units.argtypes = [vp, u64p, u64p, u64p]
+    L.fg_wpop_moments.argtypes = [vp, vp, C.c_int, dp]
+    L.fg_wpop_quantiles.argtypes = [vp, vp, C.c_int, dp, C.c_int, C.c_int, C.c_int64, dp, ip]
+    L.fg_wpop_counts.argtypes = [vp, vp, C.c_int, ip, i64p, ip, u64p, u64p, u64p, i64p, i64p]
+    L.fg_wpop_free.restype = None
+    L.fg_wpop_free.argtypes = [vp]
     L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
@@ -906,6 +915,12 @@ class Engine:
         statistics, observed values) per check -- statistics as indices or names of PPC_STATS, observed aligned with the members."""
         return PpcStream(self, n_total, vtypes, checks)
 
+    def wpop(self, n: Optional[int] = None, d_w: Optional[int] = None) -> "WeightedPopulation":
+        """A `fg_wpop`: weighted moments, exact weighted quantiles and exact weighted frequency tables of rows that stay on the
+        device.  Without arguments the population is the engine's own (after `smc_run` / `smc_prior_particles`; EngineError
+        FG_E_STATE without one); `d_w` is a device buffer of `n` normalised weights of the caller's."""
+        return WeightedPopulation(self, n, d_w)
+
     def cells_f64(self, d_cells: int, n: int, n_rec: int, rows: Sequence[int], vtypes: Sequence[int], out: Optional[int] = None) -> int:
         """`fg_diag_cells_f64`: rows `rows` of the device cells [n][n_rec][C] as doubles [n][len(rows)][C] in the device buffer `out`
         (allocated here when None: the caller frees it), asynchronously: an f64 row is copied, a u64 row converted as unsigned
@@ -1271,6 +1286,95 @@ class PpcStream(_Stream):
         counts = np.zeros((5, self.engine.C), dtype=np.int64)
         _check(lib().fg_ppc_stream_chains(self._handle(), int(slot), counts.ctypes.data_as(C.POINTER(C.c_int64))))
         return {name: counts[i].copy() for i, name in enumerate(PPC_COUNTS)}
+
+    free = _Stream.close
+
+
+WPOP_MOMENTS = ("W", "mean", "var", "std", "mcse", "n_used")      # FG_WPOP_MOMENTS words per row
+
+
+class WeightedPopulation(_Stream):
+    """`fg_wpop` (fg_wpop.hip): the summary of a weighted population that stays on the device -- what the reference does on the host
+    with ABCSMCResult::weighted_mean (abc.rs:476) and the doc example's walk over the particles (smc.rs:445-453).  Rows are device
+    buffers [d][n] of doubles (cells [n_rows][n] for `counts`), element i of a row belonging to particle i.  The handle keeps a copy
+    of the weights as they were when it was made, and their units q_i = rint(w_i 2^52): quantiles and tables are exact sums of units,
+    moments use the doubles over a fixed tree on the particle index.  Close it before its engine."""
+
+    _free = "fg_wpop_free"
+
+    def __init__(self, engine: "Engine", n: Optional[int] = None, d_w: Optional[int] = None):
+        if n is None:
+            n = engine.C
+        self._integers(n=n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        self.engine, self.n = engine, int(n)
+        self.h = None
+        out = C.c_void_p()
+        _check(lib().fg_wpop_new(engine.h, self.n, d_w, C.byref(out)))
+        self.h = out.value
+
+    def units(self) -> dict:
+        """T (the units of the population), n_bad (weights that are NaN, negative, infinite or above 1), n_zero (good weights of zero units)."""
+        T, bad, zero = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().fg_wpop_units(self._handle(), C.byref(T), C.byref(bad), C.byref(zero)))
+        return dict(T=T.value, n_bad=bad.value, n_zero=zero.value)
+
+    def moments(self, d_x: int, d: int) -> dict:
+        """W, mean, var, std, mcse, n_used of every row, each float64 [d] (n_used int64)."""
+        self._integers(d=d)
+        if not 1 <= d <= 65535:
+            raise ValueError("d must lie in [1, 65535]")
+        out = np.zeros((int(d), len(WPOP_MOMENTS)))
+        _check(lib().fg_wpop_moments(self._handle(), d_x, int(d), _dp(out)))
+        res = {name: out[:, j].copy() for j, name in enumerate(WPOP_MOMENTS)}
+        res["n_used"] = res["n_used"].astype(np.int64)
+        return res
+
+    def quantiles(self, d_x: int, d: int, probs=(0.025, 0.25, 0.5, 0.75, 0.975), digit_bits: int = 12, capacity: int = 65536):
+        """(values [d][len(probs)], passes [d][len(probs)]): the inverse weighted CDF at every probability, and the passes over its
+        row each one took."""
+        self._integers(d=d, digit_bits=digit_bits, capacity=capacity)
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        if not 1 <= d <= 65535:
+            raise ValueError("d must lie in [1, 65535]")
+        if not 1 <= pr.size <= 8:
+            raise ValueError("between 1 and 8 probabilities")
+        if not np.all((pr >= 0.0) & (pr <= 1.0)):
+            raise ValueError("probabilities must lie in [0, 1]")
+        if not 1 <= digit_bits <= 12:
+            raise ValueError("digit_bits must lie in [1, 12]")
+        if capacity < 0:
+            raise ValueError("capacity must not be negative")
+        out = np.zeros((int(d), pr.size))
+        passes = np.zeros((int(d), pr.size), dtype=np.int32)
+        _check(lib().fg_wpop_quantiles(self._handle(), d_x, int(d), _dp(pr), pr.size, int(digit_bits), int(capacity), _dp(out),
+                                       passes.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, passes
+
+    def counts(self, d_cells: int, vtypes: Sequence[int], lo: Sequence[int], bins: Sequence[int]) -> dict:
+        """Weighted frequency tables of integer rows d_cells [len(vtypes)][n].  units: a list of uint64 arrays [bins[k]]; below /
+        above: uint64 [n_rows]; min / max: lists of Python ints over the cells of non-zero units (None when T == 0; a u64 row's are
+        unsigned); T: the units of the population, so units / T are the probabilities."""
+        vt, lo, bins = [int(v) for v in vtypes], [int(v) for v in lo], [int(b) for b in bins]
+        nr = len(vt)
+        if not (nr == len(lo) == len(bins)):
+            raise ValueError("vtypes, lo and bins must have one entry per row")
+        if not 1 <= nr <= 65535:
+            raise ValueError("between 1 and 65535 rows")
+        if any(not -2 ** 63 <= v < 2 ** 63 for v in lo):
+            raise ValueError("lo must fit 64 signed bits")
+        flat = np.zeros(max(1, sum(b for b in bins if b > 0)), dtype=np.uint64)
+        below, above = np.zeros(nr, dtype=np.uint64), np.zeros(nr, dtype=np.uint64)
+        mn, mx = np.zeros(nr, dtype=np.int64), np.zeros(nr, dtype=np.int64)
+        u64p, i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
+        i32 = lambda v: (C.c_int32 * nr)(*v)
+        _check(lib().fg_wpop_counts(self._handle(), d_cells, nr, i32(vt), (C.c_int64 * nr)(*lo), i32(bins), flat.ctypes.data_as(u64p), below.ctypes.data_as(u64p),
+                                    above.ctypes.data_as(u64p), mn.ctypes.data_as(i64p), mx.ctypes.data_as(i64p)))
+        at = np.concatenate([[0], np.cumsum(bins)])
+        T = self.units()["T"]
+        ints = lambda a: [None if T == 0 else (int(v) & (2 ** 64 - 1) if vt[k] == M.U64 else int(v)) for k, v in enumerate(a)]
+        return dict(units=[flat[at[k]:at[k + 1]].copy() for k in range(nr)], below=below, above=above, min=ints(mn), max=ints(mx), T=T)
 
     free = _Stream.close
 

@@ -144,6 +144,17 @@ class SMCResult:
             raise M.FugueError(f"result not found: {name}", M.ErrorCode.TraceAddressNotFound)
         return self.results[self.result_names.index(name)]
 
+    def weighted_mean(self, address: str) -> Optional[float]:
+        """ABCSMCResult::weighted_mean's rule (abc.rs:476-489) for an SMC population: sum w x / sum w in particle order, None for an
+        address that is no f64 site or a population without weight."""
+        if address not in self.sites or self.vtypes[self.sites.index(address)] != M.F64:
+            return None
+        num = den = 0.0
+        for v, w in zip(self.get_f64(address).tolist(), self.weights.tolist()):
+            num += w * v
+            den += w
+        return num / den if den > 0.0 else None
+
 
 def _compile(model_fn) -> E.CompiledProgram:
     return model_fn if isinstance(model_fn, E.CompiledProgram) else E.compile_model(model_fn)
@@ -720,6 +731,142 @@ def adaptive_smc(seed: int, num_particles: int, model_fn, config: Optional[SMCCo
             setattr(out, k, v)
     eng.close()
     return out
+
+
+@dataclass
+class WeightedTables:
+    """Exact weighted frequency tables of the discrete sites of a population (`Engine.wpop(...).counts`): units[k][j] are the units
+    (rint(w 2^52) each) of the particles whose site k equals lo[k] + j; `below` / `above` the units outside the bins; min / max over
+    the particles of non-zero units (None without one)."""
+    names: List[str]
+    vtypes: List[int]
+    lo: List[int]
+    bins: List[int]
+    units: List[np.ndarray]
+    below: np.ndarray
+    above: np.ndarray
+    min: List[Optional[int]]
+    max: List[Optional[int]]
+    T: int
+
+    def probs(self) -> List[np.ndarray]:
+        return [u.astype(np.float64) / float(self.T) if self.T else np.full(u.shape, np.nan) for u in self.units]
+
+
+@dataclass
+class PopulationSummary:
+    """`adaptive_smc_summary`: the final population of `adaptive_smc` summarised where it lies.  One row per name: the f64 sites,
+    then (results=True) the model's return values, then (predictive=) the replicates of the selected f64 observe sites.  `quantiles`
+    [rows][len(probs)] are inverse weighted CDFs on the units of the weights -- exact, and NOT summarize_f64_parameter's
+    sorted[round((len - 1) p)]; mean / std / mcse use the weights as doubles (mcse = sqrt(sum w^2 (x - mean)^2) / sum w)."""
+    names: List[str]
+    n_particles: int
+    probs: np.ndarray
+    mean: np.ndarray
+    std: np.ndarray
+    mcse: np.ndarray
+    quantiles: np.ndarray
+    n_used: np.ndarray                 # particles behind the moments of a row: a good weight above zero and a finite value
+    log_evidence: float
+    betas: np.ndarray
+    ess: float                         # effective_sample_size of the final weights (smc.rs:230-233)
+    T: int                             # the units of the population (2^52 up to rounding)
+    n_zero: int                        # particles whose weight rounds to zero units: no part in quantiles and tables
+    sites: List[str] = field(default_factory=list)
+    result_names: List[str] = field(default_factory=list)
+    predictive_names: List[str] = field(default_factory=list)
+    tables: Optional[WeightedTables] = None
+    passes: Optional[np.ndarray] = None   # [rows][len(probs)]: the passes over its row each quantile took
+
+    def row(self, name: str) -> int:
+        if name not in self.names:
+            raise M.FugueError(f"address not found: {name}", M.ErrorCode.TraceAddressNotFound)
+        return self.names.index(name)
+
+
+def _empty_population_summary(names, probs, sites, result_names, predictive_names) -> PopulationSummary:
+    z = np.zeros(len(names))
+    return PopulationSummary(list(names), 0, probs, z + np.nan, z + np.nan, z + np.nan, np.full((len(names), probs.size), np.nan), np.zeros(len(names), dtype=np.int64),
+                             0.0, np.zeros(0), 0.0, 0, 0, list(sites), list(result_names), list(predictive_names))
+
+
+def population_summary(eng, log_evidence: float = 0.0, betas=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975), results: bool = False, predictive=False,
+                       discrete: bool = False, digit_bits: int = 12, capacity: int = 65536, seed_iter: int = 0) -> PopulationSummary:
+    """The summary of the particle population an engine holds (after `smc_run(download=False)` or the standalone SMC calls), on the
+    device: nothing of size N comes to the host, and neither the engine's values nor its weights change.  See `adaptive_smc_summary`."""
+    cp, N = eng.cp, eng.C
+    who = "adaptive_smc_summary"
+    pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    _want_results(cp, results, who=who)
+    psel = _summary_predictive(cp, predictive, who)
+    sites = [cp.site_names[j] for j in cp.f64_sites]
+    rnames = list(cp.result_names) if results else []
+    pnames = [cp.observe_names[k] for k in psel] if psel is not None else []
+    names = sites + rnames + pnames
+    disc = [j for j in range(cp.S) if cp.site_vtypes[j] != M.F64] if discrete else []
+    if not names and not disc:
+        raise ValueError(f"{who}: nothing to summarise: the model has no f64 site, and neither results, predictive nor discrete adds a row")
+    values = E.lib().fg_engine_values_device(eng.h)
+    wp, buffers = None, []
+    try:
+        wp = eng.wpop()
+        u = wp.units()
+        if u["n_bad"] > 0:
+            raise ValueError(f"{who}: {u['n_bad']} of {N} weights are NaN, negative, infinite or above 1: the population is not normalised")
+        out = PopulationSummary(names, N, pr, np.zeros(0), np.zeros(0), np.zeros(0), np.zeros((0, pr.size)), np.zeros(0, dtype=np.int64), float(log_evidence),
+                                np.zeros(0) if betas is None else np.asarray(betas, dtype=np.float64), eng.smc_ess(), u["T"], u["n_zero"], sites, rnames, pnames)
+        if names:
+            D = len(names)
+            x = eng.device_alloc(D * N * 8)
+            buffers.append(x)
+            if sites:
+                eng.cells_f64(values, 1, cp.S, cp.f64_sites, [M.F64] * len(sites), out=x)
+            if rnames:
+                eng.result_eval(None, 1, out=x + len(sites) * N * 8)
+            if pnames:
+                eng.predict_eval(None, 1, iter0=seed_iter, sel=psel, out=x + (len(sites) + len(rnames)) * N * 8, loglik=False)
+            m = wp.moments(x, D)
+            out.mean, out.std, out.mcse, out.n_used = m["mean"], m["std"], m["mcse"], m["n_used"]
+            out.quantiles, out.passes = wp.quantiles(x, D, pr, digit_bits, capacity)
+        if disc:
+            cells = eng.cells_f64(values, 1, cp.S, disc, [M.F64] * len(disc))      # the F64 tag copies a cell's bits: a gather of the rows
+            buffers.append(cells)
+            vt = [cp.site_vtypes[j] for j in disc]
+            lb = [_default_bins(cp, j) for j in disc]
+            t = wp.counts(cells, vt, [a for a, _ in lb], [b for _, b in lb])
+            out.tables = WeightedTables([cp.site_names[j] for j in disc], vt, [a for a, _ in lb], [b for _, b in lb], t["units"], t["below"], t["above"], t["min"], t["max"], t["T"])
+        return out
+    finally:
+        if wp is not None:
+            wp.close()
+        for b in buffers:
+            eng.device_free(b)
+
+
+def adaptive_smc_summary(seed: int, num_particles: int, model_fn, config: Optional[SMCConfig] = None, device: int = 0,
+                         probs=(0.025, 0.25, 0.5, 0.75, 0.975), results: bool = False, predictive=False, discrete: bool = False) -> PopulationSummary:
+    """`adaptive_smc` without the download: the same run (`smc_run(download=False)` leaves particles and weights in HBM), then the
+    weighted summary of the final population on the device (`Engine.wpop`): per f64 site the weighted mean, std, Monte Carlo error
+    and exact weighted quantiles at `probs`; `results=True` adds the rows of the model's return value at the final particles,
+    `predictive=True | [addresses]` one replicate of the selected f64 observe sites per particle (stream (seed, particle, 0, 9), as
+    `adaptive_smc` draws them), `discrete=True` the exact weighted frequency tables of the discrete sites (`PopulationSummary.tables`,
+    bins as `adaptive_mcmc_chain_summary` chooses them).  A population whose weights are not all in [0, 1] raises ValueError.
+    `num_particles == 0` returns an empty summary with log_evidence 0.0 (smc.rs:462-467)."""
+    cp = _compile(model_fn)
+    cfg = config or SMCConfig()
+    if num_particles == 0:
+        _want_results(cp, results, who="adaptive_smc_summary")
+        psel = _summary_predictive(cp, predictive, "adaptive_smc_summary")
+        sites = [cp.site_names[j] for j in cp.f64_sites]
+        rnames = list(cp.result_names) if results else []
+        pnames = [cp.observe_names[k] for k in psel] if psel is not None else []
+        return _empty_population_summary(sites + rnames + pnames, np.ascontiguousarray(probs, dtype=np.float64).reshape(-1), sites, rnames, pnames)
+    eng = E.Engine(cp, num_particles, seed=seed, device=device)
+    try:
+        r = eng.smc_run(cfg.resampling_method, cfg.ess_threshold, cfg.rejuvenation_steps, download=False)
+        return population_summary(eng, r["log_evidence"], r["betas"], probs, results, predictive, discrete)
+    finally:
+        eng.close()
 
 
 @dataclass

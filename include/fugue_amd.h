@@ -721,6 +721,46 @@ int  fg_ppc_stream_pooled(fg_ppc_stream *s, int64_t *h_counts, double *h_moments
  * FG_E_BAD_ARG: a slot outside [0, n_slots). */
 int  fg_ppc_stream_chains(fg_ppc_stream *s, int slot, int64_t *h_counts);
 void fg_ppc_stream_free(fg_ppc_stream *s);
+/* ------------------------------------------------------------------ weighted populations on the device
+ * The reference summarises a weighted population on the host: ABCSMCResult::weighted_mean (abc.rs:476) and the doc example that walks
+ * the particles by hand (smc.rs:445-453).  fg_wpop does it where the population lies: rows d_x [d][N] of doubles (element i of a row
+ * belongs to particle i) and normalised weights w [N], both in device memory.
+ *   Units: q_i = (uint64) rint(w_i 2^52), half to even, for 0 <= w_i <= 1; any other weight (NaN, negative, infinite, above 1) is BAD,
+ *   has no units and is counted in n_bad; n_zero counts the good weights of zero units; T = sum q_i (FG_E_BAD_ARG at 2^53 and above:
+ *   such weights are not normalised).  Quantiles and tables are sums of units -- integers, whatever the order of the additions -- and a
+ *   particle of zero units takes no part in them.
+ *   Quantile of p: with t = min(T, max(1, ceil(p (double)T))), the smallest value v of the row with sum_{key(x_j) <= key(v)} q_j >= t,
+ *   keys ordered as fg_diag_qstream orders them (-0.0 below +0.0, a positive-sign NaN above +inf): an inverse weighted CDF, NOT the
+ *   sorted[round((len - 1) p)] of summarize_f64_parameter.  T == 0: NaN.  Found by radix select over digits of `digit_bits` bits,
+ *   collecting a bucket once it holds at most `capacity` elements.
+ *   Moments use the doubles w_i of the particles with a good weight above zero and a finite cell, merged over the fixed binary tree
+ *   on the particle index of the chain-pooled streams: W = sum w, mean, var = ssd / W, std, mcse = sqrt(sum w_i^2 (x_i - mean)^2) / W
+ *   and n_used, the number of such particles (as a double).  No such particle: W = 0, n_used = 0, the rest NaN.
+ *   Tables: bin j of an integer row holds the units of the cells equal to lo + j, `below` / `above` the units outside the bins, min /
+ *   max are taken over the cells of non-zero units (0 when T == 0).  Cells are read by their tag as fg_diag_cstream reads them.
+ * The handle copies the weights at fg_wpop_new and reads no engine state afterwards; it changes none.  One device, one rank. */
+#define FG_WPOP_MOMENTS 6
+typedef struct fg_wpop fg_wpop;
+/* abc.rs:476 / smc.rs:445-453: the weights d_w [n] in device memory (any n >= 1), or d_w == NULL for the engine's own population
+ * (FG_E_STATE without one; FG_E_BAD_ARG unless n is the engine's number of chains).  Free the handle before its engine. */
+int  fg_wpop_new(fg_engine *e, int64_t n, const double *d_w, fg_wpop **out);
+/* abc.rs:476 / smc.rs:445-453: T, n_bad, n_zero (any may be NULL) */
+int  fg_wpop_units(const fg_wpop *h, uint64_t *out_T, uint64_t *out_n_bad, uint64_t *out_n_zero);
+/* abc.rs:476 / smc.rs:445-453: h_out [d][FG_WPOP_MOMENTS] = W, mean, var, std, mcse, n_used of rows d_x [d][n].  FG_E_BAD_ARG: d
+ * outside [1, 65535]. */
+int  fg_wpop_moments(fg_wpop *h, const double *d_x, int d, double *h_out);
+/* abc.rs:476 / smc.rs:445-453: h_out [d][n_probs]; h_passes [d][n_probs] (or NULL) = the passes over its row each quantile took.
+ * FG_E_BAD_ARG: d outside [1, 65535], n_probs outside [1, 8], a probability outside [0, 1], digit_bits outside [1, 12],
+ * capacity < 0.  FG_E_STATE: a pass whose totals differ from what the previous pass left (never a quantile). */
+int  fg_wpop_quantiles(fg_wpop *h, const double *d_x, int d, const double *h_probs, int n_probs, int digit_bits,
+                       int64_t capacity, double *h_out, int32_t *h_passes);
+/* abc.rs:476 / smc.rs:445-453: integer rows d_cells [n_rows][n] with tags h_vtypes, lower bounds h_lo and bin counts h_bins [n_rows];
+ * h_units = the rows' bins back to back, h_below / h_above / h_min / h_max [n_rows].  FG_E_BAD_ARG: n_rows outside [1, 65535], a tag
+ * that is FG_F64 or unknown, bins outside [1, 4096], lo + bins overflowing the row's integer type.  FG_E_STATE: a row whose units do
+ * not add up to T. */
+int  fg_wpop_counts(fg_wpop *h, const void *d_cells, int n_rows, const int32_t *h_vtypes, const int64_t *h_lo,
+                    const int32_t *h_bins, uint64_t *h_units, uint64_t *h_below, uint64_t *h_above, int64_t *h_min, int64_t *h_max);
+void fg_wpop_free(fg_wpop *h);                                 /* abc.rs:476 / smc.rs:445-453 */
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

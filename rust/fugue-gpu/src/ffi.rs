@@ -11,6 +11,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_diag_cstream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_loglik_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_ppc_stream { _p: [u8; 0] }
+#[repr(C)] pub struct fg_wpop { _p: [u8; 0] }
 #[repr(C)] pub struct fg_abc { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
@@ -220,6 +221,15 @@ extern "C" {
     pub fn fg_ppc_stream_pooled(s: *mut fg_ppc_stream, h_counts: *mut i64, h_moments: *mut f64) -> c_int;
     pub fn fg_ppc_stream_chains(s: *mut fg_ppc_stream, slot: c_int, h_counts: *mut i64) -> c_int;
     pub fn fg_ppc_stream_free(s: *mut fg_ppc_stream);
+    // ---- weighted populations on the device (fg_wpop.hip): what abc.rs:476 / smc.rs:445-453 do on the host
+    pub fn fg_wpop_new(e: *mut fg_engine, n: i64, d_w: *const f64, out: *mut *mut fg_wpop) -> c_int;
+    pub fn fg_wpop_units(h: *const fg_wpop, out_t: *mut u64, out_n_bad: *mut u64, out_n_zero: *mut u64) -> c_int;
+    pub fn fg_wpop_moments(h: *mut fg_wpop, d_x: *const f64, d: c_int, h_out: *mut f64) -> c_int;
+    pub fn fg_wpop_quantiles(h: *mut fg_wpop, d_x: *const f64, d: c_int, h_probs: *const f64, n_probs: c_int, digit_bits: c_int, capacity: i64,
+                             h_out: *mut f64, h_passes: *mut i32) -> c_int;
+    pub fn fg_wpop_counts(h: *mut fg_wpop, d_cells: *const c_void, n_rows: c_int, h_vtypes: *const i32, h_lo: *const i64, h_bins: *const i32,
+                          h_units: *mut u64, h_below: *mut u64, h_above: *mut u64, h_min: *mut i64, h_max: *mut i64) -> c_int;
+    pub fn fg_wpop_free(h: *mut fg_wpop);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
