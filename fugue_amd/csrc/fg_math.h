@@ -515,14 +515,14 @@ FG_HD long long fg_smp_poisson(double lambda, FgStream &s) {
         double U = fg_u01_of(ra) - 0.5, V = 1.0 - fg_u01_of(rb);
         double us = 0.5 - fabs(U);
         double kf = floor((2.0 * a / us + b) * U + lambda + 0.43);
-        if (us >= 0.07 && V <= vr) return (long long)kf;
+        if (us >= 0.07 && V <= vr) return fg_f2i_sat(kf);
         if (kf < 0.0 || (us < 0.013 && V > us)) continue;
-        if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lambda + kf * loglam - fg_lgamma(kf + 1.0)) return (long long)kf;
+        if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lambda + kf * loglam - fg_lgamma(kf + 1.0)) return fg_f2i_sat(kf);
     }
-    return (long long)lambda;
+    return fg_f2i_sat(lambda);
 }
 FG_HD long long fg_smp_binomial(unsigned long long n, double p, FgStream &s) {
-    if (p <= 0.0 || n == 0) return 0;
+    if (p <= 0.0 || n == 0 || !fg_finite(p)) return 0;   // a non-finite p draws nothing, as Bernoulli
     if (p >= 1.0) return (long long)n;
     bool flip = p > 0.5; double q = flip ? 1.0 - p : p; double nd = (double)n;
     long long k;
@@ -536,16 +536,16 @@ FG_HD long long fg_smp_binomial(unsigned long long n, double p, FgStream &s) {
         double c = nd * q + 0.5, vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq;
         double m = floor((nd + 1.0) * q), lpq = log(q / (1.0 - q));
         double hm = fg_lgamma(m + 1.0) + fg_lgamma(nd - m + 1.0);
-        k = (long long)m;
+        k = fg_f2i_sat(m);
         for (int it = 0; it < 100000; it++) {
             unsigned long long ra, rb; fg_rng_block(s, ra, rb);
             double U = fg_u01_of(ra) - 0.5, V = 1.0 - fg_u01_of(rb);
             double us = 0.5 - fabs(U);
             double kf = floor((2.0 * a / us + b) * U + c);
             if (kf < 0.0 || kf > nd) continue;
-            if (us >= 0.07 && V <= vr) { k = (long long)kf; break; }
+            if (us >= 0.07 && V <= vr) { k = fg_f2i_sat(kf); break; }
             double lv = log(V * alpha / (a / (us * us) + b));
-            if (lv <= hm - fg_lgamma(kf + 1.0) - fg_lgamma(nd - kf + 1.0) + (kf - m) * lpq) { k = (long long)kf; break; }
+            if (lv <= hm - fg_lgamma(kf + 1.0) - fg_lgamma(nd - kf + 1.0) + (kf - m) * lpq) { k = fg_f2i_sat(kf); break; }
         }
     }
     return flip ? (long long)n - k : k;

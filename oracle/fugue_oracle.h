@@ -89,6 +89,12 @@ double orc_stream_gaussian_z(orc_stream *s);
 /* sample one value from a distribution (prior init / prior-resample) */
 orc_cell orc_sample_dist(int dist, const double *params, int nparams,
                          orc_stream *s);
+/* n draws of one distribution, draw i from the fresh stream (seed, chain0 + i,
+ * iter, purpose): cells [n]; blocks [n] = Philox blocks consumed (may be NULL) */
+void orc_sample_dist_many(int dist, const double *params, int nparams,
+                          uint64_t seed, uint32_t chain0, uint32_t iter,
+                          uint32_t purpose, int64_t n, orc_cell *cells,
+                          int32_t *blocks);
 
 /* ---- model building ---- */
 orc_model *orc_model_new(void);

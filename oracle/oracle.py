@@ -107,6 +107,7 @@ def lib():
     L.orc_philox4x32_10.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.orc_sample_dist.restype = C.c_int64      # orc_cell returned as raw 8 bytes (INTEGER class)
     L.orc_sample_dist.argtypes = [C.c_int, dp, C.c_int, C.POINTER(Stream)]
+    L.orc_sample_dist_many.argtypes = [C.c_int, dp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int64, vp, vp]
     L.orc_model_new.restype = vp
     L.orc_model_free.argtypes = [vp]
     L.orc_model_add_data.argtypes = [vp, dp, C.c_int]
@@ -221,6 +222,16 @@ def sample_dist(dist: str, params, s: Stream):
     if dist in INT_DISTS:
         return int(raw)
     return float(np.array([raw], dtype=np.int64).view(np.float64)[0])
+
+
+def sample_dist_many(dist: str, params, seed: int, n: int, chain0: int = 0, it: int = 0, purpose: int = 1):
+    """n draws, draw i from the fresh stream (seed, chain0 + i, it, purpose) -> (int64 or float64 [n], Philox blocks consumed [n])."""
+    p = _d(list(params) if len(params) else [0.0])
+    cells = np.zeros(max(1, n), dtype=np.int64)
+    blocks = np.zeros(max(1, n), dtype=np.int32)
+    lib().orc_sample_dist_many(DISTS.index(dist), _dp(p), len(params), seed, chain0, it, purpose, n, cells.ctypes.data, blocks.ctypes.data)
+    cells, blocks = cells[:n], blocks[:n]
+    return (cells if dist in INT_DISTS else cells.view(np.float64)), blocks
 
 
 # ------------------------------------------------------------------ model

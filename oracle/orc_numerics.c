@@ -298,15 +298,15 @@ static int64_t smp_poisson(double lambda, orc_stream *s) {
         double U = u01_of(ra) - 0.5, V = 1.0 - u01_of(rb);
         double us = 0.5 - fabs(U);
         double kf = floor((2.0 * a / us + b) * U + lambda + 0.43);
-        if (us >= 0.07 && V <= vr) return (int64_t)kf;
+        if (us >= 0.07 && V <= vr) return f2i_sat(kf);
         if (kf < 0.0 || (us < 0.013 && V > us)) continue;
         if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -lambda + kf * loglam - lgam(kf + 1.0))
-            return (int64_t)kf;
+            return f2i_sat(kf);
     }
-    return (int64_t)lambda;
+    return f2i_sat(lambda);
 }
 static int64_t smp_binomial(uint64_t n, double p, orc_stream *s) {
-    if (p <= 0.0 || n == 0) return 0;
+    if (p <= 0.0 || n == 0 || !isfinite(p)) return 0;   /* a non-finite p draws nothing, as Bernoulli */
     if (p >= 1.0) return (int64_t)n;
     int flip = p > 0.5; double q = flip ? 1.0 - p : p; double nd = (double)n;
     int64_t k;
@@ -320,16 +320,16 @@ static int64_t smp_binomial(uint64_t n, double p, orc_stream *s) {
         double c = nd * q + 0.5, vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq;
         double m = floor((nd + 1.0) * q), lpq = log(q / (1.0 - q));
         double hm = lgam(m + 1.0) + lgam(nd - m + 1.0);
-        k = (int64_t)m;
+        k = f2i_sat(m);
         for (int it = 0; it < 100000; it++) {
             uint64_t ra, rb; orc_stream_block(s, &ra, &rb);
             double U = u01_of(ra) - 0.5, V = 1.0 - u01_of(rb);
             double us = 0.5 - fabs(U);
             double kf = floor((2.0 * a / us + b) * U + c);
             if (kf < 0.0 || kf > nd) continue;
-            if (us >= 0.07 && V <= vr) { k = (int64_t)kf; break; }
+            if (us >= 0.07 && V <= vr) { k = f2i_sat(kf); break; }
             double lv = log(V * alpha / (a / (us * us) + b));
-            if (lv <= hm - lgam(kf + 1.0) - lgam(nd - kf + 1.0) + (kf - m) * lpq) { k = (int64_t)kf; break; }
+            if (lv <= hm - lgam(kf + 1.0) - lgam(nd - kf + 1.0) + (kf - m) * lpq) { k = f2i_sat(kf); break; }
         }
     }
     return flip ? (int64_t)n - k : k;
@@ -392,4 +392,12 @@ orc_cell orc_sample_dist(int dist, const double *p, int np, orc_stream *s) {
     default: r.f = NAN;
     }
     return r;
+}
+void orc_sample_dist_many(int dist, const double *p, int np, uint64_t seed, uint32_t chain0, uint32_t iter,
+                          uint32_t purpose, int64_t n, orc_cell *cells, int32_t *blocks) {
+    for (int64_t i = 0; i < n; i++) {
+        orc_stream s; orc_stream_init(&s, seed, chain0 + (uint32_t)i, iter, purpose);
+        cells[i] = orc_sample_dist(dist, p, np, &s);
+        if (blocks) blocks[i] = (int32_t)s.c1;
+    }
 }
