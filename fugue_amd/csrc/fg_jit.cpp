@@ -43,6 +43,12 @@ std::string lit(double v) {                      // a double literal with exactl
     std::snprintf(b, sizeof b, "fg_as_double((long long)0x%016llxULL)", (unsigned long long)bits);
     return b;
 }
+// the same inside the initialiser of a __device__ table, which has to be a constant expression (fg_as_double is a call: "dynamic
+// initialization is not supported").  The non-finite entry a table can hold is ln 0 = -inf, of a Categorical's zero probability.
+std::string lit_static(double v) {
+    if (std::isfinite(v)) return lit(v);
+    return std::isnan(v) ? "(__builtin_nan(\"\"))" : (v < 0.0 ? "(-__builtin_huge_val())" : "(__builtin_huge_val())");
+}
 
 // The constants of the rolled runs of one module.  They live in ONE device buffer whose address the engine writes into the module's
 // global `fg_jit_ctab_ptr` after loading it -- not in the source text: the generated unit then depends on the STRUCTURE of a program,
@@ -387,7 +393,7 @@ struct Gen {
                 if (in_pool) {
                     std::string tn = "fg_jit_tab" + std::to_string(tables->size());
                     std::string t = "static __device__ const double " + tn + "[" + std::to_string(K) + "] = {";
-                    for (int q = 0; q < K; ++q) t += (q ? ", " : "") + lit(p.pool[(size_t)base + K + q]);
+                    for (int q = 0; q < K; ++q) t += (q ? ", " : "") + lit_static(p.pool[(size_t)base + K + q]);
                     tables->push_back(t + "};");
                     add("{ const long long xi = " + xi + "; double lp = (xi < 0 || xi >= " + std::to_string(K) + "LL) ? FG_NEG_INF : " + tn + "[(xi < 0 || xi >= " +
                         std::to_string(K) + "LL) ? 0 : (int)xi]; " + accum + " }");

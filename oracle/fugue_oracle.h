@@ -191,6 +191,33 @@ void orc_mh_run(const orc_model *m, uint64_t seed, uint32_t chain0,
                 int n_rec, orc_cell *draws, orc_cell *final_values,
                 double *scales_out, orc_mh_stats *stats, int n_threads);
 
+/* orc_mh_run's loop from the caller's start state, with a per-step trace.
+ * start: [S][n_chains] cells (NULL = drawn from the prior, as orc_mh_run); the
+ * current log-weight is then a scoring run of them.  rec_all != 0: draws holds
+ * every step, [n_warmup + n_samples][n_rec][n_chains].  kinds_out [S][n_chains]:
+ * the cached f64 proposal kinds (0 = never decided).  final_lw [n_chains].
+ * The trace's members are [n_warmup + n_samples][n_chains] and each may be NULL:
+ * the target site, the accept flag, log_alpha, the accept uniform (NaN where
+ * log_alpha >= 0 decided without one), the target's scale after the step and
+ * the proposed cell of the target. */
+typedef struct {
+    int32_t  *target;
+    int32_t  *accept;
+    double   *log_alpha;
+    double   *u;
+    double   *scale;
+    orc_cell *proposed;
+} orc_mh_trace;
+
+void orc_mh_run_from(const orc_model *m, uint64_t seed, uint32_t chain0,
+                     int n_chains, int n_warmup, int n_samples,
+                     const orc_site_proposal *overrides, const orc_cell *start,
+                     const int *rec_sites, int n_rec, int rec_all,
+                     orc_cell *draws, orc_cell *final_values,
+                     double *scales_out, int32_t *kinds_out, double *final_lw,
+                     const orc_mh_trace *trace, orc_mh_stats *stats,
+                     int n_threads);
+
 /* ---- SMC (src/inference/smc.rs) ---- */
 enum { ORC_RESAMPLE_MULTINOMIAL = 0, ORC_RESAMPLE_SYSTEMATIC = 1,
        ORC_RESAMPLE_STRATIFIED = 2 };

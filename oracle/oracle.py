@@ -64,6 +64,11 @@ class SiteProposal(C.Structure):
     _fields_ = [("kind", C.c_int32), ("lower", C.c_double), ("upper", C.c_double)]
 
 
+class MhTrace(C.Structure):
+    _fields_ = [("target", C.c_void_p), ("accept", C.c_void_p), ("log_alpha", C.c_void_p), ("u", C.c_void_p),
+                ("scale", C.c_void_p), ("proposed", C.c_void_p)]
+
+
 class SmcConfig(C.Structure):
     _fields_ = [("resampling_method", C.c_int32), ("ess_threshold", C.c_double),
                 ("rejuvenation_steps", C.c_int32), ("batched_adaptation", C.c_int32)]
@@ -141,6 +146,8 @@ def lib():
     L.orc_adapt_update.argtypes = [dp, dp, i64p, i64p, C.c_int, C.c_double, C.c_double]
     L.orc_mh_run.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(SiteProposal),
                              ip, C.c_int, vp, vp, dp, C.POINTER(MhStats), C.c_int]
+    L.orc_mh_run_from.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(SiteProposal), vp,
+                                  ip, C.c_int, C.c_int, vp, vp, dp, vp, dp, C.POINTER(MhTrace), C.POINTER(MhStats), C.c_int]
     L.orc_systematic_indices.argtypes = [dp, C.c_int64, C.c_double, i64p]
     L.orc_stratified_indices.argtypes = [dp, C.c_int64, dp, i64p]
     L.orc_multinomial_indices.argtypes = [dp, C.c_int64, dp, i64p]
@@ -392,6 +399,40 @@ class OracleModel:
                           draws.ctypes.data if want_draws else None, final.ctypes.data, _dp(scales),
                           C.byref(st), n_threads)
         return (draws[:, :len(rec), :] if want_draws else None), final[:self.S], scales[:self.S], st
+
+    def mh_run_from(self, seed, n_chains, n_warmup, n_samples, start=None, overrides=None, chain0=0, n_threads=1):
+        """orc_mh_run's loop from `start` ([S][n_chains] int64 cells; None = the prior draw), recording every site after
+        every step.  Returns a dict: draws [n_warmup + n_samples][S][n_chains] cells, final, scales, kinds [S][n_chains],
+        log_weight [n_chains], stats, and the per-step trace [steps][n_chains]: target, accept, log_alpha, u (NaN where
+        log_alpha >= 0 decided without it), scale (the target's, after the step), proposed (the target's proposed cell)."""
+        S, T = max(1, self.S), n_warmup + n_samples
+        rec_arr = (C.c_int * S)(*range(self.S))
+        draws = np.zeros((max(1, T), S, n_chains), dtype=np.int64)
+        final = np.zeros((S, n_chains), dtype=np.int64)
+        scales = np.zeros((S, n_chains))
+        kinds = np.zeros((S, n_chains), dtype=np.int32)
+        lw = np.zeros(n_chains)
+        tr = dict(target=np.zeros((max(1, T), n_chains), dtype=np.int32), accept=np.zeros((max(1, T), n_chains), dtype=np.int32),
+                  log_alpha=np.zeros((max(1, T), n_chains)), u=np.zeros((max(1, T), n_chains)),
+                  scale=np.zeros((max(1, T), n_chains)), proposed=np.zeros((max(1, T), n_chains), dtype=np.int64))
+        trace = MhTrace(*[tr[k].ctypes.data for k in ("target", "accept", "log_alpha", "u", "scale", "proposed")])
+        st0 = None
+        if start is not None:
+            st0 = np.ascontiguousarray(start, dtype=np.int64)
+            assert st0.shape == (self.S, n_chains), st0.shape
+        ov = None
+        if overrides is not None:
+            ov = (SiteProposal * self.S)()
+            for j, o in enumerate(overrides):
+                ov[j] = SiteProposal(*o) if o is not None else SiteProposal(0, 0.0, 0.0)
+        st = MhStats()
+        self.L.orc_mh_run_from(self.h, seed, chain0, n_chains, n_warmup, n_samples, ov,
+                               st0.ctypes.data if st0 is not None else None, rec_arr, self.S, 1, draws.ctypes.data,
+                               final.ctypes.data, _dp(scales), kinds.ctypes.data, _dp(lw), C.byref(trace), C.byref(st), n_threads)
+        out = dict(draws=draws[:T, :self.S], final=final[:self.S], scales=scales[:self.S], kinds=kinds[:self.S],
+                   log_weight=lw, stats=st)
+        out.update({k: v[:T] for k, v in tr.items()})
+        return out
 
     def smc_run(self, n, seed, method=1, ess_threshold=0.5, rejuvenation_steps=0, batched=0, max_betas=10000):
         cfg = SmcConfig(method, ess_threshold, rejuvenation_steps, batched)

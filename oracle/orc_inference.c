@@ -428,9 +428,13 @@ static void propose_and_score(const orc_model *m, orc_stream *st, orc_cell *pv, 
     }
 }
 
+/* The loop of adaptive_mcmc_chain (mh.rs:938-1014) for one chain.  start == NULL: the state is drawn from the
+ * prior (mh.rs:950-957); otherwise the chain starts at the caller's cells and cur_lw is a scoring run of them.
+ * rec_all: record after every step, adapting or not.  tr: optional per-step outputs (fugue_oracle.h). */
 static void mh_one_chain(const orc_model *m, uint64_t seed, uint32_t chain, int n_warmup, int n_samples,
-                         const orc_site_proposal *ov, const int *rec, int n_rec, orc_cell *draws, int col,
-                         int n_cols, orc_cell *final_values, double *scales_out, int64_t *n_acc, int64_t *n_evals) {
+                         const orc_site_proposal *ov, const orc_cell *start, const int *rec, int n_rec, int rec_all,
+                         orc_cell *draws, int col, int n_cols, orc_cell *final_values, double *scales_out,
+                         int32_t *kinds_out, double *final_lw, const orc_mh_trace *tr, int64_t *n_acc, int64_t *n_evals) {
     int S = m->n_samples;
     orc_cell *cur = (orc_cell *)calloc((size_t)S + 1, sizeof(orc_cell));
     orc_cell *pv = (orc_cell *)calloc((size_t)S + 1, sizeof(orc_cell));
@@ -442,8 +446,13 @@ static void mh_one_chain(const orc_model *m, uint64_t seed, uint32_t chain, int 
     for (int j = 0; j < S; j++) scale[j] = 1.0;            /* get_scale: mcmc_utils.rs:70-77 */
     double acc[3];
     orc_stream st;
-    orc_stream_init(&st, seed, chain, 0, ORC_RNG_PRIOR);
-    orc_run_prior(m, &st, cur, acc, NULL);                  /* mh.rs:950-957 */
+    if (start) {
+        for (int j = 0; j < S; j++) cur[j] = start[(size_t)j * n_cols + col];
+        orc_run_score(m, cur, acc, NULL);
+    } else {
+        orc_stream_init(&st, seed, chain, 0, ORC_RNG_PRIOR);
+        orc_run_prior(m, &st, cur, acc, NULL);              /* mh.rs:950-957 */
+    }
     double cur_lw = acc[0] + acc[1] + acc[2];
     int total = n_warmup + n_samples;
     for (int iter = 0; iter < total; iter++) {
@@ -460,23 +469,43 @@ static void mh_one_chain(const orc_model *m, uint64_t seed, uint32_t chain, int 
             double prop_lw = acc[0] + acc[1] + acc[2];
             double dim_term = log((double)S) - log((double)S);
             double log_alpha = prop_lw - cur_lw + (lqr - lqf) + dim_term;
-            int accept = (log_alpha >= 0.0) || (orc_stream_u01(&st) < exp(log_alpha));
+            double u = NAN;                                 /* drawn only where log_alpha >= 0 does not decide: mh.rs:733 */
+            int accept = (log_alpha >= 0.0) || ((u = orc_stream_u01(&st)) < exp(log_alpha));
             if (adapt) orc_adapt_update(&scale[target], &lscale[target], &acc_n[target], &tot_n[target], accept, 0.44, 0.7);
+            if (tr) {
+                size_t k = (size_t)iter * n_cols + col;
+                if (tr->target) tr->target[k] = target;
+                if (tr->accept) tr->accept[k] = accept;
+                if (tr->log_alpha) tr->log_alpha[k] = log_alpha;
+                if (tr->u) tr->u[k] = u;
+                if (tr->scale) tr->scale[k] = scale[target];
+                if (tr->proposed) tr->proposed[k] = pv[target];
+            }
             if (accept) { memcpy(cur, pv, (size_t)S * sizeof(orc_cell)); cur_lw = prop_lw; *n_acc += 1; }
         }
-        if (!adapt && draws) {
-            int t = iter - n_warmup;
+        if ((!adapt || rec_all) && draws) {
+            int t = rec_all ? iter : iter - n_warmup;
             for (int r = 0; r < n_rec; r++) draws[((size_t)t * n_rec + r) * n_cols + col] = cur[rec[r]];
         }
     }
     if (final_values) for (int j = 0; j < S; j++) final_values[(size_t)j * n_cols + col] = cur[j];
     if (scales_out) for (int j = 0; j < S; j++) scales_out[(size_t)j * n_cols + col] = scale[j];
+    if (kinds_out) for (int j = 0; j < S; j++) kinds_out[(size_t)j * n_cols + col] = kind_cache[j];
+    if (final_lw) final_lw[col] = cur_lw;
     free(cur); free(pv); free(scale); free(lscale); free(acc_n); free(tot_n); free(kind_cache);
 }
 
 void orc_mh_run(const orc_model *m, uint64_t seed, uint32_t chain0, int n_chains, int n_warmup, int n_samples,
                 const orc_site_proposal *overrides, const int *rec_sites, int n_rec, orc_cell *draws,
                 orc_cell *final_values, double *scales_out, orc_mh_stats *stats, int n_threads) {
+    orc_mh_run_from(m, seed, chain0, n_chains, n_warmup, n_samples, overrides, NULL, rec_sites, n_rec, 0, draws,
+                    final_values, scales_out, NULL, NULL, NULL, stats, n_threads);
+}
+
+void orc_mh_run_from(const orc_model *m, uint64_t seed, uint32_t chain0, int n_chains, int n_warmup, int n_samples,
+                     const orc_site_proposal *overrides, const orc_cell *start, const int *rec_sites, int n_rec,
+                     int rec_all, orc_cell *draws, orc_cell *final_values, double *scales_out, int32_t *kinds_out,
+                     double *final_lw, const orc_mh_trace *trace, orc_mh_stats *stats, int n_threads) {
     int64_t n_acc = 0, n_evals = 0;
     if (n_threads < 1) n_threads = 1;
 #ifdef _OPENMP
@@ -484,8 +513,8 @@ void orc_mh_run(const orc_model *m, uint64_t seed, uint32_t chain0, int n_chains
 #endif
     for (int c = 0; c < n_chains; c++) {
         int64_t a = 0, e = 0;
-        mh_one_chain(m, seed, chain0 + (uint32_t)c, n_warmup, n_samples, overrides, rec_sites, n_rec, draws, c,
-                     n_chains, final_values, scales_out, &a, &e);
+        mh_one_chain(m, seed, chain0 + (uint32_t)c, n_warmup, n_samples, overrides, start, rec_sites, n_rec, rec_all,
+                     draws, c, n_chains, final_values, scales_out, kinds_out, final_lw, trace, &a, &e);
         n_acc += a; n_evals += e;
     }
     if (stats) {
