@@ -61,6 +61,10 @@ class fg_vi_result(C.Structure):
     _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32)]
 
 
+class fg_pf_params(C.Structure):
+    _fields_ = [("prior_sig", C.c_double), ("sig_step", C.c_double), ("sig_obs", C.c_double), ("ess_threshold", C.c_double), ("seed", C.c_uint64)]
+
+
 RESAMPLE_MULTINOMIAL, RESAMPLE_SYSTEMATIC, RESAMPLE_STRATIFIED = range(3)
 PROP_AUTO, PROP_GAUSSIAN, PROP_LOGSPACE, PROP_REFLECT, PROP_PRIOR_RESAMPLE = range(5)
 
@@ -105,6 +109,7 @@ ABI_SYMBOLS = [
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
     "fg_abc_stage_end", "fg_abc_last_round", "fg_abc_get_population", "fg_abc_set_population",
+    "fg_pf_new", "fg_pf_set_sig_obs", "fg_pf_run", "fg_pf_step", "fg_pf_log_evidence", "fg_pf_t", "fg_pf_positions", "fg_pf_free",
 ]
 
 _lib = None
@@ -291,6 +296,16 @@ def lib():
     L.fg_wpop_counts.argtypes = [vp, vp, C.c_int, ip, i64p, ip, u64p, u64p, u64p, i64p, i64p]
     L.fg_wpop_free.restype = None
     L.fg_wpop_free.argtypes = [vp]
+    L.fg_pf_new.argtypes = [C.c_int, C.c_int64, C.c_int64, C.POINTER(fg_pf_params), C.POINTER(vp)]
+    L.fg_pf_set_sig_obs.argtypes = [vp, C.c_int64, C.c_double]
+    L.fg_pf_run.argtypes = [vp, dp, C.c_int64, C.c_int, dp, dp, ip, dp, dp]
+    L.fg_pf_step.argtypes = [vp, dp, C.c_int, dp, dp, ip, dp, dp, dp, dp, dp, i64p, dp]
+    L.fg_pf_log_evidence.argtypes = [vp, dp]
+    L.fg_pf_t.restype = C.c_int64
+    L.fg_pf_t.argtypes = [vp]
+    L.fg_pf_positions.argtypes = [vp, dp]
+    L.fg_pf_free.restype = None
+    L.fg_pf_free.argtypes = [vp]
     L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]

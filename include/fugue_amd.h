@@ -761,6 +761,36 @@ int  fg_wpop_quantiles(fg_wpop *h, const double *d_x, int d, const double *h_pro
 int  fg_wpop_counts(fg_wpop *h, const void *d_cells, int n_rows, const int32_t *h_vtypes, const int64_t *h_lo,
                     const int32_t *h_bins, uint64_t *h_units, uint64_t *h_below, uint64_t *h_above, int64_t *h_min, int64_t *h_max);
 void fg_wpop_free(fg_wpop *h);                                 /* abc.rs:476 / smc.rs:445-453 */
+/* ------------------------------------------------------------------ bootstrap particle filter bank
+ * WasmParticleFilter (crates/fugue-wasm/src/pf.rs): a 1-D bootstrap filter on the random-walk model x_0 ~ N(0, prior_sig),
+ * x_t = x_{t-1} + N(0, sig_step), y_t ~ N(x_t, sig_obs), systematic resampling when ESS / n < ess_threshold, the running log-evidence.
+ * A bank is B independent filters of n particles each, one workgroup per filter, T steps in one launch (fg_pf.hip).
+ * No program and no engine: a device ordinal, as the fg_device_* calls.  Parameters are clamped as pf.rs:82-94 clamps them (each
+ * sigma .max(1e-6), the threshold .clamp(0, 1)); n is NOT clamped here: below 2 is FG_E_BAD_ARG, above the cap of one workgroup's
+ * LDS (at least the reference's 5000) FG_E_LIMIT.  Random numbers: the stream (seed, particle, time, FG_RNG_PF = 11), time 0 the
+ * initial draw, time t the transition into t; the resampling uniform of step t is the first of (seed, 0, t, FG_RNG_PF_RESAMPLE = 12).
+ * Every argument is checked before the device is touched: null handles and arrays, n_filters < 1, T < 0, per_filter outside {0, 1},
+ * a non-finite parameter or observation are FG_E_BAD_ARG.  Synchronous.  fg_pf_t counts the steps whose launch was accepted; after
+ * FG_E_HIP from a run or a step the state on the device is undefined and the handle is only good for fg_pf_free. */
+typedef struct fg_pf fg_pf;
+typedef struct fg_pf_params { double prior_sig, sig_step, sig_obs, ess_threshold; uint64_t seed; } fg_pf_params;
+/* pf.rs:74-98: params [n_filters]; draws the initial populations */
+int  fg_pf_new(int device_ordinal, int64_t n_particles, int64_t n_filters, const fg_pf_params *params, fg_pf **out);
+/* pf.rs:101-103: filter in [0, n_filters), or -1 for every filter */
+int  fg_pf_set_sig_obs(fg_pf *pf, int64_t filter, double sig_obs);
+/* pf.rs:107-172, T times: h_obs [T] shared by the filters (per_filter 0) or [n_filters][T] (per_filter 1); the summaries of every
+ * step, each [T][n_filters], any may be NULL: ess_frac, log_z_inc, resampled, and the weighted mean and variance of the propagated
+ * particles under the normalised weights (before resampling). */
+int  fg_pf_run(fg_pf *pf, const double *h_obs, int64_t T, int per_filter, double *h_ess_frac, double *h_log_z_inc, int32_t *h_resampled,
+               double *h_mean, double *h_var);
+/* pf.rs:107-172, one step: h_obs [1] or [n_filters]; the summaries [n_filters]; StepOut's arrays, each [n_filters][n], any may be NULL.
+ * The same kernel as fg_pf_run and the same bits. */
+int  fg_pf_step(fg_pf *pf, const double *h_obs, int per_filter, double *h_ess_frac, double *h_log_z_inc, int32_t *h_resampled, double *h_mean,
+                double *h_var, double *h_prev, double *h_propagated, double *h_weights, int64_t *h_parents, double *h_posterior);
+int  fg_pf_log_evidence(fg_pf *pf, double *h_out);             /* pf.rs:175-177: h_out [n_filters] */
+int64_t fg_pf_t(const fg_pf *pf);                              /* pf.rs:180-182: steps taken (-1 for a null handle) */
+int  fg_pf_positions(fg_pf *pf, double *h_x);                  /* pf.rs:169: h_x [n_filters][n] */
+void fg_pf_free(fg_pf *pf);                                    /* pf.rs:60-68 */
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

@@ -13,6 +13,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_ppc_stream { _p: [u8; 0] }
 #[repr(C)] pub struct fg_wpop { _p: [u8; 0] }
 #[repr(C)] pub struct fg_abc { _p: [u8; 0] }
+#[repr(C)] pub struct fg_pf { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -61,6 +62,8 @@ pub struct fg_vi_factor { pub family: i32, pub site: i32, pub a: f64, pub b: f64
 pub struct fg_vi_config { pub n_iterations: i32, pub convergence_window: i32, pub base_learning_rate: f64, pub fd_eps: f64, pub convergence_tol: f64, pub step_decay_exponent: f64 }
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct fg_vi_result { pub converged: i32, pub iterations: i32 }
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct fg_pf_params { pub prior_sig: f64, pub sig_step: f64, pub sig_obs: f64, pub ess_threshold: f64, pub seed: u64 }
 
 pub type fg_acov_fn = Option<unsafe extern "C" fn(user: *mut c_void, lag0: c_int, n_lags: c_int, h_sums: *mut f64) -> c_int>;
 pub type fg_reduce_fn = Option<unsafe extern "C" fn(user: *mut c_void, stage: c_int, h_in: *const f64, h_out: *mut f64) -> c_int>;
@@ -230,6 +233,17 @@ extern "C" {
     pub fn fg_wpop_counts(h: *mut fg_wpop, d_cells: *const c_void, n_rows: c_int, h_vtypes: *const i32, h_lo: *const i64, h_bins: *const i32,
                           h_units: *mut u64, h_below: *mut u64, h_above: *mut u64, h_min: *mut i64, h_max: *mut i64) -> c_int;
     pub fn fg_wpop_free(h: *mut fg_wpop);
+    // ---- bootstrap particle filter bank (fg_pf.hip): crates/fugue-wasm/src/pf.rs, B filters at once
+    pub fn fg_pf_new(device_ordinal: c_int, n_particles: i64, n_filters: i64, params: *const fg_pf_params, out: *mut *mut fg_pf) -> c_int;
+    pub fn fg_pf_set_sig_obs(pf: *mut fg_pf, filter: i64, sig_obs: f64) -> c_int;
+    pub fn fg_pf_run(pf: *mut fg_pf, h_obs: *const f64, t: i64, per_filter: c_int, h_ess_frac: *mut f64, h_log_z_inc: *mut f64, h_resampled: *mut i32,
+                     h_mean: *mut f64, h_var: *mut f64) -> c_int;
+    pub fn fg_pf_step(pf: *mut fg_pf, h_obs: *const f64, per_filter: c_int, h_ess_frac: *mut f64, h_log_z_inc: *mut f64, h_resampled: *mut i32, h_mean: *mut f64,
+                      h_var: *mut f64, h_prev: *mut f64, h_propagated: *mut f64, h_weights: *mut f64, h_parents: *mut i64, h_posterior: *mut f64) -> c_int;
+    pub fn fg_pf_log_evidence(pf: *mut fg_pf, h_out: *mut f64) -> c_int;
+    pub fn fg_pf_t(pf: *const fg_pf) -> i64;
+    pub fn fg_pf_positions(pf: *mut fg_pf, h_x: *mut f64) -> c_int;
+    pub fn fg_pf_free(pf: *mut fg_pf);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
