@@ -110,6 +110,7 @@ ABI_SYMBOLS = [
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
     "fg_abc_stage_end", "fg_abc_last_round", "fg_abc_get_population", "fg_abc_set_population",
     "fg_pf_new", "fg_pf_set_sig_obs", "fg_pf_run", "fg_pf_step", "fg_pf_log_evidence", "fg_pf_t", "fg_pf_positions", "fg_pf_free",
+    "fg_grid_new", "fg_grid_eval", "fg_grid_summary", "fg_grid_marginals", "fg_grid_mixture", "fg_grid_count", "fg_grid_free",
 ]
 
 _lib = None
@@ -306,6 +307,15 @@ def lib():
     L.fg_pf_positions.argtypes = [vp, dp]
     L.fg_pf_free.restype = None
     L.fg_pf_free.argtypes = [vp]
+    L.fg_grid_new.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int64, C.POINTER(vp)]
+    L.fg_grid_eval.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
+    L.fg_grid_summary.argtypes = [vp, dp, dp, i64p, i64p]
+    L.fg_grid_marginals.argtypes = [vp, dp, dp]
+    L.fg_grid_mixture.argtypes = [vp, dp, i64p, i64p]
+    L.fg_grid_count.restype = C.c_int64
+    L.fg_grid_count.argtypes = [vp]
+    L.fg_grid_free.restype = None
+    L.fg_grid_free.argtypes = [vp]
     L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
@@ -568,6 +578,12 @@ class Engine:
         logp = np.zeros((max(1, self.S), self.C)) if want_logp else None
         _check(lib().fg_log_joint(self.h, _dp(acc), _dp(logp) if want_logp else None))
         return (acc, logp[:self.S]) if want_logp else acc
+
+    def grid(self, site_a, a_values, site_b=None, b_values=None, base_chunk: int = 0):
+        """`fg_grid_new`: the log-joint surfaces of this engine's chains over the axes of one or two f64 sites (fugue_amd/grid.py:
+        `LogJointGrid`), sites by address or sorted index.  Close it before the engine."""
+        from .grid import LogJointGrid
+        return LogJointGrid(self, site_a, a_values, site_b, b_values, base_chunk)
 
     def result_eval(self, d_draws: Optional[int], n: int, rows: Optional[Sequence[int]] = None, out: Optional[int] = None) -> int:
         """`fg_result_eval`: the model's return value for every draw and chain of the device buffer d_draws [n][n_rows][C] (row j =

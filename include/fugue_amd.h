@@ -791,6 +791,37 @@ int  fg_pf_log_evidence(fg_pf *pf, double *h_out);             /* pf.rs:175-177:
 int64_t fg_pf_t(const fg_pf *pf);                              /* pf.rs:180-182: steps taken (-1 for a null handle) */
 int  fg_pf_positions(fg_pf *pf, double *h_x);                  /* pf.rs:169: h_x [n_filters][n] */
 void fg_pf_free(fg_pf *pf);                                    /* pf.rs:60-68 */
+/* ------------------------------------------------------------------ log-joint surfaces over one or two sites
+ * log_joint_grid (crates/fugue-wasm/src/grid.rs): for two f64 sample sites and axes a_values [n_a], b_values [n_b], cell (j, i) is
+ * the total log weight (prior + likelihood + factors, as lj_out of a scoring run) of a base trace with a := a_values[i] and then
+ * b := b_values[j] (the same site twice: b wins), row-major out[j * n_a + i].  A base is an engine chain; the engine's values, its
+ * log-joint and every other state word are read only.  Axis values are scored as given: a non-finite or out-of-support value gives
+ * what ScoreGivenTrace gives, never an error.  Per base the handle keeps (n_a + n_b + 6 words on the host) log_marg_a[i] =
+ * log_sum_exp of column i, log_marg_b[j] = log_sum_exp of row j, log_norm = log_sum_exp of the row marginals (numerical.rs:15-38,
+ * rule for rule), the maximum and its flat index by the fold of wasm.rs:115-124 (strict > from -inf: the first maximum, NaN never
+ * wins, -1 when no cell exceeds -inf) and the counts of NaN, -inf and +inf cells; over the bases that arrive it accumulates
+ * mix[cell] += exp(lj[c][cell] - log_norm[c]) for the bases of finite log_norm, in arrival order.  Every sum's order is a function
+ * of (n_a, n_b) alone (fg_grid_plan.h): a base gives the same bits alone or in a bank, under any base_chunk, in one
+ * call or several, with or without d_out.  Synchronous on the engine's stream.  Free the handle before its engine. */
+typedef struct fg_grid fg_grid;
+/* grid.rs:22-46: site_a / site_b sorted site indices (site_b == -1: one axis, h_b and n_b ignored, n_b = 1); h_a [n_a], h_b [n_b];
+ * base_chunk = bases per launch and chunk table (0: the largest that keeps the table under 256 MiB, at least 1).  FG_E_BAD_ARG: a
+ * site that is not an f64 sample site (the reference's message), n_a or n_b < 1, base_chunk < 0, a null axis.  FG_E_LIMIT: 2^31
+ * cells or more; a program whose tile lives in global memory. */
+int  fg_grid_new(fg_engine *e, int site_a, int site_b, const double *h_a, int64_t n_a, const double *h_b, int64_t n_b, int64_t base_chunk,
+                 fg_grid **out);
+/* grid.rs:48-67 for the bases = engine chains [chain0, chain0 + n_bases) (FG_E_BAD_ARG unless 0 <= chain0, 1 <= n_bases and
+ * chain0 + n_bases <= n_chains): d_out [n_bases][n_b][n_a] and d_acc [3][n_bases][n_b][n_a] (prior, likelihood, factors) are device
+ * tables of the caller, either may be NULL. */
+int  fg_grid_eval(fg_grid *g, int64_t chain0, int64_t n_bases, double *d_out, double *d_acc);
+/* grid.rs:48-67, wasm.rs:115-124: per base that has arrived (n = fg_grid_count), any may be NULL: h_log_norm [n], h_max [n],
+ * h_argmax [n], h_counts [n][3] = n_nan, n_neg_inf, n_pos_inf.  FG_E_STATE before any base has arrived (the three read-outs). */
+int  fg_grid_summary(fg_grid *g, double *h_log_norm, double *h_max, int64_t *h_argmax, int64_t *h_counts);
+int  fg_grid_marginals(fg_grid *g, double *h_log_marg_a, double *h_log_marg_b);   /* grid.rs:48-67: [n][n_a], [n][n_b]; either may be NULL */
+/* grid.rs:48-67: h_log_mix [n_b][n_a] = ln(mix / n_mixed) (NaN when n_mixed is 0); the bases mixed and skipped; any may be NULL */
+int  fg_grid_mixture(fg_grid *g, double *h_log_mix, int64_t *n_mixed, int64_t *n_skipped);
+int64_t fg_grid_count(const fg_grid *g);                       /* grid.rs:48-67: bases that have arrived (-1 for a null handle) */
+void fg_grid_free(fg_grid *g);                                 /* grid.rs:22-69 */
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

@@ -14,6 +14,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_wpop { _p: [u8; 0] }
 #[repr(C)] pub struct fg_abc { _p: [u8; 0] }
 #[repr(C)] pub struct fg_pf { _p: [u8; 0] }
+#[repr(C)] pub struct fg_grid { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -244,6 +245,15 @@ extern "C" {
     pub fn fg_pf_t(pf: *const fg_pf) -> i64;
     pub fn fg_pf_positions(pf: *mut fg_pf, h_x: *mut f64) -> c_int;
     pub fn fg_pf_free(pf: *mut fg_pf);
+    // ---- log-joint surfaces over one or two sites (fg_grid.hip): crates/fugue-wasm/src/grid.rs, a bank of bases at once
+    pub fn fg_grid_new(e: *mut fg_engine, site_a: c_int, site_b: c_int, h_a: *const f64, n_a: i64, h_b: *const f64, n_b: i64, base_chunk: i64,
+                       out: *mut *mut fg_grid) -> c_int;
+    pub fn fg_grid_eval(g: *mut fg_grid, chain0: i64, n_bases: i64, d_out: *mut f64, d_acc: *mut f64) -> c_int;
+    pub fn fg_grid_summary(g: *mut fg_grid, h_log_norm: *mut f64, h_max: *mut f64, h_argmax: *mut i64, h_counts: *mut i64) -> c_int;
+    pub fn fg_grid_marginals(g: *mut fg_grid, h_log_marg_a: *mut f64, h_log_marg_b: *mut f64) -> c_int;
+    pub fn fg_grid_mixture(g: *mut fg_grid, h_log_mix: *mut f64, n_mixed: *mut i64, n_skipped: *mut i64) -> c_int;
+    pub fn fg_grid_count(g: *const fg_grid) -> i64;
+    pub fn fg_grid_free(g: *mut fg_grid);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
