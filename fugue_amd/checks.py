@@ -8,7 +8,11 @@ hold the replicates (`ChainSummary.checks`); `posterior_predictive_check` takes 
 `PriorPredictive` and feeds them as one chunk -- the same figures bit for bit, since the stream does not depend on the chunking.
 
 A check is a group of observe addresses (`CheckSpec`); a slot is one statistic of one check.  The draws of an SMC population are
-weighted and the counts here are not: an `SMCResult` is refused."""
+weighted and the counts here are not: an `SMCResult` is refused.
+
+A weighted population has `weighted_predictive_check` (a stored `SMCResult`) and `adaptive_smc_summary(checks=...)` (on the device,
+`PopulationSummary.checks`): the same statistics of one replicate per particle, the p-values as quotients of the units
+rint(w 2^52) of the weights -- exact integers (`WeightedPredictiveCheck`; `WeightedPopulation.checks`, fg_wpop_eval.hip)."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -214,3 +218,85 @@ def posterior_predictive_check(x, checks: Optional[Sequence[CheckSpec]] = None, 
         if buf is not None:
             eng.device_free(buf)
         eng.close()
+
+
+@dataclass
+class WeightedPredictiveCheck:
+    """Per slot (`names[k]`, `statistics[k]`; [n_slots] each) over the `n_particles` particles of a weighted population of `T` units
+    (rint(w 2^52) each): `t_obs`; `units` uint64 [n_slots][4], the units of the particles whose replicated statistic is below / equal
+    to / above the observed one, or where either side is NaN (they enter no p-value); `counts` int64 [n_slots][4], the particles of
+    non-zero units behind them; `p_ge`, `p_gt`, `p_mid`, quotients of unit sums (NaN for a denominator of 0); `t_rep_mean`,
+    `t_rep_sd`, `t_rep_mcse`, `n_used`: the weighted moments of the finite replicated statistics (`WeightedPopulation.moments`)."""
+    names: List[str]
+    statistics: List[str]
+    n_particles: int
+    T: int
+    t_obs: np.ndarray
+    units: np.ndarray
+    counts: np.ndarray
+    p_ge: np.ndarray
+    p_gt: np.ndarray
+    p_mid: np.ndarray
+    t_rep_mean: np.ndarray
+    t_rep_sd: np.ndarray
+    t_rep_mcse: np.ndarray
+    n_used: np.ndarray
+
+    @classmethod
+    def from_parts(cls, specs: Sequence[CheckSpec], parts: Sequence[Tuple[int, dict]], n_particles: int, T: int) -> "WeightedPredictiveCheck":
+        """From the results of `WeightedPopulation.checks` over consecutive groups of `specs`: [(index of the group's first check, result)]."""
+        names = [specs[q0 + q].name for q0, r in parts for q, _ in r["slots"]]
+        stats = [STATISTICS[st] for _, r in parts for _, st in r["slots"]]
+        cat = lambda key: np.concatenate([np.asarray(r[key]) for _, r in parts])
+        return cls(names, stats, int(n_particles), int(T), cat("t_obs"), cat("units"), cat("counts"), cat("p_ge"), cat("p_gt"), cat("p_mid"), cat("mean"), cat("std"),
+                   cat("mcse"), cat("n_used"))
+
+    @property
+    def n_slots(self) -> int:
+        return len(self.names)
+
+    def slot(self, name: str, statistic: str) -> int:
+        for k, (a, st) in enumerate(zip(self.names, self.statistics)):
+            if a == name and st == statistic:
+                return k
+        raise KeyError(f"no slot ({name!r}, {statistic!r})")
+
+
+def check_groups(tuples, N: int, budget_words: int = 1 << 24):
+    """Consecutive checks whose member rows together stay within `budget_words` cells of N each (a single check that does not is a
+    group of its own): [(first check, rows of the group, the group's checks over those rows)]."""
+    cap = max(1, budget_words // max(int(N), 1))
+    out, q = [], 0
+    while q < len(tuples):
+        rows, q1 = set(tuples[q][0]), q + 1
+        while q1 < len(tuples) and len(rows | set(tuples[q1][0])) <= cap:
+            rows |= set(tuples[q1][0])
+            q1 += 1
+        sel = sorted(rows)
+        out.append((q, sel, [([sel.index(k) for k in r], st, ob) for r, st, ob in tuples[q:q1]]))
+        q = q1
+    return out
+
+
+def weighted_predictive_check(smc, checks: Optional[Sequence[CheckSpec]] = None, observed: Optional[Dict[str, float]] = None, device: int = 0) -> WeightedPredictiveCheck:
+    """The checks of the stored replicates of an `SMCResult` (`adaptive_smc(predictive=True)`: one replicate per particle) under its
+    weights: cells and weights are uploaded and run through `WeightedPopulation.checks`, the entry `adaptive_smc_summary(checks=...)`
+    runs where the population lies -- the same bytes.  `checks` / `observed` as `posterior_predictive_check` takes them.  Weights that
+    are not all in [0, 1] raise ValueError (n_bad > 0), as the summary does."""
+    who = "weighted_predictive_check"
+    cells, w = getattr(smc, "predictive", None), getattr(smc, "weights", None)
+    if w is None:
+        raise ValueError(f"{who}: no weights (an unweighted batch goes to posterior_predictive_check)")
+    if cells is None or not hasattr(smc, "predictive_vtypes"):
+        raise ValueError(f"{who}: no stored replicates (run adaptive_smc with predictive=True)")
+    cells, w = np.ascontiguousarray(cells, dtype=np.int64), np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if cells.ndim != 2 or min(cells.shape) < 1 or cells.shape[1] != w.size:
+        raise ValueError(f"{who}: the replicates must be [n_sel][N] with N = {w.size} weights, not {cells.shape}")
+    n_bad = int(np.count_nonzero(~((w >= 0.0) & (w <= 1.0))))
+    if n_bad > 0:
+        raise ValueError(f"{who}: n_bad = {n_bad} of {w.size} weights are NaN, negative, infinite or above 1: the population is not normalised")
+    names, vtypes = list(smc.predictive_names), [int(v) for v in smc.predictive_vtypes]
+    stated = [(getattr(smc, "observe_values", None) or {}).get(a) for a in names]
+    specs, tuples = resolve_checks(checks, names, stated, observed, who)
+    with E.stored_population(w, cells, device) as (wp, d_cells):
+        return WeightedPredictiveCheck.from_parts(specs, [(0, wp.checks(d_cells, vtypes, tuples))], w.size, wp.units()["T"])

@@ -10,7 +10,11 @@ chunking.
 eq. 7.12 and the R `loo` package; ArviZ divides by N).  `elpd_loo` is plain importance-sampling LOO with the raw ratios
 r = exp(-log-likelihood): no Pareto smoothing, no k-hat.  `is_ess` = (sum r)^2 / sum r^2 and `max_weight` = max r / sum r are the
 honest diagnostic of those raw ratios: an `is_ess` of a few, or a `max_weight` near 1, says the estimate of that statement rests on
-a handful of draws."""
+a handful of draws.
+
+A weighted population has `weighted_model_comparison` (a stored `SMCResult`) and `adaptive_smc_summary(pointwise=...)` (on the device,
+`PopulationSummary.comparison`): the same figures under the particles' weights (`WeightedComparison`; `WeightedPopulation.loglik`,
+fg_wpop_eval.hip), `p_waic` in its reliability-weights form ssd / (W - sum w^2 / W), which is the divisor N - 1 at equal weights."""
 from __future__ import annotations
 
 import math
@@ -138,3 +142,43 @@ def compare_models(a: PointwiseComparison, b: PointwiseComparison, which: str = 
         raise ValueError("compare_models: the two comparisons name different observe statements")
     pa, pb = np.asarray(getattr(a, which), dtype=np.float64), np.asarray(getattr(b, which), dtype=np.float64)
     return _total(pa) - _total(pb), _se(pa - pb)
+
+
+@dataclass
+class WeightedComparison(PointwiseComparison):
+    """`PointwiseComparison` under the weights of a population of `n_draws` particles (so `compare_models` takes it as it stands):
+    lppd = ln(sum w exp x / W), elpd_loo = -ln(sum w exp(-x) / W), p_waic = ssd / (W_fin - sum w^2 / W_fin), is_ess = the Kish
+    effective size of the weights w exp(-x), in particles.  The counters count the cells of the particles that take part (a good
+    weight above zero): `n_fin` finite ones beside -inf / +inf / NaN; `words` [n_sel][12] in the order `engine.WLL_WORDS`.  A statement
+    without a finite participating cell has NaN figures."""
+    n_fin: np.ndarray = None
+    words: np.ndarray = None
+
+    @classmethod
+    def from_parts(cls, names: Sequence[str], n_particles: int, parts: Sequence[dict]) -> "WeightedComparison":
+        """From the results of `WeightedPopulation.loglik` over consecutive slices of the statements."""
+        cat = lambda key: np.concatenate([np.asarray(r[key]) for r in parts])
+        return cls(names=list(names), n_draws=int(n_particles), **{k: cat(k) for k in POINTWISE + ("n_neg_inf", "n_pos_inf", "n_nan", "n_fin", "words")})
+
+
+def weighted_model_comparison(smc, names: Optional[Sequence[str]] = None, device: int = 0) -> WeightedComparison:
+    """WAIC / IS-LOO of the stored pointwise log-likelihood of an `SMCResult` (`adaptive_smc(pointwise=True)`: [n_sel][N]) under its
+    weights: table and weights are uploaded and run through `WeightedPopulation.loglik`, the entry `adaptive_smc_summary(pointwise=...)`
+    runs where the population lies -- the same bytes.  Weights that are not all in [0, 1] raise ValueError (n_bad > 0)."""
+    who = "weighted_model_comparison"
+    ll, w = getattr(smc, "log_likelihood", None), getattr(smc, "weights", None)
+    if w is None:
+        raise ValueError(f"{who}: no weights (an unweighted table goes to model_comparison)")
+    if ll is None:
+        raise ValueError(f"{who}: the SMCResult has no log_likelihood (run adaptive_smc with pointwise=True)")
+    table, w = np.ascontiguousarray(ll, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if table.ndim != 2 or min(table.shape) < 1 or table.shape[1] != w.size:
+        raise ValueError(f"{who}: the table must be [n_sel][N] with N = {w.size} weights, not {table.shape}")
+    n_bad = int(np.count_nonzero(~((w >= 0.0) & (w <= 1.0))))
+    if n_bad > 0:
+        raise ValueError(f"{who}: n_bad = {n_bad} of {w.size} weights are NaN, negative, infinite or above 1: the population is not normalised")
+    names = list(getattr(smc, "predictive_names", None) or [f"observe#{k}" for k in range(table.shape[0])]) if names is None else [str(a) for a in names]
+    if len(names) != table.shape[0]:
+        raise ValueError(f"{who}: {len(names)} names for {table.shape[0]} statements")
+    with E.stored_population(w, table, device) as (wp, d_table):
+        return WeightedComparison.from_parts(names, w.size, [wp.loglik(d_table, table.shape[0])])

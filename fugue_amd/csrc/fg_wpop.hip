@@ -9,18 +9,7 @@
 //   tab  [H + K][4]   row | prefix | offset of the group's pairs | its element count m
 //   ctr  units [H][nb] | elements [H][nb] | mn [H] (as ~key under atomicMax, so 0 is "none yet") | mx [H] | cursor [K]
 //   pairs [sum of the collect groups' m][2]   key, units
-#include "fg_engine_internal.h"
-#include "fg_wpop_plan.h"
-
-#define FG_WP_WAVES (FG_WP_THREADS / 64)
-
-struct fg_wpop {
-    fg_engine *e = nullptr;
-    long long n = 0;
-    double *d_w = nullptr;                   // [n] the weights as they were at fg_wpop_new
-    unsigned long long *d_q = nullptr;       // [n] their units
-    uint64_t T = 0, n_bad = 0, n_zero = 0;
-};
+#include "fg_wpop_internal.h"
 
 // w -> q, and the four sums: bad weights, good weights of zero units, the units' high and low halves.  Wave reduction, LDS, then one
 // 64-bit atomic per block and non-zero sum.
@@ -65,18 +54,6 @@ __global__ __launch_bounds__(FG_WP_THREADS) void k_wpop_terms(long long n, long 
     const double mu = mean[k];
     for (long long i = (long long)blockIdx.x * FG_WP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * FG_WP_THREADS)
         st[k * n + i] = fg_wp_mcse_term(st[k * n + i], st[(rows + k) * n + i], mu);
-}
-
-// min / max of a block's keys: wave reduction, LDS, then thread 0 holds them (a > z: the block saw none)
-__device__ __forceinline__ void wp_block_minmax(unsigned long long &a, unsigned long long &z, unsigned long long (*mm)[2]) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long a2 = __shfl_down(a, o, 64), z2 = __shfl_down(z, o, 64);
-        a = a2 < a ? a2 : a; z = z2 > z ? z2 : z;
-    }
-    if ((threadIdx.x & 63) == 0) { mm[threadIdx.x >> 6][0] = a; mm[threadIdx.x >> 6][1] = z; }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int v = 1; v < FG_WP_WAVES; ++v) { a = mm[v][0] < a ? mm[v][0] : a; z = mm[v][1] > z ? mm[v][1] : z; }
 }
 
 // One group per grid row (blockIdx.y), grid-stride over the n elements of its row.  An element of non-zero units whose key matches
@@ -175,27 +152,6 @@ __global__ __launch_bounds__(FG_WP_THREADS) void k_wpop_counts(const unsigned lo
     for (int j = threadIdx.x; j < bins; j += FG_WP_THREADS)
         if (hist[j]) atomicAdd(&ctr[off + j], hist[j]);
 }
-
-namespace {
-
-struct WpScope {                             // device buffers of one call
-    std::vector<void *> p;
-    ~WpScope() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    int alloc(T **out, size_t n, const char *what) {
-        if (hipMalloc((void **)out, (n ? n : 1) * sizeof(T)) != hipSuccess) { fg_set_error(std::string("fg_wpop: no device memory for ") + what); return FG_E_HIP; }
-        p.push_back(*out);
-        return FG_OK;
-    }
-};
-
-int need_wpop(const fg_wpop *h) {
-    if (!h || !h->e) { fg_set_error("null weighted population"); return FG_E_BAD_ARG; }
-    if (hipSetDevice(h->e->device) != hipSuccess) { fg_set_error("hipSetDevice failed"); return FG_E_HIP; }
-    return FG_OK;
-}
-
-}  // namespace
 
 extern "C" {
 

@@ -6,6 +6,7 @@ gfx950 device is present.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -104,7 +105,7 @@ ABI_SYMBOLS = [
     "fg_loglik_stream_new", "fg_loglik_stream_update", "fg_loglik_stream_count", "fg_loglik_stream_pooled", "fg_loglik_stream_result", "fg_loglik_stream_free",
     "fg_ppc_stream_new", "fg_ppc_stream_update", "fg_ppc_stream_count", "fg_ppc_stream_n_slots", "fg_ppc_stream_observed", "fg_ppc_stream_pooled",
     "fg_ppc_stream_chains", "fg_ppc_stream_free", "fg_program_observe_value",
-    "fg_wpop_new", "fg_wpop_units", "fg_wpop_moments", "fg_wpop_quantiles", "fg_wpop_counts", "fg_wpop_free",
+    "fg_wpop_new", "fg_wpop_units", "fg_wpop_moments", "fg_wpop_quantiles", "fg_wpop_counts", "fg_wpop_free", "fg_wpop_checks_n_slots", "fg_wpop_checks", "fg_wpop_loglik",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -295,6 +296,9 @@ def lib():
     L.fg_wpop_moments.argtypes = [vp, vp, C.c_int, dp]
     L.fg_wpop_quantiles.argtypes = [vp, vp, C.c_int, dp, C.c_int, C.c_int, C.c_int64, dp, ip]
     L.fg_wpop_counts.argtypes = [vp, vp, C.c_int, ip, i64p, ip, u64p, u64p, u64p, i64p, i64p]
+    L.fg_wpop_checks_n_slots.argtypes = [C.c_int, ip]
+    L.fg_wpop_checks.argtypes = [vp, vp, C.c_int, ip, C.c_int, ip, ip, ip, dp, dp, u64p, i64p, dp]
+    L.fg_wpop_loglik.argtypes = [vp, vp, C.c_int, dp, dp, i64p]
     L.fg_wpop_free.restype = None
     L.fg_wpop_free.argtypes = [vp]
     L.fg_pf_new.argtypes = [C.c_int, C.c_int64, C.c_int64, C.POINTER(fg_pf_params), C.POINTER(vp)]
@@ -1254,6 +1258,26 @@ PPC_COUNTS = ("n_lt", "n_eq", "n_gt", "n_nan", "n_fin")
 PPC_SCRATCH_DRAWS = 16                                    # FG_PPC_SCRATCH_DRAWS (fg_ppc_stream_plan.h): an update walks its chunk in pieces of that many draws
 
 
+def _ppc_csr(checks):
+    """checks [(rows, statistics, observed)] -> (offsets, members, masks, observed, slots): the CSR form of the C entry points, and the
+    (check, statistic) pair of every slot."""
+    offsets, members, masks, observed, slots = [0], [], [], [], []
+    for q, (rows, stats, obs) in enumerate(checks):
+        rows, obs = [int(r) for r in rows], [float(v) for v in obs]
+        if len(rows) != len(obs):
+            raise ValueError(f"check {q}: {len(rows)} members and {len(obs)} observed values")
+        ids = sorted({PPC_STATS.index(st) if isinstance(st, str) else int(st) for st in stats})
+        mask = 0
+        for st in ids:
+            mask |= 1 << st
+        members += rows
+        observed += obs
+        offsets.append(len(members))
+        masks.append(mask)
+        slots += [(q, st) for st in ids if 0 <= st < len(PPC_STATS)]
+    return offsets, members, masks, observed, slots
+
+
 class PpcStream(_Stream):
     """`fg_ppc_stream` (fg_ppc_stream.hip): test statistics of every replicated data set of a run handed over in chunks
     [n_chunk][n_rows][C] of raw cells (`Engine.predict_eval`'s cell table), compared with the observed ones -- what the reference's
@@ -1268,20 +1292,7 @@ class PpcStream(_Stream):
         self._integers(n_total=n_total)
         self.engine, self.n, self.h = engine, int(n_total), None
         vt = [int(v) for v in vtypes]
-        offsets, members, masks, observed, self.slots = [0], [], [], [], []
-        for q, (rows, stats, obs) in enumerate(checks):
-            rows, obs = [int(r) for r in rows], [float(v) for v in obs]
-            if len(rows) != len(obs):
-                raise ValueError(f"check {q}: {len(rows)} members and {len(obs)} observed values")
-            ids = sorted({PPC_STATS.index(st) if isinstance(st, str) else int(st) for st in stats})
-            mask = 0
-            for st in ids:
-                mask |= 1 << st
-            members += rows
-            observed += obs
-            offsets.append(len(members))
-            masks.append(mask)
-            self.slots += [(q, st) for st in ids if 0 <= st < len(PPC_STATS)]
+        offsets, members, masks, observed, self.slots = _ppc_csr(checks)
         i32 = lambda v: (C.c_int32 * max(1, len(v)))(*v)
         out = C.c_void_p()
         _check(lib().fg_ppc_stream_new(engine.h, self.n, len(vt), i32(vt), len(masks), i32(offsets), i32(members), i32(masks),
@@ -1322,6 +1333,9 @@ class PpcStream(_Stream):
 
 
 WPOP_MOMENTS = ("W", "mean", "var", "std", "mcse", "n_used")      # FG_WPOP_MOMENTS words per row
+WPOP_CATS = ("lt", "eq", "gt", "nan")                             # FG_WPOP_CATS categories per slot
+WLL_WORDS = ("W", "W_fin", "W2", "mean", "ssd", "n_used", "mx", "mn", "sp", "sn", "sn2", "tmax")      # FG_WLL_WORDS words per row
+WLL_COUNTS = ("n_fin", "n_neg_inf", "n_pos_inf", "n_nan")         # FG_WLL_COUNTS counters per row
 
 
 class WeightedPopulation(_Stream):
@@ -1407,7 +1421,86 @@ class WeightedPopulation(_Stream):
         ints = lambda a: [None if T == 0 else (int(v) & (2 ** 64 - 1) if vt[k] == M.U64 else int(v)) for k, v in enumerate(a)]
         return dict(units=[flat[at[k]:at[k + 1]].copy() for k in range(nr)], below=below, above=above, min=ints(mn), max=ints(mx), T=T)
 
+    def checks(self, d_yrep: int, vtypes: Sequence[int], checks, observed=None) -> dict:
+        """Weighted predictive checks of ONE replicate per particle, d_yrep a device buffer of cells [len(vtypes)][n]: `checks` as
+        `PpcStream` takes them, [(rows, statistics, observed values)], or [(rows, statistics)] with `observed` the vectors.  Per slot
+        (`slots`: (check, statistic)): t_obs; units uint64 [n_slots][4] and counts int64 [n_slots][4], the units and the particles of
+        non-zero units whose replicated statistic is below / equal to / above the observed one, or where either is NaN; p_ge, p_gt,
+        p_mid, quotients of unit sums (NaN for a denominator of 0); W, mean, var, std, mcse, n_used of the replicated statistic."""
+        if observed is not None:
+            checks = [(c[0], c[1], o) for c, o in zip(checks, observed)]
+        vt = [int(v) for v in vtypes]
+        offsets, members, masks, obs, slots = _ppc_csr(checks)
+        if not 1 <= len(vt) <= 65535:
+            raise ValueError("between 1 and 65535 rows")
+        i32 = lambda v: (C.c_int32 * max(1, len(v)))(*v)
+        n_slots = int(lib().fg_wpop_checks_n_slots(len(masks), i32(masks)))
+        if n_slots < 0:
+            _check(n_slots)
+        t_obs, units, counts = np.zeros(n_slots), np.zeros((n_slots, len(WPOP_CATS)), dtype=np.uint64), np.zeros((n_slots, len(WPOP_CATS)), dtype=np.int64)
+        mom = np.zeros((n_slots, len(WPOP_MOMENTS)))
+        _check(lib().fg_wpop_checks(self._handle(), d_yrep, len(vt), i32(vt), len(masks), i32(offsets), i32(members), i32(masks), (C.c_double * max(1, len(obs)))(*obs),
+                                    _dp(t_obs), units.ctypes.data_as(C.POINTER(C.c_uint64)), counts.ctypes.data_as(C.POINTER(C.c_int64)), _dp(mom)))
+        res = dict(slots=slots, t_obs=t_obs, units=units, counts=counts)
+        res.update(wpop_p_values(units))
+        res.update({name: mom[:, j].copy() for j, name in enumerate(WPOP_MOMENTS)})
+        res["n_used"] = res["n_used"].astype(np.int64)
+        return res
+
+    def loglik(self, d_ll: int, n_sel: int) -> dict:
+        """Weighted WAIC / IS-LOO of rows d_ll [n_sel][n] of doubles: the figures of `LoglikStream.result` (lppd, mean_ll, p_waic in
+        its reliability-weights form, elpd_waic, elpd_loo, p_loo, is_ess, max_weight), each float64 [n_sel]; `words` float64
+        [n_sel][12] in the order WLL_WORDS; n_fin, n_neg_inf, n_pos_inf, n_nan int64 [n_sel], over the cells of the particles that take
+        part (a good weight above zero)."""
+        self._integers(n_sel=n_sel)
+        if not 1 <= n_sel <= 65535:
+            raise ValueError("n_sel must lie in [1, 65535]")
+        figs, words, counts = np.zeros((LL_FIGURES, int(n_sel))), np.zeros((int(n_sel), len(WLL_WORDS))), np.zeros((int(n_sel), len(WLL_COUNTS)), dtype=np.int64)
+        _check(lib().fg_wpop_loglik(self._handle(), d_ll, int(n_sel), _dp(figs), _dp(words), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = {name: figs[i].copy() for i, name in enumerate(LL_FIGURE_NAMES)}
+        out.update({name: counts[:, i].copy() for i, name in enumerate(WLL_COUNTS)})
+        out["words"] = words
+        return out
+
     free = _Stream.close
+
+
+_HOLDER_PROGRAM = None
+
+
+@contextlib.contextmanager
+def stored_population(weights: np.ndarray, table: np.ndarray, device: int = 0):
+    """A stored weighted population on the device: uploads `weights` [N] and `table` [rows][N] and yields (WeightedPopulation, device
+    pointer of the table); everything is freed on exit.  The handle needs an engine only for its device and stream: one chain of a
+    one-site model, compiled once per process."""
+    global _HOLDER_PROGRAM
+    if _HOLDER_PROGRAM is None:
+        from . import workloads as _W
+        _HOLDER_PROGRAM = compile_model(_W.normal_sites(1))
+    eng = Engine(_HOLDER_PROGRAM, 1, seed=0, device=device)
+    bufs, wp = [], None
+    try:
+        bufs.append(eng.upload(np.ascontiguousarray(weights, dtype=np.float64)))
+        wp = eng.wpop(int(np.size(weights)), bufs[0])
+        bufs.append(eng.upload(np.ascontiguousarray(table)))
+        yield wp, bufs[1]
+    finally:
+        if wp is not None:
+            wp.close()
+        for b in bufs:
+            eng.device_free(b)
+        eng.close()
+
+
+def wpop_p_values(units) -> dict:
+    """p_ge, p_gt, p_mid [n_slots] from unit sums [n_slots][4] (lt, eq, gt, nan): integers first, one division each (fg_wpe_p_values)."""
+    out = {k: [] for k in ("p_ge", "p_gt", "p_mid")}
+    for lt, eq, gt, _ in ([int(v) for v in row] for row in np.asarray(units).reshape(-1, 4)):
+        den = lt + eq + gt
+        out["p_ge"].append(float(gt + eq) / float(den) if den else float("nan"))
+        out["p_gt"].append(float(gt) / float(den) if den else float("nan"))
+        out["p_mid"].append(float(2 * gt + eq) / float(2 * den) if den else float("nan"))
+    return {k: np.array(v, dtype=np.float64) for k, v in out.items()}
 
 
 # ---- population-wide device primitives (no program needed) -----------------------------------

@@ -777,6 +777,8 @@ class PopulationSummary:
     predictive_names: List[str] = field(default_factory=list)
     tables: Optional[WeightedTables] = None
     passes: Optional[np.ndarray] = None   # [rows][len(probs)]: the passes over its row each quantile took
+    comparison: Optional["WeightedComparison"] = None          # pointwise=: weighted WAIC / IS-LOO per selected observe statement (fugue_amd.comparison)
+    checks: Optional["WeightedPredictiveCheck"] = None         # checks=: weighted predictive checks of one replicate per particle (fugue_amd.checks)
 
     def row(self, name: str) -> int:
         if name not in self.names:
@@ -791,20 +793,26 @@ def _empty_population_summary(names, probs, sites, result_names, predictive_name
 
 
 def population_summary(eng, log_evidence: float = 0.0, betas=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975), results: bool = False, predictive=False,
-                       discrete: bool = False, digit_bits: int = 12, capacity: int = 65536, seed_iter: int = 0) -> PopulationSummary:
+                       discrete: bool = False, digit_bits: int = 12, capacity: int = 65536, seed_iter: int = 0, pointwise=False, checks=False,
+                       stage_words: int = 1 << 24) -> PopulationSummary:
     """The summary of the particle population an engine holds (after `smc_run(download=False)` or the standalone SMC calls), on the
-    device: nothing of size N comes to the host, and neither the engine's values nor its weights change.  See `adaptive_smc_summary`."""
+    device: nothing of size N comes to the host, and neither the engine's values nor its weights change.  See `adaptive_smc_summary`.
+    `stage_words`: the cells of the reused buffer `pointwise=` / `checks=` draw into, so statements are taken `stage_words // N` at a
+    time, at least one (the default is the moments' staging budget; the figures do not depend on it, the number of `fg_predict_eval`
+    calls does)."""
     cp, N = eng.cp, eng.C
     who = "adaptive_smc_summary"
     pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
     _want_results(cp, results, who=who)
     psel = _summary_predictive(cp, predictive, who)
+    lsel = _summary_pointwise(cp, pointwise, who)
+    csel = _summary_checks(cp, checks, who)
     sites = [cp.site_names[j] for j in cp.f64_sites]
     rnames = list(cp.result_names) if results else []
     pnames = [cp.observe_names[k] for k in psel] if psel is not None else []
     names = sites + rnames + pnames
     disc = [j for j in range(cp.S) if cp.site_vtypes[j] != M.F64] if discrete else []
-    if not names and not disc:
+    if not names and not disc and lsel is None and csel is None:
         raise ValueError(f"{who}: nothing to summarise: the model has no f64 site, and neither results, predictive nor discrete adds a row")
     values = E.lib().fg_engine_values_device(eng.h)
     wp, buffers = None, []
@@ -835,6 +843,27 @@ def population_summary(eng, log_evidence: float = 0.0, betas=None, probs=(0.025,
             lb = [_default_bins(cp, j) for j in disc]
             t = wp.counts(cells, vt, [a for a, _ in lb], [b for _, b in lb])
             out.tables = WeightedTables([cp.site_names[j] for j in disc], vt, [a for a, _ in lb], [b for _, b in lb], t["units"], t["below"], t["above"], t["min"], t["max"], t["T"])
+        if lsel is not None:                             # statements in slices of at most stage_words / N into one reused buffer
+            from .comparison import WeightedComparison
+            per = max(1, min(len(lsel), int(stage_words) // N))
+            buf = eng.device_alloc(per * N * 8)
+            buffers.append(buf)
+            parts = []
+            for a in range(0, len(lsel), per):
+                eng.predict_eval(None, 1, iter0=seed_iter, sel=lsel[a:a + per], out=False, loglik=buf)
+                parts.append(wp.loglik(buf, len(lsel[a:a + per])))
+            out.comparison = WeightedComparison.from_parts([cp.observe_names[k] for k in lsel], N, parts)
+        if csel is not None:                             # checks in groups whose member statements fit the same budget
+            from .checks import WeightedPredictiveCheck, check_groups
+            groups = check_groups(csel["tuples"], N, int(stage_words))
+            buf = eng.device_alloc(max(len(g[1]) for g in groups) * N * 8)
+            buffers.append(buf)
+            parts = []
+            for q0, rows, tuples in groups:
+                gsel = [csel["sel"][k] for k in rows]
+                eng.predict_eval(None, 1, iter0=seed_iter, sel=gsel, out=buf, loglik=False)
+                parts.append((q0, wp.checks(buf, [cp.observe_vtypes[k] for k in gsel], tuples)))
+            out.checks = WeightedPredictiveCheck.from_parts(csel["specs"], parts, N, u["T"])
         return out
     finally:
         if wp is not None:
@@ -844,19 +873,26 @@ def population_summary(eng, log_evidence: float = 0.0, betas=None, probs=(0.025,
 
 
 def adaptive_smc_summary(seed: int, num_particles: int, model_fn, config: Optional[SMCConfig] = None, device: int = 0,
-                         probs=(0.025, 0.25, 0.5, 0.75, 0.975), results: bool = False, predictive=False, discrete: bool = False) -> PopulationSummary:
+                         probs=(0.025, 0.25, 0.5, 0.75, 0.975), results: bool = False, predictive=False, discrete: bool = False, pointwise=False,
+                         checks=False) -> PopulationSummary:
     """`adaptive_smc` without the download: the same run (`smc_run(download=False)` leaves particles and weights in HBM), then the
     weighted summary of the final population on the device (`Engine.wpop`): per f64 site the weighted mean, std, Monte Carlo error
     and exact weighted quantiles at `probs`; `results=True` adds the rows of the model's return value at the final particles,
     `predictive=True | [addresses]` one replicate of the selected f64 observe sites per particle (stream (seed, particle, 0, 9), as
     `adaptive_smc` draws them), `discrete=True` the exact weighted frequency tables of the discrete sites (`PopulationSummary.tables`,
-    bins as `adaptive_mcmc_chain_summary` chooses them).  A population whose weights are not all in [0, 1] raises ValueError.
+    bins as `adaptive_mcmc_chain_summary` chooses them).  `pointwise=True | [addresses]` adds `PopulationSummary.comparison`, weighted
+    WAIC / IS-LOO per selected observe statement, and `checks=True | [CheckSpec]` adds `PopulationSummary.checks`, weighted predictive
+    checks of one replicate per particle (discrete observe sites included): log-likelihood and replicates are the bits
+    `adaptive_smc(predictive=True, pointwise=True)` stores, drawn slice by slice into one reused device buffer and reduced where they
+    lie (`WeightedPopulation.loglik` / `.checks`).  A population whose weights are not all in [0, 1] raises ValueError.
     `num_particles == 0` returns an empty summary with log_evidence 0.0 (smc.rs:462-467)."""
     cp = _compile(model_fn)
     cfg = config or SMCConfig()
     if num_particles == 0:
         _want_results(cp, results, who="adaptive_smc_summary")
         psel = _summary_predictive(cp, predictive, "adaptive_smc_summary")
+        _summary_pointwise(cp, pointwise, "adaptive_smc_summary")
+        _summary_checks(cp, checks, "adaptive_smc_summary")
         sites = [cp.site_names[j] for j in cp.f64_sites]
         rnames = list(cp.result_names) if results else []
         pnames = [cp.observe_names[k] for k in psel] if psel is not None else []
@@ -864,7 +900,7 @@ def adaptive_smc_summary(seed: int, num_particles: int, model_fn, config: Option
     eng = E.Engine(cp, num_particles, seed=seed, device=device)
     try:
         r = eng.smc_run(cfg.resampling_method, cfg.ess_threshold, cfg.rejuvenation_steps, download=False)
-        return population_summary(eng, r["log_evidence"], r["betas"], probs, results, predictive, discrete)
+        return population_summary(eng, r["log_evidence"], r["betas"], probs, results, predictive, discrete, pointwise=pointwise, checks=checks)
     finally:
         eng.close()
 

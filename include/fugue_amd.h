@@ -760,6 +760,39 @@ int  fg_wpop_quantiles(fg_wpop *h, const double *d_x, int d, const double *h_pro
  * not add up to T. */
 int  fg_wpop_counts(fg_wpop *h, const void *d_cells, int n_rows, const int32_t *h_vtypes, const int64_t *h_lo,
                     const int32_t *h_bins, uint64_t *h_units, uint64_t *h_below, uint64_t *h_above, int64_t *h_min, int64_t *h_max);
+/* Predictive checks and WAIC / IS-LOO of the population (tests/end_to_end_workflows.rs:330-400 compares models and :650-745 checks
+ * replicated data after every sampler, SMC included).  Rows [rows][n], particle-fastest, in device memory; nothing of size n goes to
+ * the host; engine state is neither read nor changed.
+ *   Checks: fg_ppc_stream's checks (CSR members, 5-bit masks, observed vectors, its statistics, cell conversion and slot numbering) of
+ *   ONE replicate per particle.  Per slot, FG_WPOP_CATS categories: T_rep < / == / > T_obs by IEEE compare (-0.0 == +0.0), or either
+ *   side NaN.  A particle adds its units to exactly one category and, with units above zero, 1 to that category's element count.
+ *   The p-values are quotients of unit sums: p_ge = (U_gt + U_eq) / (U_lt + U_eq + U_gt), p_gt, p_mid = (2 U_gt + U_eq) / (2 (...)).
+ *   The moments of T_rep are fg_wpop_moments' of a scratch table of the statistics.
+ *   Log-likelihood: a particle takes part in a row iff its weight is good and above zero.  h_counts: participating cells that are
+ *   finite, -inf, +inf, NaN.  h_words, FG_WLL_WORDS per row: W (the participating weights), W_fin, W2 = sum w^2, mean, ssd and n_used of
+ *   the finite participating cells (the leaves of fg_wpop_moments), mx, mn (their exact max and min), sp = sum w exp(x - mx),
+ *   sn = sum w exp(mn - x), sn2 = sum (w exp(mn - x))^2, tmax = the largest term of sn; every sum over the fixed tree on the
+ *   particle index.  h_figures in fg_loglik_stream's order: lppd = mx + ln(sp / W), mean_ll, p_waic = ssd / (W_fin - W2 / W_fin)
+ *   (reliability weights: the divisor N - 1 at equal weights; NaN when n_used < 2), elpd_waic, elpd_loo = mn - ln(sn / W), p_loo,
+ *   is_ess = sn^2 / sn2 (Kish, in particles), max_weight = tmax / sn.  A NaN cell makes every figure NaN; a -inf cell is zero mass
+ *   in lppd and makes elpd_loo -inf, is_ess and max_weight NaN; a +inf cell makes lppd +inf; both count in W; a row without a finite
+ *   participating cell has NaN figures and its counters. */
+#define FG_WPOP_CATS 4
+#define FG_WLL_FIGURES 8
+#define FG_WLL_WORDS 12
+#define FG_WLL_COUNTS 4
+/* abc.rs:476 / smc.rs:445-453, end_to_end_workflows.rs:650-745: the slots the masks ask for (at most 65535), or FG_E_BAD_ARG */
+int  fg_wpop_checks_n_slots(int n_checks, const int32_t *h_stat_mask);
+/* abc.rs:476 / smc.rs:445-453, end_to_end_workflows.rs:650-745: d_yrep [n_rows][n] raw cells; the check arguments of
+ * fg_ppc_stream_new.  h_t_obs [n_slots], h_units [n_slots][FG_WPOP_CATS], h_counts [n_slots][FG_WPOP_CATS] (lt, eq, gt, nan),
+ * h_moments [n_slots][FG_WPOP_MOMENTS].  FG_E_BAD_ARG: fg_ppc_stream_new's, n_rows or n_slots outside [1, 65535].  FG_E_STATE: a slot
+ * whose units do not add up to T. */
+int  fg_wpop_checks(fg_wpop *h, const void *d_yrep, int n_rows, const int32_t *h_vtypes, int n_checks, const int32_t *h_offsets,
+                    const int32_t *h_members, const int32_t *h_stat_mask, const double *h_observed, double *h_t_obs, uint64_t *h_units,
+                    int64_t *h_counts, double *h_moments);
+/* abc.rs:476 / smc.rs:445-453, end_to_end_workflows.rs:330-400: d_ll [n_sel][n] doubles; h_figures [FG_WLL_FIGURES][n_sel], h_words
+ * [n_sel][FG_WLL_WORDS], h_counts [n_sel][FG_WLL_COUNTS] (h_words and h_counts may be NULL).  FG_E_BAD_ARG: n_sel outside [1, 65535]. */
+int  fg_wpop_loglik(fg_wpop *h, const double *d_ll, int n_sel, double *h_figures, double *h_words, int64_t *h_counts);
 void fg_wpop_free(fg_wpop *h);                                 /* abc.rs:476 / smc.rs:445-453 */
 /* ------------------------------------------------------------------ bootstrap particle filter bank
  * WasmParticleFilter (crates/fugue-wasm/src/pf.rs): a 1-D bootstrap filter on the random-walk model x_0 ~ N(0, prior_sig),

@@ -233,6 +233,12 @@ extern "C" {
                              h_out: *mut f64, h_passes: *mut i32) -> c_int;
     pub fn fg_wpop_counts(h: *mut fg_wpop, d_cells: *const c_void, n_rows: c_int, h_vtypes: *const i32, h_lo: *const i64, h_bins: *const i32,
                           h_units: *mut u64, h_below: *mut u64, h_above: *mut u64, h_min: *mut i64, h_max: *mut i64) -> c_int;
+    // predictive checks and WAIC / IS-LOO of the population (fg_wpop_eval.hip): tests/end_to_end_workflows.rs:330-400, :650-745
+    pub fn fg_wpop_checks_n_slots(n_checks: c_int, h_stat_mask: *const i32) -> c_int;
+    pub fn fg_wpop_checks(h: *mut fg_wpop, d_yrep: *const c_void, n_rows: c_int, h_vtypes: *const i32, n_checks: c_int, h_offsets: *const i32,
+                          h_members: *const i32, h_stat_mask: *const i32, h_observed: *const f64, h_t_obs: *mut f64, h_units: *mut u64,
+                          h_counts: *mut i64, h_moments: *mut f64) -> c_int;
+    pub fn fg_wpop_loglik(h: *mut fg_wpop, d_ll: *const f64, n_sel: c_int, h_figures: *mut f64, h_words: *mut f64, h_counts: *mut i64) -> c_int;
     pub fn fg_wpop_free(h: *mut fg_wpop);
     // ---- bootstrap particle filter bank (fg_pf.hip): crates/fugue-wasm/src/pf.rs, B filters at once
     pub fn fg_pf_new(device_ordinal: c_int, n_particles: i64, n_filters: i64, params: *const fg_pf_params, out: *mut *mut fg_pf) -> c_int;
