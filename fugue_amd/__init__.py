@@ -13,7 +13,7 @@ from .inference import (ChainBatch, ChainSummary, HMCConfig, PopulationSummary, 
                         adaptive_smc, adaptive_smc_summary, hmc_chain, hmc_chain_summary, population_summary, prior_predictive)
 from .diagnostics import (ParameterSummary, StreamMoments, classic_r_hat_f64, effective_sample_size, effective_sample_size_multichain,  # noqa: F401
                           geweke_diagnostic, r_hat_f64, summarize_f64_parameter)
-from .comparison import PointwiseComparison, WeightedComparison, compare_models, model_comparison, weighted_model_comparison  # noqa: F401
+from .comparison import PointwiseComparison, PsisLoo, WeightedComparison, compare_models, model_comparison, psis_loo, weighted_model_comparison  # noqa: F401
 from .checks import CheckSpec, PredictiveCheck, WeightedPredictiveCheck, marginal_checks, posterior_predictive_check, weighted_predictive_check  # noqa: F401
 from .validation import effective_sample_size_mcmc  # noqa: F401
 from .abc import (ABC_SMC_DEFAULT_ATTEMPT_FACTOR, ABCError, ABCSMCConfig, ABCSMCResult, EuclideanDistance, ManhattanDistance,  # noqa: F401

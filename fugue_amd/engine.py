@@ -75,6 +75,12 @@ TOK = {"const": 0, "site": 1, "data": 2, "neg": 3, "exp": 4, "ln": 5, "sqrt": 6,
 GRAD_FD_DENSE, GRAD_FD_SPARSE, GRAD_ANALYTIC = 0, 1, 2
 # engine error codes (include/fugue_amd.h)
 FG_E_NO_DEVICE, FG_E_HIP, FG_E_BAD_ARG, FG_E_NOT_FINALIZED, FG_E_STATE, FG_E_UNSUPPORTED, FG_E_LIMIT = -1, -2, -3, -4, -5, -6, -7
+# fg_psis_loo's rows (include/fugue_amd.h): FG_PSIS_WORDS doubles and FG_PSIS_COUNTS integers per statement, the status words
+PSIS_WORD_NAMES = ("elpd_loo_psis", "p_loo_psis", "khat", "sigma", "khat_threshold", "lppd", "x_min", "x_cut", "exp_cutoff", "t_star", "theta_hat",
+                   "body_sum", "tail_sum", "tail_num")
+PSIS_COUNT_NAMES = ("tail_len", "status", "n_capped", "n_fin", "n_neg_inf", "n_pos_inf", "n_nan", "n_below", "n_equal", "n_collected")
+PSIS_COUNTS = len(PSIS_COUNT_NAMES)
+PSIS_STATUS = ("fitted", "too few draws", "degenerate tail", "non-finite cells")
 
 # every symbol include/fugue_amd.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -106,6 +112,7 @@ ABI_SYMBOLS = [
     "fg_ppc_stream_new", "fg_ppc_stream_update", "fg_ppc_stream_count", "fg_ppc_stream_n_slots", "fg_ppc_stream_observed", "fg_ppc_stream_pooled",
     "fg_ppc_stream_chains", "fg_ppc_stream_free", "fg_program_observe_value",
     "fg_wpop_new", "fg_wpop_units", "fg_wpop_moments", "fg_wpop_quantiles", "fg_wpop_counts", "fg_wpop_free", "fg_wpop_checks_n_slots", "fg_wpop_checks", "fg_wpop_loglik",
+    "fg_psis_words", "fg_psis_tail_len", "fg_psis_loo",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -301,6 +308,10 @@ def lib():
     L.fg_wpop_loglik.argtypes = [vp, vp, C.c_int, dp, dp, i64p]
     L.fg_wpop_free.restype = None
     L.fg_wpop_free.argtypes = [vp]
+    L.fg_psis_words.argtypes = []
+    L.fg_psis_tail_len.restype = C.c_int64
+    L.fg_psis_tail_len.argtypes = [C.c_int64]
+    L.fg_psis_loo.argtypes = [vp, vp, C.c_int, C.c_int, dp, i64p, vp]
     L.fg_pf_new.argtypes = [C.c_int, C.c_int64, C.c_int64, C.POINTER(fg_pf_params), C.POINTER(vp)]
     L.fg_pf_set_sig_obs.argtypes = [vp, C.c_int64, C.c_double]
     L.fg_pf_run.argtypes = [vp, dp, C.c_int64, C.c_int, dp, dp, ip, dp, dp]
@@ -943,6 +954,33 @@ class Engine:
         """A `fg_loglik_stream`: WAIC and importance-sampling LOO of `n_sel` observe statements from chunks [n_chunk][n_sel][C] of the
         pointwise log-likelihood (`predict_eval`'s `loglik` table) of a run of `n_total` draws that is never stored."""
         return LoglikStream(self, n_total, n_sel)
+
+    def psis_loo(self, d_ll: int, n: int, n_sel: int, tail: bool = False) -> dict:
+        """`fg_psis_loo` (fg_psis.hip): Pareto-smoothed LOO and k-hat per observe statement of the stored table `d_ll` [n][n_sel][C] on
+        the device (C this engine's chains).  -> the figures by name (PSIS_WORD_NAMES, [n_sel] doubles each), the counts by name
+        (PSIS_COUNT_NAMES, [n_sel] int64 each), `words` [n_sel][14], `counts` [n_sel][10]; with `tail` also `tail` [n_sel][M], the sorted
+        M smallest cells of every statement.  Reads engine state and changes none."""
+        for name, v in (("n", n), ("n_sel", n_sel)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"psis_loo: {name} must be an integer, not {type(v).__name__}")
+        L = lib()
+        nw = int(L.fg_psis_words())
+        n_sel_buf = max(int(n_sel), 1)
+        words = np.zeros((n_sel_buf, nw), dtype=np.float64)
+        counts = np.zeros((n_sel_buf, PSIS_COUNTS), dtype=np.int64)
+        M = int(L.fg_psis_tail_len(int(n) * self.C)) if n >= 1 else 0
+        d_tail = self.device_alloc(8 * n_sel_buf * M) if tail and M > 0 else None
+        try:
+            _check(L.fg_psis_loo(self.h, d_ll, int(n), int(n_sel), _dp(words), counts.ctypes.data_as(C.POINTER(C.c_int64)), d_tail))
+            out = {name: words[:, j].copy() for j, name in enumerate(PSIS_WORD_NAMES)}
+            out.update({name: counts[:, j].copy() for j, name in enumerate(PSIS_COUNT_NAMES)})
+            out["words"], out["counts"] = words, counts
+            if d_tail is not None:
+                out["tail"] = self.download(d_tail, (int(n_sel), M))
+            return out
+        finally:
+            if d_tail is not None:
+                self.device_free(d_tail)
 
     def ppc_stream(self, n_total: int, vtypes: Sequence[int], checks: Sequence) -> "PpcStream":
         """A `fg_ppc_stream`: posterior predictive checks from chunks [n_chunk][len(vtypes)][C] of replicated data (`predict_eval`'s cell

@@ -794,6 +794,33 @@ int  fg_wpop_checks(fg_wpop *h, const void *d_yrep, int n_rows, const int32_t *h
  * [n_sel][FG_WLL_WORDS], h_counts [n_sel][FG_WLL_COUNTS] (h_words and h_counts may be NULL).  FG_E_BAD_ARG: n_sel outside [1, 65535]. */
 int  fg_wpop_loglik(fg_wpop *h, const double *d_ll, int n_sel, double *h_figures, double *h_words, int64_t *h_counts);
 void fg_wpop_free(fg_wpop *h);                                 /* abc.rs:476 / smc.rs:445-453 */
+/* ------------------------------------------------------------------ Pareto-smoothed LOO of a stored log-likelihood table
+ * PSIS-LOO and k-hat per observe statement (Vehtari, Simpson, Gelman, Yao, Gabry; the generalised Pareto fit of Zhang and Stephens
+ * 2009 with the weakly informative prior, as the R `loo` package's psis / gpdfit; r_eff = 1; the reference has none of it) from a
+ * table d_ll [n][n_sel][C] that lies on the device (C the engine's chains): what fg_predict_eval writes and fg_loglik_stream_update
+ * takes.  Nothing is replayed.  Per statement over its S = n C pooled cells x: lw = x_min - x; the tail is the M = min(ceil(S / 5),
+ * ceil(3 sqrt S)) smallest x, the cutoff the (M + 1)-th smallest; the fit runs over t_j = exp(lw_(j)) - exp(lw_cut) in ascending
+ * order; the smoothed tail replaces the M largest ratios, capped at the largest raw one.  The rule, the fixed summation orders and the
+ * limits: fg_psis_plan.h and DESIGN 3.22.  A row of FG_PSIS_WORDS doubles per statement:
+ *   0 elpd_loo_psis  1 p_loo_psis = lppd - elpd_loo_psis  2 khat  3 sigma  4 khat_threshold = min(1 - 1 / log10 S, 0.7)  5 lppd
+ *   6 x_min  7 the cutoff x  8 exp(lw_cut)  9 t*  10 theta-hat  11 the body's sum of ratios  12 the tail's  13 the tail's numerator
+ * and a row of FG_PSIS_COUNTS integers:
+ *   0 tail_len = M  1 status (FG_PSIS_*)  2 n_capped  3 finite cells  4 -inf cells  5 +inf cells  6 NaN cells
+ *   7 cells below the cutoff key  8 cells on it  9 cells collected (= word 7, or FG_E_STATE)
+ * Without a fit (M < 5, a degenerate tail: t* <= 0) khat = +inf and elpd_loo_psis is the raw importance-sampling value by the same
+ * formula.  A NaN cell makes every figure of its statement NaN; a -inf cell gives elpd_loo_psis = -inf and khat = +inf; +inf cells
+ * have ratio 0 and lie in the body (a +inf cell that reaches the cutoff: no fit, status FG_PSIS_NONFINITE). */
+#define FG_PSIS_WORDS 14
+#define FG_PSIS_COUNTS 10
+enum { FG_PSIS_FITTED = 0, FG_PSIS_TOO_FEW = 1, FG_PSIS_DEGENERATE = 2, FG_PSIS_NONFINITE = 3 };
+int     fg_psis_words(void);                                   /* FG_PSIS_WORDS of this library */
+/* M for S pooled draws; FG_E_BAD_ARG for S < 1, FG_E_LIMIT for S >= 2^31.  No device. */
+int64_t fg_psis_tail_len(int64_t S);
+/* h_figures [n_sel][FG_PSIS_WORDS], h_counts [n_sel][FG_PSIS_COUNTS]; d_tail_or_null, if given, receives the sorted raw tails
+ * [n_sel][M] (ascending in the order of fg_diag_quantiles' keys: -0.0 below +0.0).  Every argument is checked before the device is
+ * looked for.  FG_E_BAD_ARG: a null pointer, n < 1, n_sel < 1; FG_E_LIMIT: n C >= 2^31; FG_E_STATE: a statement whose collected
+ * cells differ from the select's count (never a figure).  Synchronous; reads engine state and changes none. */
+int     fg_psis_loo(fg_engine *e, const double *d_ll, int n, int n_sel, double *h_figures, int64_t *h_counts, double *d_tail_or_null);
 /* ------------------------------------------------------------------ bootstrap particle filter bank
  * WasmParticleFilter (crates/fugue-wasm/src/pf.rs): a 1-D bootstrap filter on the random-walk model x_0 ~ N(0, prior_sig),
  * x_t = x_{t-1} + N(0, sig_step), y_t ~ N(x_t, sig_obs), systematic resampling when ESS / n < ess_threshold, the running log-evidence.

@@ -240,6 +240,10 @@ extern "C" {
                           h_counts: *mut i64, h_moments: *mut f64) -> c_int;
     pub fn fg_wpop_loglik(h: *mut fg_wpop, d_ll: *const f64, n_sel: c_int, h_figures: *mut f64, h_words: *mut f64, h_counts: *mut i64) -> c_int;
     pub fn fg_wpop_free(h: *mut fg_wpop);
+    // ---- Pareto-smoothed LOO and k-hat of a stored log-likelihood table (fg_psis.hip)
+    pub fn fg_psis_words() -> c_int;
+    pub fn fg_psis_tail_len(S: i64) -> i64;
+    pub fn fg_psis_loo(e: *mut fg_engine, d_ll: *const f64, n: c_int, n_sel: c_int, h_figures: *mut f64, h_counts: *mut i64, d_tail_or_null: *mut f64) -> c_int;
     // ---- bootstrap particle filter bank (fg_pf.hip): crates/fugue-wasm/src/pf.rs, B filters at once
     pub fn fg_pf_new(device_ordinal: c_int, n_particles: i64, n_filters: i64, params: *const fg_pf_params, out: *mut *mut fg_pf) -> c_int;
     pub fn fg_pf_set_sig_obs(pf: *mut fg_pf, filter: i64, sig_obs: f64) -> c_int;
