@@ -11,8 +11,9 @@ from .model import (Bernoulli, Beta, Binomial, Categorical, Cauchy, ChiSquared, 
 from .inference import (ChainBatch, ChainSummary, HMCConfig, PopulationSummary, PriorPredictive, ResamplingMethod, SMCConfig, SMCResult,  # noqa: F401
                         SiteProposal, WeightedTables, adaptive_mcmc_chain, adaptive_mcmc_chain_summary, adaptive_mcmc_chain_with_overrides,
                         adaptive_smc, adaptive_smc_summary, hmc_chain, hmc_chain_summary, population_summary, prior_predictive)
-from .diagnostics import (ParameterSummary, StreamMoments, classic_r_hat_f64, effective_sample_size, effective_sample_size_multichain,  # noqa: F401
-                          geweke_diagnostic, r_hat_f64, summarize_f64_parameter)
+from .diagnostics import (ParameterSummary, RankDiagnostics, StreamMoments, classic_r_hat_f64, effective_sample_size,  # noqa: F401
+                          effective_sample_size_multichain, ess_bulk, ess_tail, geweke_diagnostic, r_hat_f64, rank_diagnostics, rank_r_hat_f64,
+                          summarize_f64_parameter)
 from .comparison import PointwiseComparison, PsisLoo, WeightedComparison, compare_models, model_comparison, psis_loo, weighted_model_comparison  # noqa: F401
 from .checks import CheckSpec, PredictiveCheck, WeightedPredictiveCheck, marginal_checks, posterior_predictive_check, weighted_predictive_check  # noqa: F401
 from .validation import effective_sample_size_mcmc  # noqa: F401

@@ -321,3 +321,93 @@ def effective_sample_size(particles) -> float:
     """effective_sample_size (smc.rs:230-233) of a weighted population (SMCResult): 1 / sum w_i^2."""
     w = np.asarray(particles.weights, dtype=np.float64)
     return float(1.0 / (w * w).sum()) if w.size else 0.0
+
+
+# ---- rank-normalised split R-hat, bulk and tail ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; fg_diag_rank.hip, DESIGN 3.23) ----
+RANK_FIGURES = ("rhat_rank", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_lower", "ess_upper", "median", "x_lo", "x_hi")
+
+
+@dataclass
+class RankDiagnostics:
+    """The rank-normalised figures of `d` coordinates, one array entry per coordinate: `rhat_rank` = max(`rhat_bulk`, `rhat_folded`),
+    `ess_bulk`, `ess_tail` = min(`ess_lower`, `ess_upper`), the `median` and the order statistics `x_lo` / `x_hi` the tail indicators
+    cut at; `counts` by name (engine.RANK_COUNT_NAMES).  The ESS is the project's estimator (the reference's Geyer sequence over whole
+    chains) applied to the rank-normalised draws, not `posterior`'s split-chain estimate."""
+    names: list
+    n_draws: int
+    rhat_rank: np.ndarray
+    rhat_bulk: np.ndarray
+    rhat_folded: np.ndarray
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray
+    ess_lower: np.ndarray
+    ess_upper: np.ndarray
+    median: np.ndarray
+    x_lo: np.ndarray
+    x_hi: np.ndarray
+    counts: dict
+
+    @property
+    def d(self) -> int:
+        return len(self.names)
+
+    def of(self, name: str) -> dict:
+        """the ten figures of one coordinate"""
+        if name not in self.names:
+            raise KeyError(name)
+        k = self.names.index(name)
+        return {f: float(getattr(self, f)[k]) for f in RANK_FIGURES}
+
+    @classmethod
+    def from_result(cls, names, n_draws: int, res: dict) -> "RankDiagnostics":
+        from . import engine as E
+        return cls(names=list(names), n_draws=int(n_draws), counts={k: np.asarray(res[k]) for k in E.RANK_COUNT_NAMES}, **{f: np.asarray(res[f]) for f in RANK_FIGURES})
+
+
+def _rank_table(x, addresses):
+    """a ChainBatch (its f64 sites, or the named ones) or an array [n][d][C] -> the table and the coordinates' names"""
+    if hasattr(x, "get_f64") and hasattr(x, "sites"):
+        names = [a for a, v in zip(x.sites, x.vtypes) if v == 0] if addresses is None else [str(a) for a in addresses]
+        if not names:
+            raise ValueError("rank_diagnostics: the ChainBatch has no f64 site")
+        return np.ascontiguousarray(np.stack([np.asarray(x.get_f64(a)) for a in names], axis=1), dtype=np.float64), names
+    table = np.ascontiguousarray(x, dtype=np.float64)
+    if table.ndim != 3 or min(table.shape) < 1:
+        raise ValueError(f"rank_diagnostics: the draws must be [n][d][C] with every extent at least 1, not {table.shape}")
+    names = [f"x[{j}]" for j in range(table.shape[1])] if addresses is None else [str(a) for a in addresses]
+    if len(names) != table.shape[1]:
+        raise ValueError(f"rank_diagnostics: {len(names)} names for {table.shape[1]} coordinates")
+    return table, names
+
+
+def rank_diagnostics(x, addresses=None, probs=(0.05, 0.95), device: int = 0) -> RankDiagnostics:
+    """Rank-normalised split R-hat, folded R-hat, bulk and tail ESS of stored draws: `x` is a `ChainBatch` (its f64 sites, or the sites
+    `addresses`) or an array [n][d][C].  The draws are uploaded and `Engine.diag_rank` runs on them on a throw-away engine; n x C must
+    stay below 2^31."""
+    from . import engine as E, workloads as W
+    table, names = _rank_table(x, addresses)
+    n, d, C_ = table.shape
+    eng = E.Engine(E.compile_model(W.normal_sites(1)), C_, seed=0, device=device)        # the call wants the engine's chain count only
+    buf = None
+    try:
+        buf = eng.upload(table)
+        return RankDiagnostics.from_result(names, n * C_, eng.diag_rank(buf, n, d, probs=probs))
+    finally:
+        if buf is not None:
+            eng.device_free(buf)
+        eng.close()
+
+
+def rank_r_hat_f64(chains, address: str) -> float:
+    """`rhat_rank` of one f64 site of a ChainBatch: the larger of the rank-normalised and the folded split R-hat."""
+    return float(rank_diagnostics(chains, [address]).rhat_rank[0])
+
+
+def ess_bulk(chains, address: str) -> float:
+    """Bulk ESS of one f64 site of a ChainBatch: the multi-chain ESS of its rank-normalised draws."""
+    return float(rank_diagnostics(chains, [address]).ess_bulk[0])
+
+
+def ess_tail(chains, address: str) -> float:
+    """Tail ESS of one f64 site of a ChainBatch: the smaller ESS of the 5 % and 95 % tail indicators."""
+    return float(rank_diagnostics(chains, [address]).ess_tail[0])

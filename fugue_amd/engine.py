@@ -81,6 +81,11 @@ PSIS_WORD_NAMES = ("elpd_loo_psis", "p_loo_psis", "khat", "sigma", "khat_thresho
 PSIS_COUNT_NAMES = ("tail_len", "status", "n_capped", "n_fin", "n_neg_inf", "n_pos_inf", "n_nan", "n_below", "n_equal", "n_collected")
 PSIS_COUNTS = len(PSIS_COUNT_NAMES)
 PSIS_STATUS = ("fitted", "too few draws", "degenerate tail", "non-finite cells")
+# fg_diag_rank_rhat_ess's rows (include/fugue_amd.h): FG_RANK_WORDS doubles and FG_RANK_COUNTS integers per coordinate; fg_diag_rank_transform's rows
+RANK_WORD_NAMES = ("rhat_rank", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_lower", "ess_upper", "median", "x_lo", "x_hi")
+RANK_COUNT_NAMES = ("n_cells", "n_runs", "longest_run", "n_nan", "n_neg_inf", "n_pos_inf", "n_nan_folded", "n_passes")
+RANK_COUNTS = len(RANK_COUNT_NAMES)
+RANK_ROWS = 4
 
 # every symbol include/fugue_amd.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -113,6 +118,7 @@ ABI_SYMBOLS = [
     "fg_ppc_stream_chains", "fg_ppc_stream_free", "fg_program_observe_value",
     "fg_wpop_new", "fg_wpop_units", "fg_wpop_moments", "fg_wpop_quantiles", "fg_wpop_counts", "fg_wpop_free", "fg_wpop_checks_n_slots", "fg_wpop_checks", "fg_wpop_loglik",
     "fg_psis_words", "fg_psis_tail_len", "fg_psis_loo",
+    "fg_diag_rank_words", "fg_diag_rank_transform", "fg_diag_rank_rhat_ess",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -312,6 +318,9 @@ def lib():
     L.fg_psis_tail_len.restype = C.c_int64
     L.fg_psis_tail_len.argtypes = [C.c_int64]
     L.fg_psis_loo.argtypes = [vp, vp, C.c_int, C.c_int, dp, i64p, vp]
+    L.fg_diag_rank_words.argtypes = []
+    L.fg_diag_rank_transform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, dp, i64p]
+    L.fg_diag_rank_rhat_ess.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int64, dp, i64p]
     L.fg_pf_new.argtypes = [C.c_int, C.c_int64, C.c_int64, C.POINTER(fg_pf_params), C.POINTER(vp)]
     L.fg_pf_set_sig_obs.argtypes = [vp, C.c_int64, C.c_double]
     L.fg_pf_run.argtypes = [vp, dp, C.c_int64, C.c_int, dp, dp, ip, dp, dp]
@@ -981,6 +990,55 @@ class Engine:
         finally:
             if d_tail is not None:
                 self.device_free(d_tail)
+
+    def diag_rank_transform(self, d_draws: int, n: int, d: int, j0: int = 0, n_j: Optional[int] = None, probs=(0.05, 0.95), d_out: Optional[int] = None,
+                            rank2: bool = False) -> dict:
+        """`fg_diag_rank_transform` (fg_diag_rank.hip): the rank-normalised rows of coordinates [j0, j0 + n_j) of the stored draws
+        `d_draws` [n][d][C] on the device.  -> `out` [n][4 n_j][C] (rows z, z_folded, I_lo, I_hi per coordinate; downloaded, or None when
+        the caller's device buffer `d_out` received them), `median` [n_j], `counts` [n_j][8] and the counts by name (RANK_COUNT_NAMES);
+        with `rank2` also `rank2` [n][n_j][C], the doubled average ranks (uint32).  Reads engine state and changes none."""
+        n_j = int(d) - int(j0) if n_j is None else n_j
+        for name, v in (("n", n), ("d", d), ("j0", j0), ("n_j", n_j)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"diag_rank_transform: {name} must be an integer, not {type(v).__name__}")
+        p_lo, p_hi = (float(p) for p in probs)
+        nb = max(int(n_j), 1)
+        cells = max(int(n), 1) * nb * self.C
+        median = np.zeros(nb)
+        counts = np.zeros((nb, RANK_COUNTS), dtype=np.int64)
+        own = self.device_alloc(8 * RANK_ROWS * cells) if d_out is None else None
+        d_r2 = self.device_alloc(4 * cells) if rank2 else None
+        try:
+            _check(lib().fg_diag_rank_transform(self.h, d_draws, int(n), int(d), int(j0), int(n_j), p_lo, p_hi, own if d_out is None else d_out, d_r2, _dp(median),
+                                                counts.ctypes.data_as(C.POINTER(C.c_int64))))
+            out = {name: counts[:, j].copy() for j, name in enumerate(RANK_COUNT_NAMES)}
+            out.update(out=self.download(own, (int(n), RANK_ROWS * int(n_j), self.C)) if own is not None else None, median=median, counts=counts)
+            if d_r2 is not None:
+                out["rank2"] = self.download(d_r2, (int(n), int(n_j), self.C), dtype=np.uint32)
+            return out
+        finally:
+            for b in (own, d_r2):
+                if b is not None:
+                    self.device_free(b)
+
+    def diag_rank(self, d_draws: int, n: int, d: int, probs=(0.05, 0.95), max_out_bytes: int = 0) -> dict:
+        """`fg_diag_rank_rhat_ess` (fg_diag_rank.hip): rank-normalised split R-hat, folded R-hat, bulk and tail ESS of every coordinate of
+        the stored draws `d_draws` [n][d][C] on the device (C this engine's chains).  -> the figures by name (RANK_WORD_NAMES, [d] doubles
+        each), the counts by name (RANK_COUNT_NAMES, [d] int64 each), `words` [d][10], `counts` [d][8].  `max_out_bytes` bounds the
+        transformed rows held at a time (0: 1 GiB); the figures do not depend on it.  Reads engine state and changes none."""
+        for name, v in (("n", n), ("d", d), ("max_out_bytes", max_out_bytes)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"diag_rank: {name} must be an integer, not {type(v).__name__}")
+        p_lo, p_hi = (float(p) for p in probs)
+        L = lib()
+        db = max(int(d), 1)
+        words = np.zeros((db, int(L.fg_diag_rank_words())), dtype=np.float64)
+        counts = np.zeros((db, RANK_COUNTS), dtype=np.int64)
+        _check(L.fg_diag_rank_rhat_ess(self.h, d_draws, int(n), int(d), p_lo, p_hi, int(max_out_bytes), _dp(words), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        out = {name: words[:, j].copy() for j, name in enumerate(RANK_WORD_NAMES)}
+        out.update({name: counts[:, j].copy() for j, name in enumerate(RANK_COUNT_NAMES)})
+        out["words"], out["counts"] = words, counts
+        return out
 
     def ppc_stream(self, n_total: int, vtypes: Sequence[int], checks: Sequence) -> "PpcStream":
         """A `fg_ppc_stream`: posterior predictive checks from chunks [n_chunk][len(vtypes)][C] of replicated data (`predict_eval`'s cell

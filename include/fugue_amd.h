@@ -821,6 +821,41 @@ int64_t fg_psis_tail_len(int64_t S);
  * looked for.  FG_E_BAD_ARG: a null pointer, n < 1, n_sel < 1; FG_E_LIMIT: n C >= 2^31; FG_E_STATE: a statement whose collected
  * cells differ from the select's count (never a figure).  Synchronous; reads engine state and changes none. */
 int     fg_psis_loo(fg_engine *e, const double *d_ll, int n, int n_sel, double *h_figures, int64_t *h_counts, double *d_tail_or_null);
+/* ------------------------------------------------------------------ rank-normalised R-hat and bulk / tail ESS
+ * Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021), "Rank-normalization, folding, and localization: an improved R-hat for
+ * assessing convergence of MCMC" -- what the R `posterior` package and Stan report; the reference has none of it -- of stored draws
+ * d_draws [n][d][C] on the device (fg_diag_rank.hip; the rule, the sort and the limits: fg_diag_rank_plan.h and DESIGN 3.23).  Per
+ * coordinate the S = n C pooled cells are sorted exactly (a stable radix sort of key and cell index; ties are ties of values: -0.0
+ * and +0.0 tie, all NaN tie above +inf); a cell's doubled average rank r2 = lo + hi + 1 gives its normal score
+ * z = ndtri((r2 / 2 - 3/8) / (S + 1/4)) (AS241 PPND16), the folded cells |x - median| are sorted again for z_folded, and
+ * I_lo / I_hi = 1 where x <= sorted[floor((S - 1) p)].  The figures are the library's own combination -- r_hat_from_f64_chains
+ * (diagnostics.rs:262-304) and ess_from_chains (mcmc_utils.rs:253-339), the code behind fg_diag_rhat_ess -- applied to those rows in
+ * the original [n][.][C] layout: same transform as `posterior`, the project's own ESS estimator (no split chains, Geyer's sequence as
+ * the reference truncates it).  A row of FG_RANK_WORDS doubles per coordinate:
+ *   0 rhat_rank = max(1, 2)  1 rhat_bulk (of z)  2 rhat_folded (of z_folded)  3 ess_bulk (of z)  4 ess_tail = min(5, 6)
+ *   5 ess_lower (of I_lo)  6 ess_upper (of I_hi)  7 median  8 x_lo = sorted[k_lo]  9 x_hi = sorted[k_hi]
+ * and a row of FG_RANK_COUNTS integers:
+ *   0 S  1 tie runs (distinct values)  2 the longest run  3 NaN cells  4 -inf cells  5 +inf cells  6 NaN folded cells
+ *   7 radix passes run, both sorts together (a pass whose digit is equal in every cell is skipped)
+ * +-inf cells are ordinary values.  A NaN cell makes every figure of its coordinate NaN; NaN folded cells (median = +-inf) make
+ * rhat_folded and rhat_rank NaN only.  This engine's chains only, no communicator: ranks over the chains of several GPUs need a
+ * distributed sort.  Both calls are synchronous, read engine state and change none; every argument is checked before the device is
+ * looked for.  FG_E_BAD_ARG: a null pointer, n < 1, d outside [1, 65535], a block outside [0, d), a probability outside [0, 1],
+ * p_lo > p_hi, max_out_bytes < 0; FG_E_LIMIT: n C >= 2^31. */
+#define FG_RANK_ROWS 4      /* z, z_folded, I_lo, I_hi */
+#define FG_RANK_WORDS 10    /* rhat_rank rhat_bulk rhat_folded ess_bulk ess_tail ess_lower ess_upper median x_lo x_hi */
+#define FG_RANK_COUNTS 8    /* S, tie runs, longest run, NaN, -inf, +inf cells, NaN folded cells, radix passes run (both sorts) */
+int     fg_diag_rank_words(void);                              /* FG_RANK_WORDS of this library */
+/* The transform alone (Vehtari et al. 2021, section 4): coordinates [j0, j0 + n_j) of d_draws [n][d][C] -> d_out
+ * [n][FG_RANK_ROWS n_j][C] (row 4 k + i: row i of coordinate j0 + k), ready for fg_diag_rhat_ess (diagnostics.rs:262-304,
+ * mcmc_utils.rs:253-339); d_rank2_or_null [n][n_j][C] u32 doubled average ranks; h_median [n_j]; h_counts [n_j][FG_RANK_COUNTS]. */
+int     fg_diag_rank_transform(fg_engine *e, const double *d_draws, int n, int d, int j0, int n_j, double p_lo, double p_hi,
+                               double *d_out, uint32_t *d_rank2_or_null, double *h_median, int64_t *h_counts);
+/* The transform block by block (a block: the coordinates whose d_out stays under max_out_bytes, at least one; 0 = 1 GiB), then the
+ * combination of fg_diag_rhat_ess (r_hat_from_f64_chains, diagnostics.rs:262-304; ess_from_chains, mcmc_utils.rs:253-339) on each
+ * block; h_figures [d][FG_RANK_WORDS], h_counts [d][FG_RANK_COUNTS].  The figures do not depend on the blocks. */
+int     fg_diag_rank_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, double p_lo, double p_hi, int64_t max_out_bytes,
+                              double *h_figures, int64_t *h_counts);
 /* ------------------------------------------------------------------ bootstrap particle filter bank
  * WasmParticleFilter (crates/fugue-wasm/src/pf.rs): a 1-D bootstrap filter on the random-walk model x_0 ~ N(0, prior_sig),
  * x_t = x_{t-1} + N(0, sig_step), y_t ~ N(x_t, sig_obs), systematic resampling when ESS / n < ess_threshold, the running log-evidence.

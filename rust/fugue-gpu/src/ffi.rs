@@ -244,6 +244,12 @@ extern "C" {
     pub fn fg_psis_words() -> c_int;
     pub fn fg_psis_tail_len(S: i64) -> i64;
     pub fn fg_psis_loo(e: *mut fg_engine, d_ll: *const f64, n: c_int, n_sel: c_int, h_figures: *mut f64, h_counts: *mut i64, d_tail_or_null: *mut f64) -> c_int;
+    // ---- rank-normalised R-hat, bulk / tail ESS of stored draws (fg_diag_rank.hip)
+    pub fn fg_diag_rank_words() -> c_int;
+    pub fn fg_diag_rank_transform(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, j0: c_int, n_j: c_int, p_lo: f64, p_hi: f64,
+                                  d_out: *mut f64, d_rank2_or_null: *mut u32, h_median: *mut f64, h_counts: *mut i64) -> c_int;
+    pub fn fg_diag_rank_rhat_ess(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, p_lo: f64, p_hi: f64, max_out_bytes: i64,
+                                 h_figures: *mut f64, h_counts: *mut i64) -> c_int;
     // ---- bootstrap particle filter bank (fg_pf.hip): crates/fugue-wasm/src/pf.rs, B filters at once
     pub fn fg_pf_new(device_ordinal: c_int, n_particles: i64, n_filters: i64, params: *const fg_pf_params, out: *mut *mut fg_pf) -> c_int;
     pub fn fg_pf_set_sig_obs(pf: *mut fg_pf, filter: i64, sig_obs: f64) -> c_int;
