@@ -7,14 +7,22 @@ import pytest
 from fugue_amd import engine as E
 from fugue_amd import model as M
 from fugue_amd import workloads as W
+from tests import knife
+from tests import oracle_margins
+from tests import parity_cases as PC
 from tests.models import ZOO
-from tests.random_models import random_program
 
 pytestmark = pytest.mark.gpu
 
 
-def _run_both(oracle, prog, C, nw, ns, seed, overrides=None, chain0=0):
+def _run_both(oracle, case):
+    """A row of tests/parity_cases.MH_CASES on the device and on the oracle.  dist: the oracle's |ln u - log_alpha| of every step of every
+    chain (tests/oracle_margins.mh_margins: the same run, traced; tests/test_knife_margins_cpu.py asserts both)."""
+    prog = case.make()
+    C, nw, ns, seed, chain0 = case.C, case.nw, case.ns, case.seed, case.chain0
     cp, om = E.compile_model(prog), oracle.OracleModel(prog)
+    assert list(cp.site_names) == list(om.site_names)
+    overrides = case.overrides_for(om.site_names)
     eng = E.Engine(cp, C, seed=seed, chain_offset=chain0)
     rec = list(range(cp.S))
     d_draws = eng.device_alloc(max(1, ns * cp.S * C) * 8)
@@ -22,33 +30,48 @@ def _run_both(oracle, prog, C, nw, ns, seed, overrides=None, chain0=0):
     draws = eng.download(d_draws, (ns, cp.S, C), dtype=np.int64)
     eng.device_free(d_draws)
     odraws, ofinal, oscales, ost = om.mh_run(seed, C, nw, ns, overrides, rec, chain0=chain0, n_threads=8)
-    return cp, eng, st, draws, odraws, ofinal, oscales, ost
+    dist, _ = oracle_margins.mh_margins(om, seed, C, nw, ns, overrides, chain0)
+    return cp, eng, st, draws, odraws, ofinal, oscales, ost, dist
 
 
-def _compare(cp, draws, odraws, max_bad_chains=0):
-    bad = np.zeros(draws.shape[2], dtype=bool)
+def _compare(cp, draws, odraws, dist, chain0=0, where="MH draws against the oracle"):
+    """Recorded draws [ns][S][C] against the oracle's: discrete cells exact, f64 cells to 1e-9.  A chain may part ways only behind a decision
+    of the oracle's within mh_edge_cases.MARGIN of its uniform (knife.excused): dist [nw + ns][C] is the oracle's |ln u - log_alpha| of every
+    step, and a chain's margin is the smallest one up to and including its first differing recorded step.  Returns the mask of parted chains."""
+    ns, C = draws.shape[0], draws.shape[2]
+    nw = dist.shape[0] - ns
+    assert nw >= 0 and dist.shape[1] == C and odraws.shape == draws.shape, (dist.shape, draws.shape, odraws.shape)
+    first = np.full(C, ns)                                     # per chain: the first recorded step that differs, and the first site there
+    site = np.full(C, -1)
     for j in range(cp.S):
         if cp.site_vtypes[j] == 0:
             g, o = draws[:, j, :].view(np.float64), odraws[:, j, :].view(np.float64)
-            bad |= (~np.isclose(g, o, rtol=1e-9, atol=1e-12)).any(axis=0)
+            ne = ~np.isclose(g, o, rtol=1e-9, atol=1e-12)
         else:
-            bad |= (draws[:, j, :] != odraws[:, j, :]).any(axis=0)
-    if bad.any() and max_bad_chains > 0:
-        from tests import knife
-        knife.used("MH draws against the oracle", chains=np.nonzero(bad)[0][:10].tolist())
-    assert bad.sum() <= max_bad_chains, np.nonzero(bad)[0][:10]
-    return bad
+            ne = draws[:, j, :] != odraws[:, j, :]
+        t = np.where(ne.any(axis=0), ne.argmax(axis=0), ns)
+        site = np.where(t < first, j, site)
+        first = np.minimum(first, t)
+    bad = first < ns
+    margin = dist.min(axis=0)
+    first_bad = {}
+    for c in np.nonzero(bad)[0]:
+        t, j = int(first[c]), int(site[c])
+        margin[c] = dist[:nw + t + 1, c].min()
+        cell = (lambda x: float(np.int64(x).view(np.float64))) if cp.site_vtypes[j] == 0 else int
+        first_bad[int(c)] = dict(recorded_step=t, step=nw + t, site=cp.site_names[j], device=cell(draws[t, j, c]), oracle=cell(odraws[t, j, c]),
+                                 margin_of_that_step=float(dist[nw + t, c]))
+    return knife.excused(where, bad, margin, PC.MH_BAND, first_bad, chain0)
 
 
-@pytest.mark.parametrize("name", ["readme", "coin", "refmodel8", "mixture", "alldists", "normal32", "hier_scale", "ridge7", "linreg", "logistic", "poisson_glm", "hier_logsigma"])
+@pytest.mark.parametrize("name", PC.MH_ZOO)
 def test_mh_chain_matches_oracle(oracle, name):
-    prog = ZOO[name]()
-    cp, eng, st, draws, odraws, ofinal, oscales, ost = _run_both(oracle, prog, C=96, nw=150, ns=60, seed=13, chain0=3)
-    # a proposal whose acceptance sits on a 1e-13 knife edge may flip on one chain
-    bad = _compare(cp, draws, odraws, max_bad_chains=1)
+    case = PC.MH_CASES[f"zoo-{name}"]
+    cp, eng, st, draws, odraws, ofinal, oscales, ost, dist = _run_both(oracle, case)
+    bad = _compare(cp, draws, odraws, dist, case.chain0)
     assert abs(st.accept_rate - ost.accept_rate) < 2e-3
     same = np.isclose(eng.mh_scales(), oscales, rtol=1e-10).all(axis=0)
-    assert same.sum() >= 95                                    # frozen after warmup: mh.rs:989-1001
+    assert same[~bad].all(), np.nonzero(~same & ~bad)[0][:10]    # every chain that did not part; frozen after warmup: mh.rs:989-1001
     # final state of every chain whose recorded draws matched: discrete cells exact, f64 cells to the draws' tolerance
     good = ~bad
     final = eng.get_values()
@@ -59,22 +82,22 @@ def test_mh_chain_matches_oracle(oracle, name):
             assert np.array_equal(final[j, good], ofinal[j, good]), cp.site_names[j]
 
 
-@pytest.mark.parametrize("seed", range(12))
+@pytest.mark.parametrize("seed", PC.MH_RANDOM_SEEDS)
 def test_mh_random_models_match_oracle(oracle, seed):
     """Random programs (tests/random_models.py: chains of Normals, scale / rate / probability sites, Categorical selects with zero
     entries in their tables, free discrete sites) through adaptive_mcmc_chain against the oracle: discrete draws exact, f64 1e-9."""
-    prog = random_program(1000 + seed)
-    cp, eng, st, draws, odraws, ofinal, oscales, ost = _run_both(oracle, prog, C=64, nw=80, ns=40, seed=21 + seed, chain0=seed)
-    _compare(cp, draws, odraws, max_bad_chains=1)
+    case = PC.MH_CASES[f"random-{seed}"]
+    cp, eng, st, draws, odraws, ofinal, oscales, ost, dist = _run_both(oracle, case)
+    _compare(cp, draws, odraws, dist, case.chain0)
     assert abs(st.accept_rate - ost.accept_rate) < 3e-3
 
 
 def test_mh_positive_support_uses_log_space_walk(oracle):
     """Gamma(3,2): support-based kind detection picks the log-space walk with its Jacobian
     (mh.rs:339-358, 201-224); mean 1.5 (tests/f_mcmc_proposals.rs:31-70)."""
-    prog = W.gamma_scale_model()
-    cp, eng, st, draws, odraws, *_ = _run_both(oracle, prog, C=512, nw=300, ns=300, seed=2)
-    _compare(cp, draws, odraws, max_bad_chains=2)
+    case = PC.MH_CASES["gamma-log-walk"]
+    cp, eng, st, draws, odraws, *_, dist = _run_both(oracle, case)
+    _compare(cp, draws, odraws, dist, case.chain0)
     x = draws[:, 0, :].view(np.float64)
     assert (x > 0).all()
     assert abs(x.mean() - 1.5) < 0.03
@@ -82,19 +105,11 @@ def test_mh_positive_support_uses_log_space_walk(oracle):
 
 def test_mh_overrides(oracle):
     """adaptive_mcmc_chain_with_overrides (mh.rs:938-944): Reflect, PriorResample and a forced
-    Gaussian walk on a positive-support site."""
-    P = M.Program()
-    a = P.sample(M.addr("a"), M.Uniform(0.0, 2.0))
-    g = P.sample(M.addr("g"), M.Gamma(2.0, 1.0))
-    t = P.sample(M.addr("t"), M.Normal(0.0, 2.0))
-    P.observe(M.addr("y"), M.Normal(a + t, 0.5 + g), 1.0)
-    cp = E.compile_model(P)
-    ov = [None] * cp.S
-    ov[cp.site_names.index("a")] = (E.PROP_REFLECT, 0.0, 2.0)
-    ov[cp.site_names.index("g")] = (E.PROP_GAUSSIAN, 0.0, 0.0)
-    ov[cp.site_names.index("t")] = (E.PROP_PRIOR_RESAMPLE, 0.0, 0.0)
-    cp, eng, st, draws, odraws, *_ = _run_both(oracle, P, C=128, nw=100, ns=100, seed=4, overrides=ov)
-    _compare(cp, draws, odraws, max_bad_chains=1)
+    Gaussian walk on a positive-support site (tests/parity_cases.overrides_model)."""
+    case = PC.MH_CASES["overrides"]
+    assert (E.PROP_GAUSSIAN, E.PROP_REFLECT, E.PROP_PRIOR_RESAMPLE) == (PC.PROP_GAUSSIAN, PC.PROP_REFLECT, PC.PROP_PRIOR_RESAMPLE)
+    cp, eng, st, draws, odraws, *_, dist = _run_both(oracle, case)
+    _compare(cp, draws, odraws, dist, case.chain0)
     av = draws[:, cp.site_names.index("a"), :].view(np.float64)
     assert (av >= 0).all() and (av <= 2).all()
 
