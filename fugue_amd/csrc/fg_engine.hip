@@ -914,6 +914,16 @@ int fg_log_joint(fg_engine *e, double *h_acc, double *h_logp) {
     return FG_OK;
 }
 
+int fg_log_joint_compiled(fg_engine *e, double *h_acc) {
+    NEED_ENGINE(e);
+    if (!h_acc) return FG_E_BAD_ARG;
+    const int rc = e->gt ? FG_E_UNSUPPORTED : fg_jit_log_joint_launch(e, e->d_acc, nullptr, true);
+    if (rc != FG_OK) { if (rc == FG_E_UNSUPPORTED) fg_set_error("fg_log_joint_compiled: the program has no unit compiled at run time"); return rc; }
+    HIPCHK(hipMemcpyAsync(h_acc, e->d_acc, (size_t)3 * e->C * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return FG_OK;
+}
+
 int fg_log_joint_stream(fg_engine *e, double *h_acc, double *h_rec_lp) {
     NEED_ENGINE(e);
     if (!e->P.sstream) { fg_set_error("fg_log_joint_stream: the program has no score stream (some statement needs the interpreter)"); return FG_E_UNSUPPORTED; }

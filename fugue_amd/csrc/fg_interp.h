@@ -85,12 +85,9 @@ __device__ __forceinline__ double fg_operand(uint32_t w, double imm, const doubl
     return pool[idx];
 }
 
-// Integer value of an observed expression (`Value::as_bool` / `as_index`,
-// crates/fugue-wasm/src/dsl.rs:68-81,1002-1021)
-__device__ __forceinline__ long long fg_int_of(double v, uint32_t vtype) {
-    if (vtype == 1u /*bool*/) return v != 0.0;
-    return fg_finite(v) ? (long long)v : 0;
-}
+// Integer value of an observed expression: fg_obs_int (fg_math.h), out of line like the densities it feeds -- only a discrete
+// statement that observes an f64 expression gets here, and its compares and selects stay out of the interpreter loop
+__device__ __noinline__ long long fg_obs_int_cold(double v, uint32_t vtype) { return fg_obs_int(v, vtype); }
 
 // ---- single-site MH proposal context (SingleSiteProposalHandler, src/inference/mh.rs:324-617) ----
 // proposal kinds FG_PROP_*: include/fugue_amd.h
@@ -295,7 +292,7 @@ __device__ __forceinline__ void fg_exec(const FgIns *prog, int n, const double *
                         }
                     }
                 } else {
-                    xi = fg_int_of(fg_operand<RM>(xw, FG_I_IMM(I, 0), slots, pool, tw, rm), vtype);
+                    xi = fg_obs_int_cold(fg_operand<RM>(xw, FG_I_IMM(I, 0), slots, pool, tw, rm), vtype);
                 }
                 if ((op & FG_F_INVALID) != 0u || xi < 0 || xi >= (long long)K) lp = FG_NEG_INF;
                 else if (in_pool) lp = pool[base + K + (int)xi];          // precomputed ln p (or -inf)
@@ -347,7 +344,7 @@ __device__ __forceinline__ void fg_exec(const FgIns *prog, int n, const double *
                 double xf = 0.0; long long xi = 0;
                 if (vtype == 0u) xf = fg_operand<RM>(xw, FG_I_IMM(I, 0), slots, pool, tw, rm);
                 else if (FG_OPND_KIND(xw) == FG_OPND_SLOT_I) xi = fg_as_i64(slots[fg_row<RM>(rm, FG_OPND_IDX(xw)) * tw]);
-                else xi = fg_int_of(fg_operand<RM>(xw, FG_I_IMM(I, 0), slots, pool, tw, rm), vtype);
+                else xi = fg_obs_int_cold(fg_operand<RM>(xw, FG_I_IMM(I, 0), slots, pool, tw, rm), vtype);
                 if ((op & FG_F_INVALID) != 0u) lp = FG_NEG_INF;
                 else if (code == 12u && hoisted) {
                     // Normal with constant parameters -- the hot case (distribution.rs:189-208):

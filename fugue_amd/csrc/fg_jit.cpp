@@ -258,7 +258,7 @@ struct Gen {
                 if (FG_OPND_KIND(bw) == FG_OPND_POOL) return;
                 const int base = (int)FG_OPND_IDX(bw);
                 std::string xi = FG_OPND_KIND(xw) == FG_OPND_SLOT_I ? "fg_as_i64(" + slot(FG_OPND_IDX(xw)) + ")"
-                                                                      : "fg_jit_int_of(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u)";
+                                                                      : "fg_obs_int(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u)";
                 if (invalid) { add("dtot = NAN;"); return; }
                 std::string dpick = "double dpv = " + dslot((uint32_t)base) + "; ";
                 for (int q = 1; q < K; ++q) dpick += "dpv = (j == " + std::to_string(q) + ") ? " + dslot((uint32_t)(base + q)) + " : dpv; ";
@@ -272,7 +272,7 @@ struct Gen {
             std::string xs;
             if (vtype == 0u) xs = "const double xf = " + opnd(xw, I.imm[0]) + "; const long long xi = 0;";
             else if (FG_OPND_KIND(xw) == FG_OPND_SLOT_I) xs = "const double xf = 0.0; const long long xi = fg_as_i64(" + slot(FG_OPND_IDX(xw)) + ");";
-            else xs = "const double xf = 0.0; const long long xi = fg_jit_int_of(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u);";
+            else xs = "const double xf = 0.0; const long long xi = fg_obs_int(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u);";
             if (dx == "0.0" && d0 == "0.0" && d1 == "0.0" && d2 == "0.0") return;
             if (invalid) { add("dtot = NAN;"); return; }
             char sig[64];
@@ -388,7 +388,7 @@ struct Gen {
                 const uint32_t bw = I.opnd[1]; const int K = (int)I.opnd[2];
                 const bool in_pool = FG_OPND_KIND(bw) == FG_OPND_POOL; const int base = (int)FG_OPND_IDX(bw);
                 std::string xi = FG_OPND_KIND(xw) == FG_OPND_SLOT_I ? "fg_as_i64(" + slot(FG_OPND_IDX(xw)) + ")"
-                                                                      : "fg_jit_int_of(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u)";
+                                                                      : "fg_obs_int(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u)";
                 if (invalid) { add("{ double lp = FG_NEG_INF; " + accum + " }"); return; }
                 if (in_pool) {
                     std::string tn = "fg_jit_tab" + std::to_string(tables->size());
@@ -407,7 +407,7 @@ struct Gen {
             std::string xs;
             if (vtype == 0u) xs = "const double xf = " + opnd(xw, I.imm[0]) + "; const long long xi = 0;";
             else if (FG_OPND_KIND(xw) == FG_OPND_SLOT_I) xs = "const double xf = 0.0; const long long xi = fg_as_i64(" + slot(FG_OPND_IDX(xw)) + ");";
-            else xs = "const double xf = 0.0; const long long xi = fg_jit_int_of(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u);";
+            else xs = "const double xf = 0.0; const long long xi = fg_obs_int(" + opnd(xw, I.imm[0]) + ", " + std::to_string(vtype) + "u);";
             if (invalid) { add("{ double lp = FG_NEG_INF; " + accum + " }"); return; }
             if (code == 12u && hoisted) {                                     // Normal with constant parameters, inline as in fg_interp.h
                 const std::string z = (op & FG_F_POW2SCALE) ? "(xf - p0) * " + lit(I.h[4]) : std::string("(xf - p0) / p1");
@@ -585,8 +585,7 @@ __device__ const double *fg_jit_ctab_ptr = nullptr;
 static __device__ __forceinline__ const FG_JIT_AS4 double *fg_jit_ctab() { return (const FG_JIT_AS4 double *)(unsigned long)fg_jit_ctab_ptr; }
 // the 17 samplers behind one call, like the interpreter's fg_sample_cold (the same fg_sample_dist: the same draws)
 static __device__ __noinline__ long long fg_jit_sample(uint32_t kind, bool hoisted, double p0, double p1, double p2, FgStream &s) { return fg_sample_dist(kind, hoisted, p0, p1, p2, s); }
-// fg_int_of (fg_interp.h): the integer value of an observed expression
-static __device__ __forceinline__ long long fg_jit_int_of(double v, unsigned vtype) { if (vtype == 1u) return v != 0.0; return fg_finite(v) ? (long long)v : 0; }
+// (the integer value of an observed expression is fg_obs_int of the embedded fg_math.h: the library's own text)
 )FGJ";
 
 }  // namespace

@@ -35,6 +35,22 @@ FG_HD long long fg_f2i_sat(double v) {   // Rust `as i64`
     if (v <= -9223372036854775808.0) return FG_I64_MIN;
     return (long long)v;
 }
+// An observed expression as the integer a discrete density is evaluated at (crates/fugue-wasm/src/dsl.rs): `Value::as_index` (:71-77) is
+// `x as i64` only for a finite x without a fractional part, `Stmt::Observe` (:985-998) takes `as_index().unwrap_or(0)` -- then `.max(0)`
+// for the u64 / usize families -- and `as_bool` (:79-84) is `!= 0.0` (NaN is true).  vtype: FG_BOOL 1, FG_U64 2, FG_USIZE 3, FG_I64 4.
+FG_HD long long fg_obs_int(double v, uint32_t vtype) {
+    if (vtype == 1u) return v != 0.0;
+    if (!fg_finite(v) || v != floor(v)) return 0;
+    const long long i = fg_f2i_sat(v);
+    return (vtype != 4u && i < 0) ? 0 : i;
+}
+// Binomial's n from its f64 parameter (`build_dist`, dsl.rs:843-851): negative, fractional or non-finite is an error -- the statement is
+// factor(-inf), dsl.rs:1002-1006 --, otherwise `n as u64` (saturating)
+FG_HD bool fg_binomial_n(double p0, unsigned long long *n) {
+    if (!(p0 >= 0.0) || !fg_finite(p0) || p0 != floor(p0)) return false;
+    *n = p0 >= 18446744073709551616.0 ? 18446744073709551615ull : (unsigned long long)p0;
+    return true;
+}
 FG_HD double fg_as_double(long long bits) { union { long long i; double d; } u; u.i = bits; return u.d; }
 FG_HD long long fg_as_i64(double d) { union { long long i; double d; } u; u.d = d; return u.i; }
 FG_HD double fg_clamp(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }  // NaN stays
@@ -79,8 +95,9 @@ FG_HD bool fg_hoist(uint32_t kind, double p0, double p1, double p2, double *h) {
                              h[0] = fg_lgamma(p0) + fg_lgamma(p1) - fg_lgamma(p0 + p1); return true;
     case 8:  /* Gamma */     if (p0 <= 0.0 || p1 <= 0.0 || !fg_finite(p0) || !fg_finite(p1)) return false;
                              h[0] = log(p1); h[1] = fg_lgamma(p0); return true;
-    case 2:  /* Binomial */  if (!fg_finite(p1) || !(p1 >= 0.0 && p1 <= 1.0)) return false;
-                             { double n = (double)(unsigned long long)p0; h[0] = fg_lgamma(n + 1.0);
+    case 2:  /* Binomial */  { unsigned long long nn; if (!fg_binomial_n(p0, &nn)) return false;
+                               if (!fg_finite(p1) || !(p1 >= 0.0 && p1 <= 1.0)) return false;
+                               double n = (double)nn; h[0] = fg_lgamma(n + 1.0);
                                h[1] = (p1 > 0.0) ? log(p1) : FG_NEG_INF; h[2] = (p1 < 1.0) ? log(1.0 - p1) : FG_NEG_INF; } return true;
     case 13: /* Poisson */   if (p0 <= 0.0 || !fg_finite(p0)) return false; h[0] = log(p0); return true;
     case 14: /* StudentT */  if (p0 <= 0.0 || p2 <= 0.0 || !fg_finite(p0) || !fg_finite(p2) || !fg_finite(p1)) return false;
@@ -169,9 +186,11 @@ FG_HD double fg_logpdf(uint32_t kind, bool hoisted, bool pow2, double xf, long l
         double lg = hoisted ? h[1] : fg_lgamma(p0);
         return p0 * log_rate + (p0 - 1.0) * log_x - p1 * xf - lg; }
     case 2: { /* Binomial(n, p): :1138-1165 */
+        unsigned long long n;
+        if (!fg_binomial_n(p0, &n)) return FG_NEG_INF;                  // dsl.rs:843-851 (a hoisted n passed fg_hoist: the test is then constant)
         if (!hoisted && (!fg_finite(p1) || !(p1 >= 0.0 && p1 <= 1.0))) return FG_NEG_INF;
         if (xi < 0) return FG_NEG_INF;
-        unsigned long long n = (unsigned long long)p0, k = (unsigned long long)xi;
+        const unsigned long long k = (unsigned long long)xi;
         if (k > n) return FG_NEG_INF;
         if (p1 == 0.0) return (k == 0) ? 0.0 : FG_NEG_INF;
         if (p1 == 1.0) return (k == n) ? 0.0 : FG_NEG_INF;
@@ -270,7 +289,7 @@ FG_HD double fg_dlogpdf(uint32_t kind, double xf, long long xi, double p0, doubl
     case 1: { const double ps = fg_digamma(p0 + p1);                                                                          // Beta(a, b)
               return ((p0 - 1.0) / xf - (p1 - 1.0) / (1.0 - xf)) * dx + (log(xf) - fg_digamma(p0) + ps) * dp0 + (log(1.0 - xf) - fg_digamma(p1) + ps) * dp1; }
     case 8: return ((p0 - 1.0) / xf - p1) * dx + (log(p1) + log(xf) - fg_digamma(p0)) * dp0 + (p0 / p1 - xf) * dp1;           // Gamma(shape, rate)
-    case 2: { const double n = (double)(unsigned long long)p0, k = (double)xi; return (k / p1 - (n - k) / (1.0 - p1)) * dp1; } // Binomial(n, p)
+    case 2: { unsigned long long nn = 0; (void)fg_binomial_n(p0, &nn); const double n = (double)nn, k = (double)xi; return (k / p1 - (n - k) / (1.0 - p1)) * dp1; } // Binomial(n, p)
     case 13: return ((double)xi / p0 - 1.0) * dp0;                                                                            // Poisson(lambda)
     case 14: { const double z = (xf - p1) / p2, q = p0 + z * z;                                                               // StudentT(df, loc, scale)
                const double gx = -(p0 + 1.0) * z / (p2 * q);

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(FG_WAVE * 4, FG_MIN_WAVES) void k_predict_eval(FgPr
                     if (want_ll) {
                         long long xi;
                         if (FG_OPND_KIND(xw) == FG_OPND_SLOT_I) xi = fg_as_i64(slots[FG_OPND_IDX(xw) * tw]);
-                        else xi = fg_int_of(fg_operand(xw, I->imm[0], slots, pool, tw), vtype);
+                        else xi = fg_obs_int_cold(fg_operand(xw, I->imm[0], slots, pool, tw), vtype);
                         if ((op & FG_F_INVALID) != 0u || xi < 0 || xi >= (long long)K) lp = FG_NEG_INF;
                         else if (in_pool) lp = pool[base + K + (int)xi];          // precomputed ln p (or -inf)
                         else { const double p = slots[(base + (int)xi) * tw]; lp = p > 0.0 ? log(p) : FG_NEG_INF; }
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(FG_WAVE * 4, FG_MIN_WAVES) void k_predict_eval(FgPr
                         double xf = 0.0; long long xi = 0;
                         if (vtype == 0u) xf = fg_operand(xw, I->imm[0], slots, pool, tw);
                         else if (FG_OPND_KIND(xw) == FG_OPND_SLOT_I) xi = fg_as_i64(slots[FG_OPND_IDX(xw) * tw]);
-                        else xi = fg_int_of(fg_operand(xw, I->imm[0], slots, pool, tw), vtype);
+                        else xi = fg_obs_int_cold(fg_operand(xw, I->imm[0], slots, pool, tw), vtype);
                         if ((op & FG_F_INVALID) != 0u) lp = FG_NEG_INF;
                         else if (code == 12u && hoisted) {   // Normal with constant parameters, as fg_exec has it inline
                             if (!fg_finite(xf)) lp = FG_NEG_INF;

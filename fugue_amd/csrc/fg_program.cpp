@@ -342,10 +342,11 @@ void fg_program::compile_stmt(const FgStmt &s, std::vector<FgIns> &out, int &tem
         // a constant observed count under varying parameters (a count regression): its own term -- ln k!, ln C(n, k) -- once, here
         if (!params_const && nodes[s.value].is_const && s.vtype != FG_F64 && s.vtype != FG_BOOL && (s.dist == FG_POISSON || s.dist == FG_BINOMIAL)) {
             const double v = nodes[s.value].cval;
-            const long long xi = std::isfinite(v) ? (long long)v : 0LL;                 // fg_int_of (fg_interp.h)
+            const long long xi = fg_obs_int(v, (uint32_t)s.vtype);                      // the count the kernels observe (fg_math.h)
             if (s.dist == FG_POISSON && xi >= 0) { I.op |= FG_F_XHOIST; I.h[3] = fg_lgamma((double)xi + 1.0); }
-            if (s.dist == FG_BINOMIAL && nodes[s.params[0]].is_const && xi >= 0) {
-                const unsigned long long n = (unsigned long long)nodes[s.params[0]].cval, k = (unsigned long long)xi;
+            unsigned long long n = 0;
+            if (s.dist == FG_BINOMIAL && nodes[s.params[0]].is_const && xi >= 0 && fg_binomial_n(nodes[s.params[0]].cval, &n)) {
+                const unsigned long long k = (unsigned long long)xi;
                 if (k <= n) { I.op |= FG_F_XHOIST; I.h[3] = fg_lgamma((double)n + 1.0) - fg_lgamma((double)k + 1.0) - fg_lgamma((double)(n - k) + 1.0); }
             }
         }
@@ -591,9 +592,8 @@ int fg_program::finalize() {
             g.flags = FG_G_GEN | (FG_INS_OPCODE(F.op) << 16) | (kx == FG_OPND_IMM ? FG_G_X_CONST : 0u) | (vt != (uint32_t)FG_F64 ? FG_G_GEN_XINT : 0u) |
                       ((F.op & FG_F_HOISTED) ? FG_G_GEN_HOISTED : 0u) | ((F.op & FG_F_SCALEHOIST) ? FG_G_GEN_SH : 0u) | ((F.op & FG_F_INVALID) ? FG_G_GEN_INVALID : 0u) |
                       ((F.op & FG_F_XHOIST) ? FG_G_GEN_XH : 0u);
-            // an observed constant of a discrete distribution is its integer value (fg_int_of, fg_interp.h)
-            if (kx == FG_OPND_IMM) g.x = vt == (uint32_t)FG_F64 ? F.imm[0]
-                                        : fg_as_double(vt == (uint32_t)FG_BOOL ? (long long)(F.imm[0] != 0.0) : (std::isfinite(F.imm[0]) ? (long long)F.imm[0] : 0LL));
+            // an observed constant of a discrete distribution is its integer value (fg_obs_int, fg_math.h)
+            if (kx == FG_OPND_IMM) g.x = vt == (uint32_t)FG_F64 ? F.imm[0] : fg_as_double(fg_obs_int(F.imm[0], vt));
             for (int q = 0; q < 3; q++) {
                 if (FG_OPND_KIND(F.opnd[1 + q]) == FG_OPND_SLOT_F) { g.flags |= FG_G_GEN_P0SLOT << q; g.p[q] = fg_as_double((long long)FG_OPND_IDX(F.opnd[1 + q])); }
                 else g.p[q] = F.imm[1 + q];
@@ -968,7 +968,9 @@ int fg_program_observe_value(const fg_program *p, int k, double *out) {
     const FgStmt *s = observe_stmt(p, k);
     if (!s || !out) { fg_set_error("fg_program_observe_value: k outside [0, O) or a null output"); return FG_E_BAD_ARG; }
     if (s->value < 0 || !p->nodes[s->value].is_const) return 0;
-    *out = p->nodes[s->value].cval;
+    // a discrete statement observes the integer its expression converts to (fg_obs_int): that is what replicated counts compare with
+    const double v = p->nodes[s->value].cval;
+    *out = s->vtype == FG_F64 ? v : (double)fg_obs_int(v, (uint32_t)s->vtype);
     return 1;
 }
 int fg_program_stream_records(const fg_program *p, int which) {

@@ -94,7 +94,7 @@ ABI_SYMBOLS = [
     "fg_program_n_instructions", "fg_program_n_slots", "fg_program_site_name", "fg_program_site_vtype",
     "fg_program_site_of_handle", "fg_program_f64_site", "fg_program_dep_count", "fg_program_stream_records", "fg_last_error", "fg_abi_version",
     "fg_engine_new", "fg_engine_free", "fg_engine_synchronize", "fg_engine_stream", "fg_engine_set_stream", "fg_engine_n_chains",
-    "fg_engine_set_values", "fg_engine_get_values", "fg_engine_values_device", "fg_prior_init", "fg_log_joint", "fg_log_joint_stream",
+    "fg_engine_set_values", "fg_engine_get_values", "fg_engine_values_device", "fg_prior_init", "fg_log_joint", "fg_log_joint_stream", "fg_log_joint_compiled",
     "fg_program_sample_discrete_uniform",
     "fg_hmc_config_default", "fg_hmc_init", "fg_hmc_step", "fg_hmc_step_info", "fg_hmc_get_mass", "fg_hmc_run", "fg_hmc_get_stats", "fg_hmc_get_step_sizes",
     "fg_hmc_get_log_joint", "fg_hmc_set_step_size", "fg_hmc_set_n_leapfrog", "fg_hmc_is_warming_up", "fg_hmc_iterations", "fg_hmc_short_quotient", "fg_hmc_range_proved", "fg_hmc_step_recorded",
@@ -210,6 +210,7 @@ def lib():
     L.fg_prior_init.argtypes = [vp, C.c_uint32, dp]
     L.fg_log_joint.argtypes = [vp, dp, dp]
     L.fg_log_joint_stream.argtypes = [vp, dp, dp]
+    L.fg_log_joint_compiled.argtypes = [vp, dp]
     L.fg_hmc_config_default.argtypes = [C.POINTER(fg_hmc_config)]
     L.fg_hmc_init.argtypes = [vp, C.POINTER(fg_hmc_config), C.c_int]
     L.fg_hmc_step.argtypes = [vp, C.c_int, vp]
@@ -672,6 +673,12 @@ class Engine:
         rec = np.zeros((max(1, self.cp.stream_records[1]), self.C)) if want_records else None
         _check(lib().fg_log_joint_stream(self.h, _dp(acc), _dp(rec) if want_records else None))
         return (acc, rec[:self.cp.stream_records[1]]) if want_records else acc
+
+    def log_joint_compiled(self) -> np.ndarray:
+        """ScoreGivenTrace through the unit compiled at run time (k_log_joint_jit), acc [3][C]; EngineError where the program has none."""
+        acc = np.zeros((3, self.C))
+        _check(lib().fg_log_joint_compiled(self.h, _dp(acc)))
+        return acc
 
     # ---- HMC ----------------------------------------------------------------------------
     def hmc_init(self, cfg: fg_hmc_config, n_warmup: int):

@@ -117,7 +117,9 @@ int fg_program_observe_vtype(const fg_program *p, int k);
 int fg_program_observe_dist(const fg_program *p, int k);
 /* the observed value of observe statement k (program order) where the model states it: returns 1 and *out = the value as the double
  * `x as f64` when it reads no site (a literal or a data element: the `observations` slice of the reference's workflows,
- * tests/end_to_end_workflows.rs:650-745), 0 when it reads a site (its value moves with the draw; *out is left alone).  FG_E_BAD_ARG:
+ * tests/end_to_end_workflows.rs:650-745), 0 when it reads a site (its value moves with the draw; *out is left alone).  A discrete
+ * statement gives the value AS OBSERVED: the integer its expression converts to (dsl.rs:71-84,985-998: 2.5 -> 0, -2 -> 0 for a count,
+ * any non-zero -> 1 for a Bernoulli), which is what replicated cells compare with.  FG_E_BAD_ARG:
  * k outside [0, O), a null argument. */
 int fg_program_observe_value(const fg_program *p, int k, double *out);
 int fg_program_f64_site(const fg_program *p, int k);
@@ -188,6 +190,10 @@ int fg_log_joint(fg_engine *e, double *h_acc, double *h_logp);
  * fg_program_stream_records(p, 1): the log-density of every statement.  FG_E_UNSUPPORTED when the program has no
  * score stream. */
 int fg_log_joint_stream(fg_engine *e, double *h_acc, double *h_rec_lp);
+/* The same scoring run through the program's unit compiled at run time (k_log_joint_jit: what a sampler session re-scores its state
+ * with after fg_engine_set_values), built here if it does not exist yet.  h_acc [3][C].  No fall-back: FG_E_UNSUPPORTED when the
+ * program has no compiled unit (FG_JIT=0, no run-time compiler, no f64 site, the global-tile instantiations). */
+int fg_log_joint_compiled(fg_engine *e, double *h_acc);
 /* The model's return value `A` for every draw and chain -- the first half of each `(A, Trace)` pair hmc_chain / adaptive_mcmc_chain
  * return (src/inference/hmc.rs:566-583, mh.rs:921-944) and the value a Particle's trace gives (smc.rs) -- evaluated on the device:
  * d_draws [n][n_rows][C] 8-byte cells -> d_out [n][R][C] doubles, R = fg_program_n_results.  Row j of a draw holds sorted site

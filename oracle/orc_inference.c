@@ -348,14 +348,6 @@ static int64_t f2i_sat(double v) {
 static double stmt_lp(const orc_stmt *s, const double *p, int np, orc_cell x) {
     return s->vtype == ORC_F64 ? orc_logpdf(s->dist, 0, x.f, 0, p, np) : orc_logpdf(s->dist, 1, 0.0, x.i, p, np);
 }
-static orc_cell obs_value(const orc_model *m, const orc_stmt *s, const orc_cell *vals) {
-    double v = orc_eval(m, s->value, vals);
-    orc_cell c;
-    if (s->vtype == ORC_F64) c.f = v;
-    else if (s->vtype == ORC_BOOL) c.i = (v != 0.0);
-    else c.i = isfinite(v) ? (int64_t)v : 0;
-    return c;
-}
 
 /* One run of SingleSiteProposalHandler (mh.rs:361-617) for a fixed-structure
  * model: propose at `target`, replay and re-score everything else.
@@ -369,7 +361,7 @@ static void propose_and_score(const orc_model *m, orc_stream *st, orc_cell *pv, 
         const orc_stmt *s = &m->stmts[i];
         if (s->kind == ORC_STMT_FACTOR) { acc[2] += orc_eval(m, s->value, pv); continue; }
         int np = orc_stmt_params(m, s, pv, p);
-        if (s->kind == ORC_STMT_OBSERVE) { acc[1] += stmt_lp(s, p, np, obs_value(m, s, pv)); continue; }
+        if (s->kind == ORC_STMT_OBSERVE) { acc[1] += stmt_lp(s, p, np, orc_observe_value(m, s, pv)); continue; }
         int j = s->sorted;
         if (j == target) {
             orc_cell cur = pv[j], prop = cur;

@@ -30,6 +30,7 @@ struct orc_model {
 
 double orc_eval(const orc_model *m, int id, const orc_cell *vals);
 int    orc_stmt_params(const orc_model *m, const orc_stmt *s, const orc_cell *vals, double *p);
+orc_cell orc_observe_value(const orc_model *m, const orc_stmt *s, const orc_cell *vals);   /* Stmt::Observe, dsl.rs:985-998 */
 double orc_logpdf_du(int64_t x, int64_t lo, int64_t hi);
 
 #endif

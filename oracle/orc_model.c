@@ -165,13 +165,26 @@ static double stmt_logpdf(const orc_stmt *s, const double *p, int np, orc_cell x
     return orc_logpdf(s->dist, 1, 0.0, x.i, p, np);
 }
 
-static orc_cell observe_value(const orc_model *m, const orc_stmt *s, const orc_cell *vals) {
+/* Value::as_index, crates/fugue-wasm/src/dsl.rs:71-77: `F64(x) if x.fract() == 0.0 && x.is_finite() => Some(*x as i64)`, else None.
+ * f64::fract is `x - x.trunc()`; `as i64` saturates.  Returns 0 for None. */
+static int as_index(double x, int64_t *out) {
+    double fr = x - trunc(x);                          /* NaN for NaN and +-inf */
+    if (!(fr == 0.0) || !isfinite(x)) return 0;
+    if (x >= 9223372036854775808.0) *out = INT64_MAX;
+    else if (x <= -9223372036854775808.0) *out = INT64_MIN;
+    else *out = (int64_t)x;
+    return 1;
+}
+/* Stmt::Observe, dsl.rs:985-998: what each family of value type observes of the evaluated expression */
+orc_cell orc_observe_value(const orc_model *m, const orc_stmt *s, const orc_cell *vals) {
     double v = orc_eval(m, s->value, vals);
     orc_cell c;
+    int64_t i = 0;
     switch (s->vtype) {
-    case ORC_F64:  c.f = v; break;
-    case ORC_BOOL: c.i = (v != 0.0); break;           /* Value::as_bool, dsl.rs:76-81 */
-    default: c.i = isfinite(v) ? (int64_t)v : 0; break;
+    case ORC_F64:  c.f = v; break;                     /* v.as_f64() */
+    case ORC_BOOL: c.i = (v != 0.0); break;            /* v.as_bool(), dsl.rs:79-84: NaN is true */
+    case ORC_I64:  c.i = as_index(v, &i) ? i : 0; break;                   /* as_index().unwrap_or(0) */
+    default:       c.i = as_index(v, &i) ? (i > 0 ? i : 0) : 0; break;     /* U64 / Usize: as_index().unwrap_or(0).max(0) */
     }
     return c;
 }
@@ -190,7 +203,7 @@ void orc_run_score(const orc_model *m, const orc_cell *vals, double acc[3], doub
             acc[0] += lp;
             if (logp) logp[s->sorted] = lp;
         } else {
-            acc[1] += stmt_logpdf(s, pbuf, np, observe_value(m, s, vals));
+            acc[1] += stmt_logpdf(s, pbuf, np, orc_observe_value(m, s, vals));
         }
     }
 }
@@ -210,7 +223,7 @@ void orc_run_prior(const orc_model *m, orc_stream *st, orc_cell *vals, double ac
             acc[0] += lp;
             if (logp) logp[s->sorted] = lp;
         } else {
-            acc[1] += stmt_logpdf(s, pbuf, np, observe_value(m, s, vals));
+            acc[1] += stmt_logpdf(s, pbuf, np, orc_observe_value(m, s, vals));
         }
     }
 }

@@ -82,9 +82,12 @@ static double lp_gamma(double x, double shape, double rate) {
 }
 /* Binomial(n, p): distribution.rs:1138-1165 */
 static double lp_binomial(int64_t k, double nd, double p) {
+    /* build_dist, dsl.rs:843-851: `a[0] < 0.0 || a[0].fract() != 0.0` is an error (the statement is factor(-inf), :1002-1006);
+     * fract() of NaN and of +-inf is NaN.  Otherwise `a[0] as u64`, saturating. */
+    if (nd < 0.0 || (nd - trunc(nd)) != 0.0) return NEG_INF;
     if (!isfinite(p) || !(p >= 0.0 && p <= 1.0)) return NEG_INF;
     if (k < 0) return NEG_INF;                 /* u64 domain */
-    uint64_t n = (uint64_t)nd;
+    uint64_t n = nd >= 18446744073709551616.0 ? UINT64_MAX : (uint64_t)nd;
     if ((uint64_t)k > n) return NEG_INF;
     if (p == 0.0) return (k == 0) ? 0.0 : NEG_INF;
     if (p == 1.0) return ((uint64_t)k == n) ? 0.0 : NEG_INF;

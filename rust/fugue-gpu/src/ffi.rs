@@ -301,6 +301,7 @@ extern "C" {
     pub fn fg_engine_n_chains(e: *const fg_engine) -> i64;
     pub fn fg_engine_values_device(e: *mut fg_engine) -> *mut c_void;                // d_cells [S][C]
     pub fn fg_log_joint_stream(e: *mut fg_engine, h_acc: *mut f64, h_rec_lp: *mut f64) -> c_int;
+    pub fn fg_log_joint_compiled(e: *mut fg_engine, h_acc: *mut f64) -> c_int;      // k_log_joint_jit, no fall-back
     // ---- pieces of the samplers with their randomness injected (what the reference's unit tests drive: hmc.rs:304-329, 419-535)
     pub fn fg_hmc_get_log_joint(e: *mut fg_engine, h_lj: *mut f64) -> c_int;
     pub fn fg_hmc_get_mass(e: *mut fg_engine, h_m_inv: *mut f64) -> c_int;

@@ -142,6 +142,34 @@ def hierarchy_mirror():
     return P
 
 
+# observed values that are no counts: the reference observes 0 where `as_index` is None (a fractional part) and clamps a negative
+# count to 0 (dsl.rs:71-77, 985-998); the text hands the expression over unchanged and the conversion happens where it is scored
+OBS_CAST = '''
+    let x <- sample(addr!("x"), Normal(0.0, 1.0));
+    observe(addr!("k"), Poisson(3.0), 2.5);
+    observe(addr!("kx"), Poisson(exp(x)), 2.5);
+    observe(addr!("neg"), Poisson(3.0), -2.0);
+    observe(addr!("b"), Binomial(8, 0.25), 2.5);
+    observe(addr!("c"), Categorical(0.2, 0.5, 0.3), 1.5);
+    observe(addr!("flag"), Bernoulli(0.3), 0.5);
+    observe(addr!("seven"), Poisson(3.0), 7.0);
+    pure(x)
+'''
+
+
+def obs_cast_mirror():
+    P = M.Program()
+    x = P.sample(M.addr("x"), M.Normal(0.0, 1.0))
+    P.observe(M.addr("k"), M.Poisson(3.0), 2.5)
+    P.observe(M.addr("kx"), M.Poisson(M.exp(x)), 2.5)
+    P.observe(M.addr("neg"), M.Poisson(3.0), -2.0)
+    P.observe(M.addr("b"), M.Binomial(8, 0.25), 2.5)
+    P.observe(M.addr("c"), M.Categorical([0.2, 0.5, 0.3]), 1.5)
+    P.observe(M.addr("flag"), M.Bernoulli(0.3), 0.5)
+    P.observe(M.addr("seven"), M.Poisson(3.0), 7.0)
+    return P
+
+
 PAIRS = {
     "coin": (COIN, COIN_DATA, coin_mirror),
     "regression": (REGRESSION, REGRESSION_DATA, regression_mirror),
@@ -150,4 +178,5 @@ PAIRS = {
     "factor_math": (FACTOR_MATH, None, factor_math_mirror),
     "discrete": (DISCRETE, None, discrete_mirror),
     "hierarchy": (HIERARCHY, HIERARCHY_DATA, hierarchy_mirror),
+    "obs_cast": (OBS_CAST, None, obs_cast_mirror),
 }

@@ -211,6 +211,38 @@ def hier_logsigma(groups: int = 5) -> M.Program:
     return P
 
 
+def obs_casts() -> M.Program:
+    """Observed constants that are no counts -- 2.5 (no index: the reference observes 0), -2.0 (clamped to 0) -- beside an ordinary 7.0, on
+    Poisson / Binomial / Categorical statements whose parameters read f64 sites (dsl.rs:71-77, 985-998), plus a discrete latent: the
+    transition kernels and the compiled units must carry the converted integer and its hoisted ln k! / ln C(n, k).  (1e300 saturates at
+    i64::MAX, where a Poisson term is -3.8e20 -- one ulp of the log-joint is then 65536 and no accept test or finite difference means
+    anything -- and a Binomial or Categorical term -inf: it has its own model, `obs_casts_sat`, for the tests that score.)"""
+    P = M.Program()
+    a = P.sample(M.addr("a"), M.Normal(0.0, 1.0))
+    r = P.sample(M.addr("r"), M.Gamma(3.0, 1.5))
+    b = P.sample(M.addr("b"), M.Beta(2.0, 3.0))
+    z = P.sample(M.addr("z"), M.Categorical([0.4, 0.6]))
+    for i, v in enumerate([2.5, -2.0, 7.0]):
+        P.observe(M.addr("pe", i), M.Poisson(M.exp(0.3 * a) + z), v)          # an expression rate: the interpreter / the generated statement
+        P.observe(M.addr("pr", i), M.Poisson(r), v)                            # a leaf rate: a stream record with the count's own term
+        P.observe(M.addr("bi", i), M.Binomial(9, b), v)
+        P.observe(M.addr("ca", i), M.Categorical([b, 1.0 - b]), 1.0 if v == 7.0 else v)       # (7 is outside a table of two: the ordinary value here is 1)
+    return P
+
+
+def obs_casts_sat() -> M.Program:
+    """The observed constant 1e300: `x as i64` saturates, the count is i64::MAX and ln k! = lgamma(2^63) is hoisted by the host.  For the
+    tests that score a program against the oracle (1e-12 relative); no sampler can move under a term of -3.8e20."""
+    P = M.Program()
+    a = P.sample(M.addr("a"), M.Normal(0.0, 1.0))
+    r = P.sample(M.addr("r"), M.Gamma(3.0, 1.5))
+    P.observe(M.addr("pe"), M.Poisson(M.exp(0.3 * a)), 1e300)
+    P.observe(M.addr("pr"), M.Poisson(r), 1e300)
+    return P
+
+
+ZOO["obs_casts"] = obs_casts
+ZOO["obs_casts_sat"] = obs_casts_sat
 ZOO["logistic"] = lambda: W.logistic_regression(*W.classification_data(14)[:2])     # the reference's classification example, small
 ZOO["poisson_glm"] = poisson_glm
 ZOO["hier_logsigma"] = hier_logsigma

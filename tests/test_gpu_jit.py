@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 INTERP_MODELS = ["alldists", "poisson_glm", "hier_logsigma", "logistic", "coin"]
 
 
-@pytest.mark.parametrize("name,adapt_mass", [("alldists", True), ("alldists", False), ("poisson_glm", True), ("hier_logsigma", False), ("logistic", True), ("coin", False)])
+@pytest.mark.parametrize("name,adapt_mass", [("alldists", True), ("alldists", False), ("poisson_glm", True), ("hier_logsigma", False), ("logistic", True), ("coin", False), ("obs_casts", False), ("obs_casts_sat", False)])
 def test_jit_hmc_is_bit_identical_to_the_interpreter(name, adapt_mass, monkeypatch):
     cp = E.compile_model(ZOO[name]())
     C, nw, ns = 150, 30, 20
@@ -117,7 +117,7 @@ def test_jit_is_not_used_where_a_faster_kernel_exists(monkeypatch):
         eng.close()
 
 
-@pytest.mark.parametrize("name,with_overrides", [("alldists", False), ("alldists", True), ("poisson_glm", False), ("hier_logsigma", True), ("logistic", False), ("coin", False)])
+@pytest.mark.parametrize("name,with_overrides", [("alldists", False), ("alldists", True), ("poisson_glm", False), ("hier_logsigma", True), ("logistic", False), ("coin", False), ("obs_casts", True), ("obs_casts_sat", False)])
 def test_jit_mh_is_bit_identical_to_the_interpreter(name, with_overrides, monkeypatch):
     """adaptive_mcmc_chain with the scoring run compiled at run time (eight generated statement segments shared by the waves of a
     tile, k_mh_jit_steps) against the one-wave interpreter kernel: recorded draws, final state, adapted scales, log-weights and accept

@@ -75,7 +75,7 @@ def test_prior_init_matches_oracle(oracle, name):
         _close(acc[:, c], oacc, 1e-10, 1e-10)
 
 
-@pytest.mark.parametrize("name", ["readme", "normal32", "coin", "refmodel8", "ridge", "mixture", "alldists", "hier_scale", "ridge7", "linreg", "rand0", "rand1", "rand2", "rand3", "rand4", "rand5"])
+@pytest.mark.parametrize("name", ["readme", "normal32", "coin", "refmodel8", "ridge", "mixture", "alldists", "hier_scale", "ridge7", "linreg", "rand0", "rand1", "rand2", "rand3", "rand4", "rand5", "obs_casts"])
 def test_fd_gradient_matches_oracle(oracle, name):
     """grad_log_joint (hmc.rs:304-329): dense FD vs oracle, and sparse FD vs dense.
     A central difference with h=1e-5 amplifies a 1-ulp difference in log pi by 1/(2h), so
@@ -99,7 +99,7 @@ def test_fd_gradient_matches_oracle(oracle, name):
         _close(g_sparse[fin, c], og[fin], 1e-7, tol)
 
 
-@pytest.mark.parametrize("name", ["readme", "normal32", "refmodel8", "ridge", "alldists", "hier_scale", "mixture", "logistic", "poisson_glm", "hier_logsigma"])
+@pytest.mark.parametrize("name", ["readme", "normal32", "refmodel8", "ridge", "alldists", "hier_scale", "mixture", "logistic", "poisson_glm", "hier_logsigma", "obs_casts"])
 @pytest.mark.parametrize("mode", [E.GRAD_FD_DENSE, E.GRAD_FD_SPARSE])
 def test_hmc_transition_injected(oracle, name, mode):
     """hmc_transition (hmc.rs:419-473) under injected momentum and uniform: accept decision,
