@@ -14,6 +14,8 @@ from .inference import (ChainBatch, ChainSummary, HMCConfig, PopulationSummary, 
 from .diagnostics import (ParameterSummary, RankDiagnostics, StreamMoments, classic_r_hat_f64, effective_sample_size,  # noqa: F401
                           effective_sample_size_multichain, ess_bulk, ess_tail, geweke_diagnostic, r_hat_f64, rank_diagnostics, rank_r_hat_f64,
                           summarize_f64_parameter)
+from .diagnostics import (McseDiagnostics, ess_mean, ess_median, ess_quantile, ess_sd, mad, mcse_diagnostics, mcse_mean, mcse_median,  # noqa: F401
+                          mcse_quantile, mcse_sd, summarise_draws)
 from .comparison import PointwiseComparison, PsisLoo, WeightedComparison, compare_models, model_comparison, psis_loo, weighted_model_comparison  # noqa: F401
 from .checks import CheckSpec, PredictiveCheck, WeightedPredictiveCheck, marginal_checks, posterior_predictive_check, weighted_predictive_check  # noqa: F401
 from .validation import effective_sample_size_mcmc  # noqa: F401

@@ -15,11 +15,7 @@
 //                   (block aggregates first, k_rank_carry scans them in block order, then the final form), r2 = lo + hi + 1, the
 //                   normal score, and the scatter by cell index into the caller's row
 // Integer atomics only, and only where order cannot matter (counts, a maximum).  No floating-point atomics.
-#include "fg_engine_internal.h"
-#include "fg_diag_rank_plan.h"
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
+#include "fg_diag_rank_internal.h"
 
 __device__ __forceinline__ double rank_cell(const double *draws, u32 i, u32 C, long long d, long long j) {
     const u32 t = i / C, c = i - t * C;
@@ -260,31 +256,6 @@ __global__ __launch_bounds__(FG_RANK_RUN_THREADS) void k_rank_carry(int *bs, u32
     for (u32 b = b1; b > b0; --b) { const u32 v = be[b - 1]; be[b - 1] = rue; rue = v < rue ? v : rue; }
 }
 
-namespace {
-
-struct RankWork {                              // the workspace of one call: reused for every coordinate and both sorts
-    u64 *key[2] = { nullptr, nullptr };
-    u32 *idx[2] = { nullptr, nullptr };
-    u32 *table = nullptr, *hist = nullptr, *stat = nullptr, *be = nullptr;
-    int *bs = nullptr;
-    std::vector<void *> p;
-    ~RankWork() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    int alloc(T **out, size_t bytes, const char *what) {
-        if (hipMalloc((void **)out, bytes ? bytes : 1) != hipSuccess) { fg_set_error(std::string("fg_diag_rank: no device memory for ") + what); return FG_E_HIP; }
-        p.push_back(*out);
-        return FG_OK;
-    }
-    int init(const FgRankPlan &P) {
-        for (int i = 0; i < 2; ++i)
-            if (alloc(&key[i], P.b_keys, "the keys") || alloc(&idx[i], P.b_idx, "the cell indices")) return FG_E_HIP;
-        if (alloc(&table, P.b_table, "the scan table") || alloc(&hist, P.b_hist, "the digit histograms") || alloc(&stat, 2 * P.b_stat, "the counters") ||
-            alloc(&bs, P.b_carry / 2, "the run carries") || alloc(&be, P.b_carry / 2, "the run carries"))
-            return FG_E_HIP;
-        return FG_OK;
-    }
-};
-
 // the radix passes on (key[0], idx[0]); returns the buffer that holds the sorted pairs through *cur and adds the passes run
 int rank_sort(fg_engine *e, const FgRankPlan &P, RankWork &W, int *cur, long long *passes_run) {
     std::vector<u32> hist((size_t)FG_RANK_PASSES * FG_RANK_BINS);
@@ -313,6 +284,15 @@ int rank_sort(fg_engine *e, const FgRankPlan &P, RankWork &W, int *cur, long lon
     return FG_OK;
 }
 
+int rank_keys(fg_engine *e, const FgRankPlan &P, RankWork &W, const double *d_draws, int d, long long j) {
+    hipLaunchKernelGGL(k_rank_keys<false>, dim3(P.nb_key), dim3(FG_RANK_THREADS), 0, e->stream, d_draws, (u32)P.S, (u32)e->C, (long long)d, j, 0.0, W.key[0], W.idx[0], W.hist, W.stat,
+                       (double *)nullptr, 0ll, 0ll, (u64)0, (u64)0);
+    HIPCHK(hipGetLastError());
+    return FG_OK;
+}
+
+namespace {
+
 int rank_runs(fg_engine *e, const FgRankPlan &P, RankWork &W, int cur, FgRankRunArgs A) {
     A.keys = W.key[cur]; A.idx = W.idx[cur]; A.S = (u32)P.S; A.bs = W.bs; A.be = W.be;
     hipLaunchKernelGGL(k_rank_runs<false>, dim3(P.nb_run), dim3(FG_RANK_RUN_THREADS), 0, e->stream, A);
@@ -333,9 +313,7 @@ int rank_transform(fg_engine *e, const FgRankPlan &P, RankWork &W, const double 
         long long passes = 0;
         HIPCHK(hipMemsetAsync(W.hist, 0, P.b_hist, e->stream));
         HIPCHK(hipMemsetAsync(W.stat, 0, 2 * P.b_stat, e->stream));
-        hipLaunchKernelGGL(k_rank_keys<false>, dim3(P.nb_key), dim3(FG_RANK_THREADS), 0, e->stream, d_draws, S, C, (long long)d, j, 0.0, W.key[0], W.idx[0], W.hist, W.stat,
-                           (double *)nullptr, 0ll, 0ll, (u64)0, (u64)0);
-        HIPCHK(hipGetLastError());
+        if (int rc = rank_keys(e, P, W, d_draws, d, j)) return rc;
         int cur = 0;
         if (int rc = rank_sort(e, P, W, &cur, &passes)) return rc;
         FgRankRunArgs A;

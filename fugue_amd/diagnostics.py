@@ -411,3 +411,153 @@ def ess_bulk(chains, address: str) -> float:
 def ess_tail(chains, address: str) -> float:
     """Tail ESS of one f64 site of a ChainBatch: the smaller ESS of the 5 % and 95 % tail indicators."""
     return float(rank_diagnostics(chains, [address]).ess_tail[0])
+
+
+# ---- MCSE and ESS of the mean, the sd and quantiles, and the mad (`posterior::summarise_draws`; fg_diag_mcse.hip, DESIGN 3.24) ----
+MCSE_FIGURES = ("mean", "sd", "rhat", "ess_mean", "mcse_mean", "ess_sd", "ess_sq", "mcse_sd", "median", "mad")
+MCSE_PROB_FIGURES = ("q", "q7", "ess_quantile", "mcse_quantile", "th_lo", "th_hi")
+SUMMARY_COLUMNS = ("mean", "median", "sd", "mad", "q5", "q95", "rhat", "ess_bulk", "ess_tail", "mcse_mean", "mcse_sd", "mcse_q5", "mcse_median", "mcse_q95")
+
+
+@dataclass
+class McseDiagnostics:
+    """The Monte Carlo standard errors and effective sample sizes of `d` coordinates: the fixed figures (MCSE_FIGURES) one array entry
+    per coordinate, the figures per probability (MCSE_PROB_FIGURES) [d][len(probs)]; `counts` by name (engine.MCSE_COUNT_NAMES and
+    engine.MCSE_PROB_COUNT_NAMES).  The ESS is the project's estimator (the reference's Geyer sequence over whole chains) applied to the
+    rows `posterior` uses, not Stan's split-chain FFT estimate."""
+    names: list
+    n_draws: int
+    probs: np.ndarray
+    mean: np.ndarray
+    sd: np.ndarray
+    rhat: np.ndarray
+    ess_mean: np.ndarray
+    mcse_mean: np.ndarray
+    ess_sd: np.ndarray
+    ess_sq: np.ndarray
+    mcse_sd: np.ndarray
+    median: np.ndarray
+    mad: np.ndarray
+    q: np.ndarray
+    q7: np.ndarray
+    ess_quantile: np.ndarray
+    mcse_quantile: np.ndarray
+    th_lo: np.ndarray
+    th_hi: np.ndarray
+    counts: dict
+
+    @property
+    def d(self) -> int:
+        return len(self.names)
+
+    def _prob(self, p: float) -> int:
+        hit = np.flatnonzero(self.probs == float(p))
+        if hit.size == 0:
+            raise KeyError(p)
+        return int(hit[0])
+
+    def of(self, name: str) -> dict:
+        """the figures of one coordinate: the fixed ones as floats, those per probability as arrays [len(probs)]"""
+        if name not in self.names:
+            raise KeyError(name)
+        k = self.names.index(name)
+        out = {f: float(getattr(self, f)[k]) for f in MCSE_FIGURES}
+        out.update({f: np.asarray(getattr(self, f)[k]).copy() for f in MCSE_PROB_FIGURES})
+        return out
+
+    def at(self, figure: str, p: float) -> np.ndarray:
+        """one figure per probability (MCSE_PROB_FIGURES) at the probability `p` of the call: [d]"""
+        if figure not in MCSE_PROB_FIGURES:
+            raise KeyError(figure)
+        return np.asarray(getattr(self, figure))[:, self._prob(p)]
+
+    @classmethod
+    def from_result(cls, names, n_draws: int, res: dict) -> "McseDiagnostics":
+        from . import engine as E
+        return cls(names=list(names), n_draws=int(n_draws), probs=np.asarray(res["probs"], dtype=np.float64),
+                   counts={k: np.asarray(res[k]) for k in E.MCSE_COUNT_NAMES + E.MCSE_PROB_COUNT_NAMES},
+                   **{f: np.asarray(res[f]) for f in MCSE_FIGURES + MCSE_PROB_FIGURES})
+
+
+def _with_uploaded(x, addresses, device, call):
+    """upload the table of `x` to a throw-away engine of its chain count and run call(engine, buffer, n, d, names, n C) on it"""
+    from . import engine as E, workloads as W
+    table, names = _rank_table(x, addresses)
+    n, d, C_ = table.shape
+    eng = E.Engine(E.compile_model(W.normal_sites(1)), C_, seed=0, device=device)        # the calls want the engine's chain count only
+    buf = None
+    try:
+        buf = eng.upload(table)
+        return call(eng, buf, n, d, names, n * C_)
+    finally:
+        if buf is not None:
+            eng.device_free(buf)
+        eng.close()
+
+
+def mcse_diagnostics(x, addresses=None, probs=(0.05, 0.5, 0.95), device: int = 0) -> McseDiagnostics:
+    """MCSE and ESS of the mean, the standard deviation and the quantiles `probs` (at most 8), the median and the mad of stored draws:
+    `x` is a `ChainBatch` (its f64 sites, or the sites `addresses`) or an array [n][d][C].  The draws are uploaded and `Engine.diag_mcse`
+    runs on them on a throw-away engine; n x C must stay below 2^31."""
+    return _with_uploaded(x, addresses, device, lambda eng, buf, n, d, names, S: McseDiagnostics.from_result(names, S, eng.diag_mcse(buf, n, d, probs=probs)))
+
+
+def mcse_mean(chains, address: str) -> float:
+    """`posterior::mcse_mean` of one f64 site of a ChainBatch: sd / sqrt(ess_mean)."""
+    return float(mcse_diagnostics(chains, [address], probs=(0.5,)).mcse_mean[0])
+
+
+def mcse_sd(chains, address: str) -> float:
+    """`posterior::mcse_sd` of one f64 site of a ChainBatch (Kenney and Keeping's formula on the ESS of the squared centred draws)."""
+    return float(mcse_diagnostics(chains, [address], probs=(0.5,)).mcse_sd[0])
+
+
+def mcse_quantile(chains, address: str, prob: float) -> float:
+    """`posterior::mcse_quantile` of one f64 site of a ChainBatch at the probability `prob`."""
+    return float(mcse_diagnostics(chains, [address], probs=(float(prob),)).mcse_quantile[0, 0])
+
+
+def mcse_median(chains, address: str) -> float:
+    """`posterior::mcse_median`: `mcse_quantile` at 0.5."""
+    return mcse_quantile(chains, address, 0.5)
+
+
+def ess_mean(chains, address: str) -> float:
+    """`posterior::ess_mean` of one f64 site of a ChainBatch: the multi-chain ESS of its raw draws."""
+    return float(mcse_diagnostics(chains, [address], probs=(0.5,)).ess_mean[0])
+
+
+def ess_sd(chains, address: str) -> float:
+    """`posterior::ess_sd` of one f64 site of a ChainBatch: the ESS of |x - mean|."""
+    return float(mcse_diagnostics(chains, [address], probs=(0.5,)).ess_sd[0])
+
+
+def ess_quantile(chains, address: str, prob: float) -> float:
+    """`posterior::ess_quantile` of one f64 site of a ChainBatch: the ESS of the indicator x <= the order statistic at `prob`."""
+    return float(mcse_diagnostics(chains, [address], probs=(float(prob),)).ess_quantile[0, 0])
+
+
+def ess_median(chains, address: str) -> float:
+    """`posterior::ess_median`: `ess_quantile` at 0.5."""
+    return ess_quantile(chains, address, 0.5)
+
+
+def mad(chains, address: str) -> float:
+    """R's `mad` of one f64 site of a ChainBatch: 1.4826 times the median of |x - median| over all its draws."""
+    return float(mcse_diagnostics(chains, [address], probs=(0.5,)).mad[0])
+
+
+def summarise_draws(x, addresses=None, device: int = 0) -> dict:
+    """`posterior::summarise_draws`' default table of stored draws (`x` as for `mcse_diagnostics`): one row per site, a dict of the columns
+    SUMMARY_COLUMNS -- mean, median, sd, mad, q5, q95 (the interpolated type-7 quantiles), rhat (= rhat_rank), ess_bulk, ess_tail, then
+    mcse_mean, mcse_sd, mcse_q5, mcse_median, mcse_q95 -- from one `Engine.diag_rank` and one `Engine.diag_mcse` call on one upload."""
+    def call(eng, buf, n, d, names, S):
+        return names, RankDiagnostics.from_result(names, S, eng.diag_rank(buf, n, d, probs=(0.05, 0.95))), \
+            McseDiagnostics.from_result(names, S, eng.diag_mcse(buf, n, d, probs=(0.05, 0.5, 0.95)))
+    names, rk, mc = _with_uploaded(x, addresses, device, call)
+    out = {}
+    for k, name in enumerate(names):
+        out[name] = dict(mean=float(mc.mean[k]), median=float(mc.median[k]), sd=float(mc.sd[k]), mad=float(mc.mad[k]), q5=float(mc.q7[k, 0]), q95=float(mc.q7[k, 2]),
+                         rhat=float(rk.rhat_rank[k]), ess_bulk=float(rk.ess_bulk[k]), ess_tail=float(rk.ess_tail[k]), mcse_mean=float(mc.mcse_mean[k]),
+                         mcse_sd=float(mc.mcse_sd[k]), mcse_q5=float(mc.mcse_quantile[k, 0]), mcse_median=float(mc.mcse_quantile[k, 1]), mcse_q95=float(mc.mcse_quantile[k, 2]))
+    return out

@@ -86,6 +86,12 @@ RANK_WORD_NAMES = ("rhat_rank", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tai
 RANK_COUNT_NAMES = ("n_cells", "n_runs", "longest_run", "n_nan", "n_neg_inf", "n_pos_inf", "n_nan_folded", "n_passes")
 RANK_COUNTS = len(RANK_COUNT_NAMES)
 RANK_ROWS = 4
+# fg_diag_mcse's rows (include/fugue_amd.h): FG_MCSE_FIXED_WORDS doubles, then FG_MCSE_PROB_WORDS per probability; the counts likewise
+MCSE_WORD_NAMES = ("mean", "sd", "rhat", "ess_mean", "mcse_mean", "ess_sd", "ess_sq", "mcse_sd", "median", "mad")
+MCSE_PROB_WORD_NAMES = ("q", "q7", "ess_quantile", "mcse_quantile", "th_lo", "th_hi")
+MCSE_COUNT_NAMES = ("n_cells", "n_nan", "n_neg_inf", "n_pos_inf", "n_nan_folded", "n_passes")
+MCSE_PROB_COUNT_NAMES = ("k_p", "i_lo", "i_hi")
+MCSE_MAX_PROBS = 8
 
 # every symbol include/fugue_amd.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -119,6 +125,7 @@ ABI_SYMBOLS = [
     "fg_wpop_new", "fg_wpop_units", "fg_wpop_moments", "fg_wpop_quantiles", "fg_wpop_counts", "fg_wpop_free", "fg_wpop_checks_n_slots", "fg_wpop_checks", "fg_wpop_loglik",
     "fg_psis_words", "fg_psis_tail_len", "fg_psis_loo",
     "fg_diag_rank_words", "fg_diag_rank_transform", "fg_diag_rank_rhat_ess",
+    "fg_diag_mcse_words", "fg_mcse_quantile_ranks", "fg_diag_mcse_transform", "fg_diag_mcse",
     "fg_program_result", "fg_program_n_results", "fg_program_result_name", "fg_program_result_sites", "fg_result_eval",
     "fg_program_observe_name", "fg_program_observe_vtype", "fg_program_observe_dist", "fg_predict_eval",
     "fg_abc_distance", "fg_abc_mixture", "fg_abc_new", "fg_abc_free", "fg_abc_round_prior", "fg_abc_stage_begin", "fg_abc_round_stage",
@@ -322,6 +329,10 @@ def lib():
     L.fg_diag_rank_words.argtypes = []
     L.fg_diag_rank_transform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, dp, i64p]
     L.fg_diag_rank_rhat_ess.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int64, dp, i64p]
+    L.fg_diag_mcse_words.argtypes = [C.c_int]
+    L.fg_mcse_quantile_ranks.argtypes = [C.c_int64, C.c_double, C.c_double, i64p, i64p]
+    L.fg_diag_mcse_transform.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, vp, vp, dp, dp, i64p]
+    L.fg_diag_mcse.argtypes = [vp, vp, C.c_int, C.c_int, dp, C.c_int, C.c_int64, dp, i64p]
     L.fg_pf_new.argtypes = [C.c_int, C.c_int64, C.c_int64, C.POINTER(fg_pf_params), C.POINTER(vp)]
     L.fg_pf_set_sig_obs.argtypes = [vp, C.c_int64, C.c_double]
     L.fg_pf_run.argtypes = [vp, dp, C.c_int64, C.c_int, dp, dp, ip, dp, dp]
@@ -378,6 +389,14 @@ def _check(rc: int):
 
 def _dp(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def mcse_quantile_ranks(S: int, p: float, ess: float):
+    """`fg_mcse_quantile_ranks`: the 0-based positions (i_lo, i_hi) of mcse_quantile's two order statistics among S sorted cells, from the
+    15.87 % and 84.13 % points of Beta(ess p + 1, ess (1 - p) + 1).  Host only: no device and no engine."""
+    lo, hi = C.c_int64(-1), C.c_int64(-1)
+    _check(lib().fg_mcse_quantile_ranks(int(S), float(p), float(ess), C.byref(lo), C.byref(hi)))
+    return int(lo.value), int(hi.value)
 
 
 def hmc_config(n_leapfrog=16, target_accept=0.8, init_step_size=None, finite_diff_eps=1e-5, adapt_mass=False,
@@ -1045,6 +1064,68 @@ class Engine:
         out = {name: words[:, j].copy() for j, name in enumerate(RANK_WORD_NAMES)}
         out.update({name: counts[:, j].copy() for j, name in enumerate(RANK_COUNT_NAMES)})
         out["words"], out["counts"] = words, counts
+        return out
+
+    def diag_mcse_transform(self, d_draws: int, n: int, d: int, mean, j0: int = 0, n_j: Optional[int] = None, probs=(0.05, 0.5, 0.95), d_out: Optional[int] = None,
+                            sorted_cells: bool = False) -> dict:
+        """`fg_diag_mcse_transform` (fg_diag_mcse.hip): the rows |x - mean|, (x - mean)^2 and I_p per probability of coordinates
+        [j0, j0 + n_j) of the stored draws `d_draws` [n][d][C] on the device, centred at `mean` [n_j].  -> `out` [n][(2 + len(probs)) n_j][C]
+        (downloaded, or None when the caller's device buffer `d_out` received them), `median` [n_j], `mad` [n_j], `counts`
+        [n_j][6 + 3 len(probs)] and the counts by name (MCSE_COUNT_NAMES; `k_p` [n_j][len(probs)]); with `sorted_cells` also `sorted`
+        [n_j][n C], the sorted cells.  Reads engine state and changes none."""
+        n_j = int(d) - int(j0) if n_j is None else n_j
+        for name, v in (("n", n), ("d", d), ("j0", j0), ("n_j", n_j)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"diag_mcse_transform: {name} must be an integer, not {type(v).__name__}")
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        nb, npb = max(int(n_j), 1), len(pr)
+        if mean.size != nb:
+            raise ValueError(f"diag_mcse_transform: {mean.size} means for {nb} coordinates")
+        rows = 2 + npb
+        cells = max(int(n), 1) * nb * self.C
+        median, mad = np.zeros(nb), np.zeros(nb)
+        counts = np.zeros((nb, len(MCSE_COUNT_NAMES) + len(MCSE_PROB_COUNT_NAMES) * npb), dtype=np.int64)
+        own = self.device_alloc(8 * rows * cells) if d_out is None else None
+        d_sorted = self.device_alloc(8 * cells) if sorted_cells else None
+        try:
+            _check(lib().fg_diag_mcse_transform(self.h, d_draws, int(n), int(d), int(j0), int(n_j), _dp(mean), _dp(pr), npb, own if d_out is None else d_out, d_sorted,
+                                                _dp(median), _dp(mad), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+            out = {name: counts[:, j].copy() for j, name in enumerate(MCSE_COUNT_NAMES)}
+            out["k_p"] = counts[:, len(MCSE_COUNT_NAMES)::len(MCSE_PROB_COUNT_NAMES)].copy()
+            out.update(out=self.download(own, (int(n), rows * int(n_j), self.C)) if own is not None else None, median=median, mad=mad, counts=counts, probs=pr)
+            if d_sorted is not None:
+                out["sorted"] = self.download(d_sorted, (int(n_j), int(n) * self.C))
+            return out
+        finally:
+            for b in (own, d_sorted):
+                if b is not None:
+                    self.device_free(b)
+
+    def diag_mcse(self, d_draws: int, n: int, d: int, probs=(0.05, 0.5, 0.95), max_out_bytes: int = 0) -> dict:
+        """`fg_diag_mcse` (fg_diag_mcse.hip): the Monte Carlo standard errors and effective sample sizes of the mean, the standard deviation
+        and the quantiles `probs` (at most 8), the median and the mad of every coordinate of the stored draws `d_draws` [n][d][C] on the
+        device (C this engine's chains).  -> the fixed figures by name (MCSE_WORD_NAMES, [d] doubles each), the figures per probability by
+        name (MCSE_PROB_WORD_NAMES, [d][len(probs)] each), the counts by name (MCSE_COUNT_NAMES [d], MCSE_PROB_COUNT_NAMES
+        [d][len(probs)]), `words`, `counts`, `probs`.  `max_out_bytes` bounds the rows and sorted keys held at a time (0: 1 GiB); the
+        figures do not depend on it.  Reads engine state and changes none."""
+        for name, v in (("n", n), ("d", d), ("max_out_bytes", max_out_bytes)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"diag_mcse: {name} must be an integer, not {type(v).__name__}")
+        pr = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+        npb, nf, ncf = len(pr), len(MCSE_WORD_NAMES), len(MCSE_COUNT_NAMES)
+        npw, npc = len(MCSE_PROB_WORD_NAMES), len(MCSE_PROB_COUNT_NAMES)
+        L = lib()
+        db = max(int(d), 1)
+        words = np.zeros((db, nf + npw * max(npb, 1)), dtype=np.float64)
+        counts = np.zeros((db, ncf + npc * max(npb, 1)), dtype=np.int64)
+        _check(L.fg_diag_mcse(self.h, d_draws, int(n), int(d), _dp(pr), npb, int(max_out_bytes), _dp(words), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        assert words.shape[1] == int(L.fg_diag_mcse_words(npb))
+        out = {name: words[:, j].copy() for j, name in enumerate(MCSE_WORD_NAMES)}
+        out.update({name: words[:, nf + j::npw].copy() for j, name in enumerate(MCSE_PROB_WORD_NAMES)})
+        out.update({name: counts[:, j].copy() for j, name in enumerate(MCSE_COUNT_NAMES)})
+        out.update({name: counts[:, ncf + j::npc].copy() for j, name in enumerate(MCSE_PROB_COUNT_NAMES)})
+        out["words"], out["counts"], out["probs"] = words, counts, pr
         return out
 
     def ppc_stream(self, n_total: int, vtypes: Sequence[int], checks: Sequence) -> "PpcStream":

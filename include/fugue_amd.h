@@ -862,6 +862,49 @@ int     fg_diag_rank_transform(fg_engine *e, const double *d_draws, int n, int d
  * block; h_figures [d][FG_RANK_WORDS], h_counts [d][FG_RANK_COUNTS].  The figures do not depend on the blocks. */
 int     fg_diag_rank_rhat_ess(fg_engine *e, const double *d_draws, int n, int d, double p_lo, double p_hi, int64_t max_out_bytes,
                               double *h_figures, int64_t *h_counts);
+/* ------------------------------------------------------------------ MCSE and ESS of the mean, the sd and quantiles
+ * What `posterior::summarise_draws` reports next to a mean, a standard deviation and a quantile -- mcse_mean, mcse_sd, mcse_quantile,
+ * ess_mean, ess_sd, ess_quantile (ess_median: p = 0.5) and mad; the reference has none of it -- of stored draws d_draws [n][d][C] on the
+ * device (fg_diag_mcse.hip; the rule, the Beta inverse and the limits: fg_diag_mcse_plan.h and DESIGN 3.24).  Per coordinate: mean,
+ * sd, rhat and ess_mean are fg_diag_rhat_ess's own figures of the raw draws; the S = n C pooled cells are sorted as fg_diag_rank_* sort
+ * them (same key: -0.0 and +0.0 tie, all NaN tie above +inf); the rows |x - mean|, (x - mean)^2 and, per probability p, I_p = 1 where
+ * x <= sorted[floor((S - 1) p)] go through the combination of fg_diag_rhat_ess (r_hat_from_f64_chains, diagnostics.rs:262-304;
+ * ess_from_chains, mcmc_utils.rs:253-339) in the original [n][.][C] layout; mcse_sd is Kenney and Keeping's formula, mcse_quantile half
+ * the distance of the order statistics at the 15.87 % and 84.13 % points of Beta(ess p + 1, ess (1 - p) + 1), as `posterior` has them.
+ * The ESS is the project's estimator (no split chains, Geyer's sequence as the reference truncates it), not Stan's FFT estimator.
+ * A row of FG_MCSE_FIXED_WORDS + FG_MCSE_PROB_WORDS n_probs doubles per coordinate:
+ *   0 mean  1 sd  2 rhat  3 ess_mean  4 mcse_mean = sd / sqrt(ess_mean)  5 ess_sd (of |x - mean|)  6 ess_sq (of (x - mean)^2)  7 mcse_sd
+ *   8 median  9 mad = 1.4826 median |x - median|;  then per probability, in the order given:
+ *   q = sorted[k_p]  q7 (the interpolated type-7 quantile)  ess_quantile (of I_p)  mcse_quantile = (th_hi - th_lo) / 2
+ *   th_lo = sorted[i_lo]  th_hi = sorted[i_hi]
+ * and a row of FG_MCSE_FIXED_COUNTS + FG_MCSE_PROB_COUNTS n_probs integers:
+ *   0 S  1 NaN cells  2 -inf cells  3 +inf cells  4 NaN folded cells  5 radix passes run (both sorts);  per probability: k_p  i_lo  i_hi
+ * (i_lo = i_hi = -1 and th_lo, th_hi, mcse_quantile NaN where ess_quantile is not finite or not positive).  +-inf cells are ordinary
+ * values of the sort; what passes through the mean follows IEEE.  A NaN cell makes every word of its coordinate NaN; NaN folded cells
+ * (median = +-inf) make mad NaN.  This engine's chains only.  The calls are synchronous, read engine state and change none; every
+ * argument is checked before the device is looked for.  FG_E_BAD_ARG: a null pointer, n < 1, d outside [1, 65535], a block outside
+ * [0, d), n_probs outside [1, 8], a probability outside [0, 1], max_out_bytes < 0; FG_E_LIMIT: n C >= 2^31. */
+#define FG_MCSE_MAX_PROBS 8
+#define FG_MCSE_FIXED_WORDS 10   /* mean sd rhat ess_mean mcse_mean ess_sd ess_sq mcse_sd median mad */
+#define FG_MCSE_PROB_WORDS 6     /* q q7 ess_quantile mcse_quantile th_lo th_hi */
+#define FG_MCSE_FIXED_COUNTS 6   /* S, NaN, -inf, +inf cells, NaN folded cells, radix passes run (both sorts) */
+#define FG_MCSE_PROB_COUNTS 3    /* k_p i_lo i_hi */
+int     fg_diag_mcse_words(int n_probs);                       /* the figures' row length; FG_E_BAD_ARG outside [1, 8] */
+/* The 0-based positions of mcse_quantile's two order statistics among S sorted cells: i_lo = max(floor(a1 S), 1) - 1 and
+ * i_hi = min(ceil(a2 S), S) - 1 with a1, a2 the 0.15865525393145707 and 0.8413447460685429 points of Beta(ess p + 1, ess (1 - p) + 1).
+ * Host only, no device.  FG_E_BAD_ARG: a null pointer, S < 1, p outside [0, 1], ess not finite or not positive. */
+int     fg_mcse_quantile_ranks(int64_t S, double p, double ess, int64_t *i_lo, int64_t *i_hi);
+/* The rows alone: coordinates [j0, j0 + n_j) of d_draws [n][d][C], centred at h_mean [n_j], -> d_out [n][(2 + n_probs) n_j][C] (row
+ * (2 + n_probs) k + i: row i of coordinate j0 + k; rows |c|, c c, I_p ...), ready for fg_diag_rhat_ess; d_sorted_or_null [n_j][S] the
+ * sorted cells as doubles; h_median [n_j]; h_mad [n_j]; h_counts [n_j][FG_MCSE_FIXED_COUNTS + FG_MCSE_PROB_COUNTS n_probs] (i_lo and
+ * i_hi are -1 here: they need the figures). */
+int     fg_diag_mcse_transform(fg_engine *e, const double *d_draws, int n, int d, int j0, int n_j, const double *h_mean, const double *h_probs,
+                               int n_probs, double *d_out, double *d_sorted_or_null, double *h_median, double *h_mad, int64_t *h_counts);
+/* Every figure, block by block (a block: the coordinates whose rows and sorted keys stay under max_out_bytes, at least one; 0 = 1 GiB);
+ * h_figures [d][fg_diag_mcse_words(n_probs)], h_counts [d][FG_MCSE_FIXED_COUNTS + FG_MCSE_PROB_COUNTS n_probs].  The figures do not
+ * depend on the blocks. */
+int     fg_diag_mcse(fg_engine *e, const double *d_draws, int n, int d, const double *h_probs, int n_probs, int64_t max_out_bytes,
+                     double *h_figures, int64_t *h_counts);
 /* ------------------------------------------------------------------ bootstrap particle filter bank
  * WasmParticleFilter (crates/fugue-wasm/src/pf.rs): a 1-D bootstrap filter on the random-walk model x_0 ~ N(0, prior_sig),
  * x_t = x_{t-1} + N(0, sig_step), y_t ~ N(x_t, sig_obs), systematic resampling when ESS / n < ess_threshold, the running log-evidence.

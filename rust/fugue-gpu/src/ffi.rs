@@ -250,6 +250,13 @@ extern "C" {
                                   d_out: *mut f64, d_rank2_or_null: *mut u32, h_median: *mut f64, h_counts: *mut i64) -> c_int;
     pub fn fg_diag_rank_rhat_ess(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, p_lo: f64, p_hi: f64, max_out_bytes: i64,
                                  h_figures: *mut f64, h_counts: *mut i64) -> c_int;
+    // ---- MCSE and ESS of the mean, the sd and quantiles of stored draws, and the mad (fg_diag_mcse.hip)
+    pub fn fg_diag_mcse_words(n_probs: c_int) -> c_int;
+    pub fn fg_mcse_quantile_ranks(S: i64, p: f64, ess: f64, i_lo: *mut i64, i_hi: *mut i64) -> c_int;
+    pub fn fg_diag_mcse_transform(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, j0: c_int, n_j: c_int, h_mean: *const f64, h_probs: *const f64,
+                                  n_probs: c_int, d_out: *mut f64, d_sorted_or_null: *mut f64, h_median: *mut f64, h_mad: *mut f64, h_counts: *mut i64) -> c_int;
+    pub fn fg_diag_mcse(e: *mut fg_engine, d_draws: *const f64, n: c_int, d: c_int, h_probs: *const f64, n_probs: c_int, max_out_bytes: i64,
+                        h_figures: *mut f64, h_counts: *mut i64) -> c_int;
     // ---- bootstrap particle filter bank (fg_pf.hip): crates/fugue-wasm/src/pf.rs, B filters at once
     pub fn fg_pf_new(device_ordinal: c_int, n_particles: i64, n_filters: i64, params: *const fg_pf_params, out: *mut *mut fg_pf) -> c_int;
     pub fn fg_pf_set_sig_obs(pf: *mut fg_pf, filter: i64, sig_obs: f64) -> c_int;
