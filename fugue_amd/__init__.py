@@ -23,5 +23,6 @@ from .abc import (ABC_SMC_DEFAULT_ATTEMPT_FACTOR, ABCError, ABCSMCConfig, ABCSMC
                   SummaryStatsDistance, abc_rejection, abc_scalar_summary, abc_smc, abc_smc_weighted)
 from .pf import BankStep, PFRun, ParticleFilter, ParticleFilterBank, StepOut  # noqa: F401
 from .grid import GridSurface, LogJointGrid, log_joint_grid, log_joint_surface  # noqa: F401
+from .gibbs import GibbsSweep, SweepOutput, gibbs_chain, hmc_gibbs_chain, site_support  # noqa: F401
 from .vi import (GuideError, MeanFieldGuide, ParamCoord, Support, VIConfig, VIResult, VariationalParam, elbo_gradient_fd,  # noqa: F401
                  elbo_with_guide, estimate_elbo, optimize_meanfield_vi, optimize_meanfield_vi_with_config)

@@ -834,17 +834,22 @@ int fg_engine_set_stream(fg_engine *e, void *hip_stream) {
 int64_t fg_engine_n_chains(const fg_engine *e) { return e ? e->C : 0; }
 void *fg_engine_values_device(fg_engine *e) { return e ? (void *)e->d_values : nullptr; }
 
-int fg_engine_set_values(fg_engine *e, const void *h) {
-    NEED_ENGINE(e);
-    if (!h) return FG_E_BAD_ARG;
-    HIPCHK(hipMemcpyAsync(e->d_values, h, (size_t)e->S * e->C * 8, hipMemcpyHostToDevice, e->stream));
-    // a live sampler session caches the log-joint of its current state: re-score it at the new values (what the reference's
-    // callers do after editing a trace: crates/fugue-wasm/src/mh.rs:239-255 runs ScoreGivenTrace)
+// a live sampler session caches the log-joint of its current state: re-score it at the engine's values (what the reference's
+// callers do after editing a trace: crates/fugue-wasm/src/mh.rs:239-255 runs ScoreGivenTrace).  Asynchronous on the engine's stream;
+// shared by fg_engine_set_values and fg_gibbs_sweep (fg_gibbs.hip).
+int fg_internal_rescore_sessions(fg_engine *e) {
     for (double *lj : { e->mh_ready ? e->M.lw : (double *)nullptr, e->hmc_ready ? e->H.lj : (double *)nullptr })
         if (lj && (e->gt || fg_jit_log_joint_launch(e, e->d_acc, lj, false) != FG_OK))
             FG_LAUNCH_GT(e, k_log_joint, dim3((unsigned)((e->C + e->tw - 1) / e->tw)), dim3(e->tw), e->lds_score, e->stream, e->P, e->X, e->d_acc,
                                    (double *)nullptr, lj);
     HIPCHK(hipGetLastError());
+    return FG_OK;
+}
+int fg_engine_set_values(fg_engine *e, const void *h) {
+    NEED_ENGINE(e);
+    if (!h) return FG_E_BAD_ARG;
+    HIPCHK(hipMemcpyAsync(e->d_values, h, (size_t)e->S * e->C * 8, hipMemcpyHostToDevice, e->stream));
+    if (int rc = fg_internal_rescore_sessions(e)) return rc;
     HIPCHK(hipStreamSynchronize(e->stream));
     return FG_OK;
 }

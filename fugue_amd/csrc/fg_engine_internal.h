@@ -210,6 +210,7 @@ int fg_hmc_interp_launch(fg_engine *e, int iter0, int n, int welford_on, double 
 
 // fg_engine.hip internals used by fg_state.hip
 extern "C" {
+int fg_internal_rescore_sessions(fg_engine *e);   // the cached log-joint of a live MH / HMC session at the engine's values (fg_gibbs.hip)
 int fg_internal_hmc_alloc(fg_engine *e, bool mass);
 void fg_internal_hmc_set_cfg(fg_engine *e, const fg_hmc_config *cfg);
 int fg_internal_hmc_step(fg_engine *e, int n_transitions, double *d_draws, double *d_pos_all, double *d_info);

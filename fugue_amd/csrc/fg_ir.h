@@ -151,5 +151,6 @@ enum : uint32_t {
     FG_RNG_PREDICT = 9,      // replicated data of the observe statements (fg_predict.hip): iteration word = the draw's index in the sampling phase
     FG_RNG_ABC = 10,         // proposals of weighted ABC-SMC (fg_abc.hip): chain word = chain offset + attempt, iteration word = the stage
     FG_RNG_PF = 11,          // particle filter bank (fg_pf.hip): key = the filter's seed, chain word = particle, iteration word = time (0: the initial draw)
-    FG_RNG_PF_RESAMPLE = 12  // ... its systematic-resampling uniform: the first of (seed, 0, time, 12)
+    FG_RNG_PF_RESAMPLE = 12, // ... its systematic-resampling uniform: the first of (seed, 0, time, 12)
+    FG_RNG_GIBBS = 13        // exact Gibbs moves of the discrete sites (fg_gibbs.hip): iteration word = the sweep index, block i = the pick of listed site i
 };

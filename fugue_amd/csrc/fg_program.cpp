@@ -988,6 +988,29 @@ int fg_program_site_vtype(const fg_program *p, int j) {
     if (j < 0 || j >= (int)p->site_vtype.size()) return FG_ERR_ADDRESS_NOT_FOUND;
     return p->site_vtype[j];
 }
+// the support of a discrete site where constants alone state it (what fg_gibbs_new enumerates): the bounds the compiled statement scores with
+int fg_program_site_support(const fg_program *p, int j, int64_t *lo, int64_t *hi) {
+    NEED_FINAL(p);
+    if (j < 0 || j >= (int)p->sorted_stmt.size() || !lo || !hi) { fg_set_error("fg_program_site_support: a site outside [0, S) or a null pointer"); return FG_E_BAD_ARG; }
+    const FgStmt &s = p->stmts[(size_t)p->sorted_stmt[(size_t)j]];
+    if (s.vtype == FG_F64) return 0;
+    auto constant = [&](size_t k) { return p->nodes[(size_t)s.params[k]].is_const; };
+    long long a = 0, b = -1;
+    if (s.dist == FG_BERNOULLI) b = 1;                                      // whatever p is
+    else if (s.dist == FG_CATEGORICAL) b = (long long)s.params.size() - 1;  // the number of probabilities is the program's, not a value
+    else if (s.dist == FG_DISCRETEUNIFORM) {
+        if (!constant(0) || !constant(1)) return 0;
+        a = fg_f2i_sat(p->nodes[(size_t)s.params[0]].cval); b = fg_f2i_sat(p->nodes[(size_t)s.params[1]].cval);   // compile_stmt's bounds
+        if (s.exact_bounds) { a = s.lo; b = s.hi; }
+    } else if (s.dist == FG_BINOMIAL) {
+        unsigned long long n = 0;
+        if (!constant(0) || !fg_binomial_n(p->nodes[(size_t)s.params[0]].cval, &n) || n > (unsigned long long)FG_I64_MAX) return 0;
+        b = (long long)n;
+    } else return 0;
+    if (b < a) return 0;
+    *lo = a; *hi = b;
+    return 1;
+}
 int fg_program_site_of_handle(const fg_program *p, int h) {
     NEED_FINAL(p);
     if (h < 0 || h >= (int)p->handle_to_sorted.size()) return FG_ERR_ADDRESS_NOT_FOUND;

@@ -132,6 +132,8 @@ ABI_SYMBOLS = [
     "fg_abc_stage_end", "fg_abc_last_round", "fg_abc_get_population", "fg_abc_set_population",
     "fg_pf_new", "fg_pf_set_sig_obs", "fg_pf_run", "fg_pf_step", "fg_pf_log_evidence", "fg_pf_t", "fg_pf_positions", "fg_pf_free",
     "fg_grid_new", "fg_grid_eval", "fg_grid_summary", "fg_grid_marginals", "fg_grid_mixture", "fg_grid_count", "fg_grid_free",
+    "fg_program_site_support", "fg_gibbs_new", "fg_gibbs_n_sites", "fg_gibbs_n_cells", "fg_gibbs_layout", "fg_gibbs_sweep", "fg_gibbs_count", "fg_gibbs_seek",
+    "fg_gibbs_stats", "fg_gibbs_probs", "fg_gibbs_free",
 ]
 
 _lib = None
@@ -352,6 +354,20 @@ def lib():
     L.fg_grid_count.argtypes = [vp]
     L.fg_grid_free.restype = None
     L.fg_grid_free.argtypes = [vp]
+    L.fg_program_site_support.argtypes = [vp, C.c_int, i64p, i64p]
+    L.fg_gibbs_new.argtypes = [vp, ip, C.c_int, C.POINTER(vp)]
+    L.fg_gibbs_n_sites.argtypes = [vp]
+    L.fg_gibbs_n_cells.restype = C.c_int64
+    L.fg_gibbs_n_cells.argtypes = [vp]
+    L.fg_gibbs_layout.argtypes = [vp, ip, i64p, ip, i64p]
+    L.fg_gibbs_sweep.argtypes = [vp, C.c_int, ip, C.c_int, vp, vp, vp]
+    L.fg_gibbs_count.restype = C.c_int64
+    L.fg_gibbs_count.argtypes = [vp]
+    L.fg_gibbs_seek.argtypes = [vp, C.c_int64]
+    L.fg_gibbs_stats.argtypes = [vp, i64p]
+    L.fg_gibbs_probs.argtypes = [vp, dp, i64p]
+    L.fg_gibbs_free.restype = None
+    L.fg_gibbs_free.argtypes = [vp]
     L.fg_diag_cells_f64.argtypes = [vp, vp, C.c_int, C.c_int, ip, ip, C.c_int, vp]
     L.fg_hmc_last_kernel.restype = C.c_char_p
     L.fg_hmc_last_kernel.argtypes = [vp]
@@ -628,6 +644,13 @@ class Engine:
         `LogJointGrid`), sites by address or sorted index.  Close it before the engine."""
         from .grid import LogJointGrid
         return LogJointGrid(self, site_a, a_values, site_b, b_values, base_chunk)
+
+    def gibbs(self, sites=None):
+        """`fg_gibbs_new`: the exact Gibbs transition of this engine's chains over the discrete sites `sites` (addresses or sorted
+        indices, in visiting order; None: every discrete site whose finite support constants state) -- fugue_amd/gibbs.py:
+        `GibbsSweep`.  Close it before the engine."""
+        from .gibbs import GibbsSweep
+        return GibbsSweep(self, sites)
 
     def result_eval(self, d_draws: Optional[int], n: int, rows: Optional[Sequence[int]] = None, out: Optional[int] = None) -> int:
         """`fg_result_eval`: the model's return value for every draw and chain of the device buffer d_draws [n][n_rows][C] (row j =

@@ -81,6 +81,8 @@ class ChainBatch:
     predictive: Optional[np.ndarray] = None                   # [n_samples][n_sel][n_chains] int64 cells like `cells`: replicated data, draw t from stream (seed, chain, t, 9)
     log_likelihood: Optional[np.ndarray] = None               # pointwise=True: [n_samples][n_sel][n_chains] float64, log p(observed value | draw) per observe statement
     observe_values: Dict[str, Optional[float]] = field(default_factory=dict)   # every observe address -> the observed value the model states (a literal or a data element), None where it reads a site; filled whatever `predictive` is
+    gibbs_probs: Optional[Dict[str, np.ndarray]] = None       # hmc_gibbs_chain / gibbs_chain: address of a swept site -> [K], the Rao-Blackwell estimate of P(site = lo + k | data) over the sampling sweeps
+    gibbs_stats: Optional[Dict[str, np.ndarray]] = None       # ... and lo, K, n, moved, stuck, nan_cells, neg_inf_cells per swept site (`sites`: their addresses)
 
     def get_predictive(self, address: str) -> np.ndarray:     # [n_samples][n_chains]: float64 for an f64 observe site, int64 otherwise
         if self.predictive is None or address not in self.predictive_names:

@@ -966,6 +966,49 @@ int  fg_grid_marginals(fg_grid *g, double *h_log_marg_a, double *h_log_marg_b); 
 int  fg_grid_mixture(fg_grid *g, double *h_log_mix, int64_t *n_mixed, int64_t *n_skipped);
 int64_t fg_grid_count(const fg_grid *g);                       /* grid.rs:48-67: bases that have arrived (-1 for a null handle) */
 void fg_grid_free(fg_grid *g);                                 /* grid.rs:22-69 */
+/* ------------------------------------------------------------------ exact Gibbs moves of the discrete sites
+ * hmc.rs:68-71: HMC moves the f64 sites only and holds every discrete site at its prior draw ("compose with `mh` to also move
+ * discrete sites").  A sweep is that composition with the exact conditional in place of a blind proposal: for every chain and every
+ * listed site, in list order, the trace is scored (the run fg_log_joint does, bit for bit) at every value of the site's finite
+ * support, the scores are normalised and the site's new value is drawn from them with the (i + 1)-th uniform of the stream (seed,
+ * chain_offset + chain, sweep index, 13).  The rule, the summation orders and the refusals: fg_gibbs_plan.h, DESIGN 3.25.  Chain c's
+ * sweep t gives the same bits alone or among any number of chains, under any cut of the chains into engines, in one call of several
+ * sweeps or in several calls.  The conditional probabilities are summed per (cell, chain) -- cell = cell0 of the site + the value's
+ * index -- and pooled over the chains on a fixed tree: the Rao-Blackwell estimate of P(site = value | data).  Asynchronous on the
+ * engine's stream unless a host pointer is written.  Free the handle before its engine. */
+#define FG_GIBBS_K_CAP 4096          /* values of one site's support */
+#define FG_GIBBS_COUNTS 4            /* per site: moved, stuck, nan_cells, neg_inf_cells */
+typedef struct fg_gibbs fg_gibbs;
+/* hmc.rs:68-71: the support of sorted site `site` where constants alone state it: returns 1 and [*lo, *hi] for Bernoulli [0, 1],
+ * Categorical of K probabilities [0, K - 1] (whatever their values), DiscreteUniform with constant bounds lo <= hi, Binomial with a
+ * constant valid n [0, n]; 0 otherwise (Poisson, f64 sites, bounds that read a site; *lo and *hi are left alone).  FG_E_BAD_ARG: a
+ * site outside [0, S), a null pointer. */
+int  fg_program_site_support(const fg_program *p, int site, int64_t *lo, int64_t *hi);
+/* hmc.rs:68-71: h_sites [n_sites] sorted site indices in visiting order; n_sites == 0: every site for which fg_program_site_support
+ * returns 1 with at most FG_GIBBS_K_CAP values, in site order.  Arguments are checked before the device is looked for.  FG_E_BAD_ARG
+ * (the message names the site): a site that is not discrete, a site without a finite constant support, a site listed twice,
+ * n_sites < 0, a null pointer, an empty resulting list.  FG_E_LIMIT: a listed site with more than FG_GIBBS_K_CAP values; a program
+ * whose tile lives in global memory. */
+int  fg_gibbs_new(fg_engine *e, const int32_t *h_sites, int n_sites, fg_gibbs **out);
+int  fg_gibbs_n_sites(const fg_gibbs *g);                      /* hmc.rs:68-71: listed sites G (FG_E_BAD_ARG for a null handle) */
+int64_t fg_gibbs_n_cells(const fg_gibbs *g);                   /* hmc.rs:68-71: the sum of their K (-1 for a null handle) */
+/* hmc.rs:68-71: per listed site, any may be NULL: h_site [G], h_lo [G], h_K [G], h_cell0 [G] */
+int  fg_gibbs_layout(const fg_gibbs *g, int32_t *h_site, int64_t *h_lo, int32_t *h_K, int64_t *h_cell0);
+/* hmc.rs:68-71: n_sweeps sweeps with the sweep indices count, count + 1, ...; one launch each.  d_rec (device, may be NULL)
+ * [n_sweeps][n_rec][C]: the 8-byte cells of the sites h_rec_sites (any sites of the program) after each sweep.  d_scores and d_cond
+ * (device, either may be NULL) [cells][C]: the scores and the conditional probabilities of the call's last sweep; the cells of a stuck
+ * site hold NaN in d_cond.  After the last sweep the cached log-joint of a live HMC / MH session is re-scored as fg_engine_set_values
+ * does.  FG_E_BAD_ARG: n_sweeps < 0, n_rec < 0, a recorded site outside [0, S), d_rec without sites; FG_E_LIMIT: the sweep index would
+ * pass 2^32. */
+int  fg_gibbs_sweep(fg_gibbs *g, int n_sweeps, const int32_t *h_rec_sites, int n_rec, int64_t *d_rec, double *d_scores, double *d_cond);
+int64_t fg_gibbs_count(const fg_gibbs *g);                     /* hmc.rs:68-71: the sweep index of the next sweep (-1 for a null handle) */
+int  fg_gibbs_seek(fg_gibbs *g, int64_t t);                    /* hmc.rs:68-71: sets it; FG_E_BAD_ARG outside [0, 2^32) */
+/* hmc.rs:68-71: h_counts [G][FG_GIBBS_COUNTS] = moved, stuck, nan_cells, neg_inf_cells summed over the chains and the sweeps run */
+int  fg_gibbs_stats(fg_gibbs *g, int64_t *h_counts);
+/* hmc.rs:68-71: h_mean [cells] = the tree-pooled probability sums divided by the contributing (sweep, chain) pairs of the cell's site
+ * (NaN when there is none), h_n [G] = those pairs (sweeps run x C - stuck); either may be NULL.  FG_E_STATE before any sweep has run. */
+int  fg_gibbs_probs(fg_gibbs *g, double *h_mean, int64_t *h_n);
+void fg_gibbs_free(fg_gibbs *g);                               /* hmc.rs:68-71 */
 /* RCCL communicator of the ranks of one run (one process per GPU): rank 0 obtains a 128-byte id (ncclGetUniqueId), the
  * host distributes it by any means, every rank calls fg_comm_init.  RCCL is bound at run time (librccl.so). */
 int fg_comm_unique_id(void *out_128_bytes);

@@ -15,6 +15,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fg_abc { _p: [u8; 0] }
 #[repr(C)] pub struct fg_pf { _p: [u8; 0] }
 #[repr(C)] pub struct fg_grid { _p: [u8; 0] }
+#[repr(C)] pub struct fg_gibbs { _p: [u8; 0] }
 
 pub const FG_E_NO_DEVICE: c_int = -1;
 pub const FG_E_HIP: c_int = -2;
@@ -277,6 +278,18 @@ extern "C" {
     pub fn fg_grid_mixture(g: *mut fg_grid, h_log_mix: *mut f64, n_mixed: *mut i64, n_skipped: *mut i64) -> c_int;
     pub fn fg_grid_count(g: *const fg_grid) -> i64;
     pub fn fg_grid_free(g: *mut fg_grid);
+    // ---- exact Gibbs moves of the discrete sites (fg_gibbs.hip): src/inference/hmc.rs:68-71, "compose with `mh` to also move discrete sites"
+    pub fn fg_program_site_support(p: *const fg_program, site: c_int, lo: *mut i64, hi: *mut i64) -> c_int;
+    pub fn fg_gibbs_new(e: *mut fg_engine, h_sites: *const i32, n_sites: c_int, out: *mut *mut fg_gibbs) -> c_int;
+    pub fn fg_gibbs_n_sites(g: *const fg_gibbs) -> c_int;
+    pub fn fg_gibbs_n_cells(g: *const fg_gibbs) -> i64;
+    pub fn fg_gibbs_layout(g: *const fg_gibbs, h_site: *mut i32, h_lo: *mut i64, h_K: *mut i32, h_cell0: *mut i64) -> c_int;
+    pub fn fg_gibbs_sweep(g: *mut fg_gibbs, n_sweeps: c_int, h_rec_sites: *const i32, n_rec: c_int, d_rec: *mut i64, d_scores: *mut f64, d_cond: *mut f64) -> c_int;
+    pub fn fg_gibbs_count(g: *const fg_gibbs) -> i64;
+    pub fn fg_gibbs_seek(g: *mut fg_gibbs, t: i64) -> c_int;
+    pub fn fg_gibbs_stats(g: *mut fg_gibbs, h_counts: *mut i64) -> c_int;
+    pub fn fg_gibbs_probs(g: *mut fg_gibbs, h_mean: *mut f64, h_n: *mut i64) -> c_int;
+    pub fn fg_gibbs_free(g: *mut fg_gibbs);
     pub fn fg_diag_exchange_bytes(e: *const fg_engine) -> i64;
     pub fn fg_comm_unique_id(out_128_bytes: *mut c_void) -> c_int;
     pub fn fg_comm_init(e: *mut fg_engine, world: c_int, rank: c_int, id_128_bytes: *const c_void, out_comm: *mut *mut c_void) -> c_int;
