@@ -264,7 +264,8 @@ FG_HD double fg_logpdf(uint32_t kind, bool hoisted, bool pow2, double xf, long l
 // in the parameterisations of distribution.rs (Gamma(shape, rate), InverseGamma(shape, scale), Weibull(shape, scale), StudentT(df, loc,
 // scale), Exponential(rate)).  NaN where the density is not finite (outside the support, invalid parameters, an endpoint with infinite
 // density): the force is then non-finite and the transition diverges, as with the finite difference of a -inf log-joint.  Discrete
-// values have no dx.  fg_digamma: recurrence up to 6, then the asymptotic series (|error| < 1e-12 for x > 0).
+// values have no dx.  fg_digamma: recurrence up to 6, then the asymptotic series (|error| < 1e-12 max(1, |psi(x)|) for x > 0: relative
+// for small x, where psi ~ -1/x -- the absolute error there is an ulp of psi, 1.5e-8 at x = 1e-8; tests/test_gpu_math_exact.py).
 // ---------------------------------------------------------------------------------------
 FG_HD double fg_digamma(double x) {
     if (!(x > 0.0) || !fg_finite(x)) return NAN;

@@ -95,3 +95,68 @@ extern "C" int fg_debug_rng_pairs(int mode, long long n, unsigned long long seed
     if (d_out) (void)hipFree(d_out);
     return rc;
 }
+
+// fg_debug_math -- the device's arithmetic primitives on the caller's operands, for tests/test_gpu_math_exact.py, which holds them to exact
+// values (tests/golden/math_exact.json).  out: FG_DEBUG_MATH_ROWS rows of n 64-bit cells (doubles as their bits); rows an op does not
+// name stay zero.  a, b, c: host arrays of n doubles (PAIR: a, b are the two 64-bit words of a Philox block).
+// op 0 DIV (a, b, c = 1.0 / b formed on the host, as fg_program.cpp does): 0 fg_div_const(a, b, c) | 1 a / b
+// op 1 LOG (a):      0 fg_fast_log_t<false> | 1 fg_fast_log_t<true> | 2 log
+// op 2 SINCOS (a):   0, 1 sin, cos of fg_fast_sincos_t<false> | 2, 3 of fg_fast_sincos_t<true>
+// op 3 PAIR (a, b):  0, 1 fg_normal_pair_of<false> | 2, 3 fg_normal_pair_of<true> | 4 fg_gaussian_z_of
+// op 4 OCML (a, b):  0 log(a) | 1 log1p(a) | 2 lgamma(a) | 3 exp(a) | 4 pow(a, b) | 5 tan(a) -- what fg_logpdf and the samplers call
+// op 5 DIGAMMA (a):  0 fg_digamma
+#define FG_DEBUG_MATH_ROWS 6
+#define FG_DEBUG_MATH_OPS 6
+__global__ __launch_bounds__(256) void k_debug_math(int op, long long n, const double *a, const double *b, const double *c, unsigned long long *out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    auto put = [&](int row, double v) { out[(long long)row * n + i] = (unsigned long long)fg_as_i64(v); };
+    if (op == 0) {
+        const double x = a[i], d = b[i];
+        put(0, fg_div_const(x, d, c[i])); put(1, x / d);
+    } else if (op == 1) {
+        const double x = a[i];
+        put(0, fg_fast_log_t<false>(x)); put(1, fg_fast_log_t<true>(x)); put(2, log(x));
+    } else if (op == 2) {
+        const double x = a[i];
+        double sn, cs;
+        fg_fast_sincos_t<false>(x, sn, cs); put(0, sn); put(1, cs);
+        fg_fast_sincos_t<true>(x, sn, cs); put(2, sn); put(3, cs);
+    } else if (op == 3) {
+        const unsigned long long wa = (unsigned long long)fg_as_i64(a[i]), wb = (unsigned long long)fg_as_i64(b[i]);
+        double z0, z1;
+        fg_normal_pair_of<false>(wa, wb, z0, z1); put(0, z0); put(1, z1);
+        fg_normal_pair_of<true>(wa, wb, z0, z1); put(2, z0); put(3, z1);
+        put(4, fg_gaussian_z_of(wa, wb));
+    } else if (op == 4) {
+        const double x = a[i];
+        put(0, log(x)); put(1, log1p(x)); put(2, fg_lgamma(x)); put(3, exp(x)); put(4, pow(x, b[i])); put(5, tan(x));
+    } else {
+        put(0, fg_digamma(a[i]));
+    }
+}
+
+// Host side: out is a host buffer of FG_DEBUG_MATH_ROWS * n cells; a (every op), b (DIV, PAIR, OCML) and c (DIV) are host arrays of n doubles.
+extern "C" int fg_debug_math(int op, long long n, const double *a, const double *b, const double *c, unsigned long long *out) {
+    if (n <= 0 || op < 0 || op >= FG_DEBUG_MATH_OPS || !out || !a || ((op == 0 || op == 3 || op == 4) && !b) || (op == 0 && !c)) return -1;
+    double *d_in[3] = {nullptr, nullptr, nullptr};
+    const double *h_in[3] = {a, b, c};
+    unsigned long long *d_out = nullptr;
+    const size_t wbytes = (size_t)n * 8, obytes = (size_t)FG_DEBUG_MATH_ROWS * wbytes;
+    int rc = -1;
+    do {
+        if (hipMalloc(&d_out, obytes) != hipSuccess || hipMemset(d_out, 0, obytes) != hipSuccess) break;
+        bool ok = true;
+        for (int k = 0; k < 3 && ok; k++)
+            if (h_in[k]) ok = hipMalloc(&d_in[k], wbytes) == hipSuccess && hipMemcpy(d_in[k], h_in[k], wbytes, hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) break;
+        hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, n, d_in[0], d_in[1], d_in[2], d_out);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) break;
+        if (hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost) != hipSuccess) break;
+        rc = 0;
+    } while (0);
+    for (int k = 0; k < 3; k++)
+        if (d_in[k]) (void)hipFree(d_in[k]);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}
